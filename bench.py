@@ -17,7 +17,12 @@ cpu_baseline, one scalar per secondary leg); a few short per-leg lines precede i
 ports, notes, samples) goes to bench_detail.json next to this file (and to gpurun_out/ when that exists).
 What the fields mean is written once, in DESIGN.md section 5.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n-sketches 100000] [--n-genomes 10000]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n-sketches 100000] [--n-genomes 10000] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: the table, the warm-up steps, the K timed steps and the line (no roofline,
+no warm rate, no checksum, no secondary legs).  --full adds everything else, as described above and in DESIGN.md section 5:
+roofline and warm rate, the checksum assert, the CPU baselines, brackets, host-to-host, sketch, screen, C5 and CLI legs
+(the --no-* options drop single legs of it).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import hashlib
@@ -63,7 +68,17 @@ def parse_args():
     ap.add_argument("--detail", default=None, help="where the full result goes (default: bench_detail.json next to this file, and gpurun_out/)")
     ap.add_argument("--dry-cpu", action="store_true",
                     help="plumbing test only (CI without GPUs): gloo + CPU tensors, no kernels, output marked dry")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (roofline, warm rate, checksum, CPU baselines, "
+                         "secondary legs; the --no-* options apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of the last step's {numer, denom} and their sums as DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_cpu:
+        ap.error("--dump-outputs needs the kernels: --dry-cpu computes nothing")
+    return args
 
 
 def src_sha(*rel):
@@ -314,6 +329,38 @@ def cpu_baseline_sketch_cli(n_genomes, threads):
         subprocess.run(["rm", "-rf", d])
 
 
+DUMP_PAIRS = 1 << 21            # pairs sampled by --dump-outputs: 2 x float32 + a float64 index each = 32 MiB
+
+
+def dump_outputs(path, out, rb, re, total_pairs, dev, world, rank):
+    """--dump-outputs: what the timed path computed in its last step, every pair's {numer, denom} (out of
+    mg_compare_tri_dev, reference order: pair (i, j), j < i, at i*(i-1)/2 + j), as .npy files in `path`:
+    pair_index / numer / denom for a fixed, seeded sample of DUMP_PAIRS pairs (all pairs of a smaller triangle), and
+    sums = [sum of numer, sum of denom] over every pair.  Each rank contributes the pairs of its row block."""
+    import torch
+    import torch.distributed as dist
+    from mash_amd import shard
+    if total_pairs <= DUMP_PAIRS:
+        idx = np.arange(total_pairs, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(20261016).integers(0, total_pairs, DUMP_PAIRS, dtype=np.int64))
+    lo, hi = shard.tri_pairs(0, rb), shard.tri_pairs(0, re)
+    mine = (idx >= lo) & (idx < hi)
+    got = torch.zeros((len(idx), 2), dtype=torch.int32, device=dev)
+    got[torch.from_numpy(np.nonzero(mine)[0]).to(dev)] = out[torch.from_numpy(idx[mine] - lo).to(dev)]
+    sums = torch.stack([out[:hi - lo, 0].sum(dtype=torch.int64), out[:hi - lo, 1].sum(dtype=torch.int64)])
+    if world > 1:
+        dist.all_reduce(got)
+        dist.all_reduce(sums)
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        got = got.cpu().numpy()
+        np.save(os.path.join(path, "pair_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, "numer.npy"), got[:, 0].astype(np.float32))
+        np.save(os.path.join(path, "denom.npy"), got[:, 1].astype(np.float32))
+        np.save(os.path.join(path, "sums.npy"), sums.cpu().numpy().astype(np.float64))
+
+
 def _num(x, digits=4):
     """Short float for the headline line."""
     if x is None or isinstance(x, (str, bool, int)):
@@ -411,6 +458,7 @@ def emit(result, detail_path=None):
 
 def main():
     args = parse_args()
+    full = args.full
     import torch
     import torch.distributed as dist
     from mash_amd import abi, shard
@@ -598,53 +646,55 @@ def main():
     for w in range(args.warmup):
         tw = time.perf_counter()
         cold_step()
-        if w == 0 and not dry:
+        if w == 0 and full and not dry:
             torch.cuda.synchronize()
             first_call_ms = (time.perf_counter() - tw) * 1e3    # the very first call of the process: also pays the hipMallocs
-    eng.prof_enable(True)
-    eng.prof_reset()
+    if full:
+        eng.prof_enable(True)
+        eng.prof_reset()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         cold_step()
     barrier()
-    dt = time.perf_counter() - t0
+    dt = max_over_ranks(time.perf_counter() - t0)
+    value = total_pairs * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rb, re, total_pairs, dev, world, rank)
     srcs = ("mash_amd/csrc/compare_sparse.hip", "mash_amd/csrc/compare_dense.hip", "mash_amd/csrc/compare_merged.hip", "mash_amd/csrc/compare_internal.h",
             "mash_amd/csrc/index_build.hip", "mash_amd/csrc/compare_join.hip")
-    pmc = load_pmc("compare_c3_cold_pmc.json", *srcs) if (n == 100_000 and world == 1 and not dry) else None
-    roofline = compare_roofline(eng, my_pairs, n, S, args.steps, pmc) if not dry else {"bound": "hbm", "dry": True}
-    dt = max_over_ranks(dt)
-    value = total_pairs * args.steps / dt
-    # what every rank's index cost (a rank's index covers the rows below its block's end only: host_compare.cpp tri_view)
-    index_ms_by_rank = None
-    if world > 1:
-        mine = 0.0 if dry else float((roofline.get("phases") or {}).get("index", {}).get("ms_per_pass") or 0.0)
-        tens = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
-        dist.all_gather(tens, torch.tensor([mine], dtype=torch.float64, device=dev))
-        index_ms_by_rank = [round(float(x.item()), 3) for x in tens]
-    if not dry and "pass" in roofline:
-        roofline["step_frac"] = round(roofline["pass"]["compulsory_bytes"] / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)
-        roofline["index_ms"] = roofline["phases"].get("index", {}).get("ms_per_pass")
-    # further passes over the same table (index and plan exist): the warm rate
-    eng.prof_reset()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    wdt = max_over_ranks(time.perf_counter() - t0)
-    pmc_w = load_pmc("compare_c3_pmc.json", *srcs) if (n == 100_000 and world == 1 and not dry) else None
-    roofline_warm = compare_roofline(eng, my_pairs, n, S, args.steps, pmc_w) if not dry else None
-    eng.prof_enable(False)
-    # the dominant kernel BY ITSELF (a further pass over the indexed table launches it once, nothing beside it): what the
-    # per-table step's paced launches are to be read against
-    if roofline_warm and roofline.get("beside") and roofline_warm.get("kernel") == "mg::sp_fill_value_kernel":
-        roofline["alone"] = {"kernel": roofline_warm["kernel"], "kernel_ms": roofline_warm["kernel_ms"], "achieved": roofline_warm["achieved"],
-                             "frac": roofline_warm["frac"]}
+    roofline = roofline_warm = index_ms_by_rank = checksum = wdt = None
+    if full:
+        pmc = load_pmc("compare_c3_cold_pmc.json", *srcs) if (n == 100_000 and world == 1 and not dry) else None
+        roofline = compare_roofline(eng, my_pairs, n, S, args.steps, pmc) if not dry else {"bound": "hbm", "dry": True}
+        # what every rank's index cost (a rank's index covers the rows below its block's end only: host_compare.cpp tri_view)
+        if world > 1:
+            mine = 0.0 if dry else float((roofline.get("phases") or {}).get("index", {}).get("ms_per_pass") or 0.0)
+            tens = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
+            dist.all_gather(tens, torch.tensor([mine], dtype=torch.float64, device=dev))
+            index_ms_by_rank = [round(float(x.item()), 3) for x in tens]
+        if not dry and "pass" in roofline:
+            roofline["step_frac"] = round(roofline["pass"]["compulsory_bytes"] / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)
+            roofline["index_ms"] = roofline["phases"].get("index", {}).get("ms_per_pass")
+        # further passes over the same table (index and plan exist): the warm rate
+        eng.prof_reset()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        wdt = max_over_ranks(time.perf_counter() - t0)
+        pmc_w = load_pmc("compare_c3_pmc.json", *srcs) if (n == 100_000 and world == 1 and not dry) else None
+        roofline_warm = compare_roofline(eng, my_pairs, n, S, args.steps, pmc_w) if not dry else None
+        eng.prof_enable(False)
+        # the dominant kernel BY ITSELF (a further pass over the indexed table launches it once, nothing beside it): what the
+        # per-table step's paced launches are to be read against
+        if roofline_warm and roofline.get("beside") and roofline_warm.get("kernel") == "mg::sp_fill_value_kernel":
+            roofline["alone"] = {"kernel": roofline_warm["kernel"], "kernel_ms": roofline_warm["kernel_ms"], "achieved": roofline_warm["achieved"],
+                                 "frac": roofline_warm["frac"]}
 
     # the produced output (outside the timed region): every pair's denom and numer, as sums
-    checksum = None
-    if not dry:
+    if full and not dry:
         sums = torch.stack([out[:my_pairs, 0].sum(dtype=torch.int64), out[:my_pairs, 1].sum(dtype=torch.int64)])
         if world > 1:
             dist.all_reduce(sums)
@@ -667,14 +717,15 @@ def main():
                    "table_broadcast_ms": round(bcast_ms, 2), "index_ms_by_rank": index_ms_by_rank,
                    "rccl_ranks": rccl_ranks, "comm": comm_kind, "output_checksum": checksum,
                    "first_call_ms": round(first_call_ms, 2) if first_call_ms is not None else None},
-        "warm_value": total_pairs * args.steps / wdt, "warm_ms_per_step": wdt * 1e3 / args.steps,
-        "roofline": roofline, "roofline_warm": roofline_warm,
     }
+    if full:
+        result.update({"warm_value": total_pairs * args.steps / wdt, "warm_ms_per_step": wdt * 1e3 / args.steps,
+                       "roofline": roofline, "roofline_warm": roofline_warm})
     if dry:
         result["dry"] = True               # plumbing test: NOT a measurement
         result["rank_blocks"] = blocks
 
-    single = rank == 0 and world == 1 and not dry
+    single = full and rank == 0 and world == 1 and not dry
     # ------------------------------------------------------------------ cpu baseline (rank 0, N=1)
     if single and not args.no_cpu:
         m = min(n, 40000)
@@ -869,7 +920,7 @@ def main():
         result["host_to_host"] = h2h
 
     # ------------------------------------------------------------------ secondary: sketching (config 2)
-    if not args.no_sketch and not dry:
+    if full and not args.no_sketch and not dry:
         g_blocks = shard.even_blocks(args.n_genomes, world)
         g0, g1 = g_blocks[rank], g_blocks[rank + 1]
         ng, L = g1 - g0, args.genome_len
@@ -975,7 +1026,7 @@ def main():
     # by batch; the one collective is the all-reduce of the observation counters (RCCL) plus
     # an all-gather of the per-rank mixture sketches (mash_amd/screen_dist.py).  A step is the
     # whole job: table build, every batch, counters gathered + exchanged.
-    if not args.no_screen and not dry:
+    if full and not args.no_screen and not dry:
         import gc
         gc.collect()
         torch.cuda.empty_cache()

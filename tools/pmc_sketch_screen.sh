@@ -6,8 +6,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $ROOT/bench.py --no-cpu --no-h2h --no-screen --no-c5 --no-cli --no-brackets --steps 1 --warmup 0 --detail /tmp/d1.json"
-BS="python $ROOT/bench.py --no-cpu --no-h2h --no-sketch --no-c5 --no-cli --no-brackets --steps 1 --warmup 0 --detail /tmp/d2.json"
+B="python $ROOT/bench.py --full --no-cpu --no-h2h --no-screen --no-c5 --no-cli --no-brackets --steps 1 --warmup 0 --detail /tmp/d1.json"
+BS="python $ROOT/bench.py --full --no-cpu --no-h2h --no-sketch --no-c5 --no-cli --no-brackets --steps 1 --warmup 0 --detail /tmp/d2.json"
 run() { local name=$1; shift; rm -rf "$OUT/r05k_${name}"; timeout 300 rocprofv3 "$@" > "$OUT/r05k_${name}.log" 2>&1; echo "$name rc=$?"; }
 run fetch --pmc FETCH_SIZE --output-format csv -d "$OUT/r05k_fetch" -o p -- $B
 run write --pmc WRITE_SIZE --output-format csv -d "$OUT/r05k_write" -o p -- $B

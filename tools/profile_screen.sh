@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BS="python $ROOT/bench.py --no-cpu --no-h2h --no-sketch --no-c5 --no-cli --no-brackets --steps 1 --warmup 0 --detail /tmp/screen_detail.json"
+BS="python $ROOT/bench.py --full --no-cpu --no-h2h --no-sketch --no-c5 --no-cli --no-brackets --steps 1 --warmup 0 --detail /tmp/screen_detail.json"
 rm -rf $OUT/r04_s_fetch $OUT/r04_s_write
 timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/r04_s_fetch -o p -- $BS > $OUT/r04_s_fetch.log 2>&1; echo "fetch rc=$?"
 timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/r04_s_write -o p -- $BS > $OUT/r04_s_write.log 2>&1; echo "write rc=$?"

@@ -30,8 +30,8 @@ for w in c3 one_species; do timeout 300 python tools/ranks_on_one_gpu.py $w 8 > 
 timeout 600 python tools/species_engines.py > gpurun_out/${TAG}_species_engines.txt 2>/dev/null; tail -2 gpurun_out/${TAG}_species_engines.txt | cut -c1-300
 timeout 600 python tools/compare_e2e.py > gpurun_out/${TAG}_compare_e2e.json 2>/dev/null; tail -1 gpurun_out/${TAG}_compare_e2e.json | cut -c1-300
 for w in c3 c5; do timeout 300 python tools/range_check.py $w 50000 100000 > gpurun_out/${TAG}_range_$w.txt 2>/dev/null; tail -1 gpurun_out/${TAG}_range_$w.txt; done
-timeout 1500 python bench.py --detail gpurun_out/${TAG}_bench_detail.json > gpurun_out/${TAG}_bench_line.json 2> gpurun_out/${TAG}_bench_stderr.log
-echo "bench rc=$?"; tail -1 gpurun_out/${TAG}_bench_line.json | cut -c1-3500
+# (the detail goes where bench.py puts it by default; the headline is the last line printed here)
+timeout 1500 python bench.py --full 2>&1 | tail -8 | cut -c1-3500; echo "bench rc=${PIPESTATUS[0]}"
 # what travels back: summaries only (64 MiB at most)
 find gpurun_out -name "*kernel_trace.csv" -delete 2>/dev/null
 for d in gpurun_out/${TAG}_*_fetch gpurun_out/${TAG}_*_write gpurun_out/${TAG}_*_sqa gpurun_out/${TAG}_*_sqb gpurun_out/${TAG}_*_sqc; do [ -d "$d" ] && rm -rf "$d"; done

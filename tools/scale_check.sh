@@ -66,10 +66,10 @@ echo "== 3. bench.py over N"
 for N in 1 2 4 8; do
     [ $N -gt $NG ] && break
     if [ $N -eq 1 ]; then
-        python bench.py --gpus 1 --steps 3 --warmup 1 --no-sketch --no-screen --no-c5 --no-h2h --no-brackets --no-cpu > $OUT/n$N.json 2> $OUT/n$N.err || fail=1
+        python bench.py --gpus 1 --steps 3 --warmup 1 --full --no-sketch --no-screen --no-c5 --no-h2h --no-brackets --no-cpu > $OUT/n$N.json 2> $OUT/n$N.err || fail=1
     else
         python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-            bench.py --gpus $N --steps 3 --warmup 1 --no-sketch --no-screen --no-c5 --no-h2h --no-brackets --no-cpu > $OUT/n$N.json 2> $OUT/n$N.err || fail=1
+            bench.py --gpus $N --steps 3 --warmup 1 --full --no-sketch --no-screen --no-c5 --no-h2h --no-brackets --no-cpu > $OUT/n$N.json 2> $OUT/n$N.err || fail=1
     fi
     grep '^{' $OUT/n$N.json | tail -1 >> $OUT/scale.jsonl
 done
