@@ -273,6 +273,23 @@ void mg_dtable_free(mg_dtable *d)
     delete d;
 }
 
+// fn(g) for every device g of the communicator, each on a host thread of its own (one device: on the calling thread); the
+// first failing device's error, in device order, becomes the communicator's
+template <class F>
+static int per_device(mg_comm *c, F fn)
+{
+    const size_t G = c->ctxs.size();
+    std::vector<int> rcs(G, MG_OK);
+    std::vector<std::thread> th;
+    for (size_t g = 0; g < G; g++) {
+        if (G == 1) rcs[g] = fn(g); else th.emplace_back([&, g]() { rcs[g] = fn(g); });
+    }
+    for (auto &t : th) t.join();
+    for (size_t g = 0; g < G; g++)
+        if (rcs[g] != MG_OK) { c->err = c->ctxs[g]->err; return rcs[g]; }
+    return MG_OK;
+}
+
 // The LARGER side of a rect job need not be replicated: every device gets a block of consecutive rows
 // (host -> each GPU its own rows, no exchange).  Such a table is the reference side of
 // mg_compare_rect_*_sharded_host, which then splits the job by reference rows ("broadcast
@@ -296,19 +313,12 @@ int mg_dtable_upload_rows(mg_comm *c, const uint64_t *hashes, const uint32_t *nh
         d->row0[(size_t)g + 1] = hi;
     }
     d->t.assign((size_t)G, nullptr);
-    std::vector<int> rcs((size_t)G, MG_OK);
-    std::vector<std::thread> th;
-    auto up = [&](int g) {
-        const uint64_t lo = d->row0[(size_t)g], hi = d->row0[(size_t)g + 1];
+    const int rc = per_device(c, [&](size_t g) {
+        const uint64_t lo = d->row0[g], hi = d->row0[g + 1];
         // (an empty block still gets a table: one padding row, zero rows visible)
-        rcs[(size_t)g] = mg_table_upload(c->ctxs[(size_t)g], hashes + lo * s, nhash + lo, lengths ? lengths + lo : nullptr, hi - lo, s, &d->t[(size_t)g]);
-    };
-    for (int g = 0; g < G; g++) {
-        if (G == 1) up(g); else th.emplace_back(up, g);
-    }
-    for (auto &t : th) t.join();
-    for (int g = 0; g < G; g++)
-        if (rcs[(size_t)g] != MG_OK) { c->err = c->ctxs[(size_t)g]->err; const int rc = rcs[(size_t)g]; mg_dtable_free(d); return rc; }
+        return mg_table_upload(c->ctxs[g], hashes + lo * s, nhash + lo, lengths ? lengths + lo : nullptr, hi - lo, s, &d->t[g]);
+    });
+    if (rc != MG_OK) { mg_dtable_free(d); return rc; }
     *out = d;
     return MG_OK;
 }
@@ -392,19 +402,10 @@ static int sharded_blocks(mg_comm *c, uint64_t rb, uint64_t re, bool triangle, u
         else mg_shard_rows(rb, re, G, std::min(g, G - 1), &lo, &hi);
         b[(size_t)g] = g < G ? lo : hi;
     }
-    std::vector<int> rcs((size_t)G, MG_OK);
-    std::vector<std::thread> th;
-    for (int g = 0; g < G; g++) {
-        const uint64_t lo = b[(size_t)g], hi = b[(size_t)g + 1];
-        const uint64_t before = triangle ? tri_pairs(rb, lo) : (lo - rb) * ncols;
-        if (lo >= hi) continue;
-        if (G == 1) rcs[0] = fn(0, lo, hi, before);
-        else th.emplace_back([&, g, lo, hi, before]() { rcs[(size_t)g] = fn(g, lo, hi, before); });
-    }
-    for (auto &t : th) t.join();
-    for (int g = 0; g < G; g++)
-        if (rcs[(size_t)g] != MG_OK) { c->err = c->ctxs[(size_t)g]->err; return rcs[(size_t)g]; }
-    return MG_OK;
+    return per_device(c, [&](size_t g) {
+        const uint64_t lo = b[g], hi = b[g + 1];
+        return lo < hi ? fn((int)g, lo, hi, triangle ? tri_pairs(rb, lo) : (lo - rb) * ncols) : MG_OK;
+    });
 }
 
 int dtable_check(mg_comm *c, const mg_dtable *t, const char *who, bool rows_ok)
@@ -449,15 +450,12 @@ static int ref_block(mg_comm *c, const mg_dtable *ref, size_t g, const mg_table 
 template <class T, class Call>
 static int rect_by_ref_rows(mg_comm *c, const mg_dtable *ref, const mg_dtable *qry, uint64_t q_begin, uint64_t q_end, T *out_host, Call call)
 {
-    const size_t G = c->ctxs.size();
     const uint64_t nref = ref->by_rows ? ref->n : ref->t[0]->n;
-    std::vector<int> rcs(G, MG_OK);
-    std::vector<std::thread> th;
-    auto work = [&](size_t g) {
+    return per_device(c, [&](size_t g) {
         const mg_table *blk = nullptr;
         uint64_t lo = 0, hi = 0;
         int rc = ref_block(c, ref, g, &blk, &lo, &hi);
-        if (rc != MG_OK || lo >= hi) { rcs[g] = rc; return; }
+        if (rc != MG_OK || lo >= hi) return rc;
         const uint64_t w = hi - lo;
         // queries in blocks that bound the staging buffer (256 MiB)
         const uint64_t qstep = std::max<uint64_t>(1, (256ull << 20) / (w * sizeof(T)));
@@ -469,15 +467,8 @@ static int rect_by_ref_rows(mg_comm *c, const mg_dtable *ref, const mg_dtable *q
             for (uint64_t q = q0; q < q1 && rc == MG_OK; q++)
                 memcpy(out_host + (q - q_begin) * nref + lo, tmp.data() + (q - q0) * w, w * sizeof(T));
         }
-        rcs[g] = rc;
-    };
-    for (size_t g = 0; g < G; g++) {
-        if (G == 1) work(g); else th.emplace_back(work, g);
-    }
-    for (auto &t : th) t.join();
-    for (size_t g = 0; g < G; g++)
-        if (rcs[g] != MG_OK) { c->err = c->ctxs[g]->err; return rcs[g]; }
-    return MG_OK;
+        return rc;
+    });
 }
 
 // which side of a rect job is cut: the reference rows when that table is row-sharded or the larger side
@@ -552,30 +543,43 @@ int mg_compare_rect_pairs_sharded_host(mg_comm *c, const mg_dtable *ref, const m
     });
 }
 
+// One device's survivors: call(out, capacity, count) into 2^16 records, once more with exactly the count reported if that was
+// too few.  v holds the list (nothing after an error).
+template <class Call>
+static int collect_results(std::vector<mg_result> &v, Call call)
+{
+    v.resize(1u << 16);
+    uint64_t n = 0;
+    int r = call(v.data(), (uint64_t)v.size(), &n);
+    if (r == MG_ERR_NOMEM && n > v.size()) {
+        v.resize(n);
+        r = call(v.data(), (uint64_t)v.size(), &n);
+    }
+    v.resize(r == MG_OK ? n : 0);
+    return r;
+}
+
+// the devices' lists hold *count_out records in all; more than `capacity`: MG_ERR_NOMEM
+static int results_total(mg_comm *c, const std::vector<std::vector<mg_result>> &part, uint64_t capacity, uint64_t *count_out)
+{
+    uint64_t total = 0;
+    for (auto &v : part) total += v.size();
+    *count_out = total;
+    if (total > capacity) return comm_fail(c, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
+    return MG_OK;
+}
+
 // survivors of both filters: every GPU collects its block's list, the lists are joined in block (= reference) order
 template <class Call>
 static int sharded_results(mg_comm *c, uint64_t rb, uint64_t re, bool triangle, uint64_t ncols, mg_result *out_host,
                            uint64_t capacity, uint64_t *count_out, Call call, double row_weight = 0.0)
 {
-    const size_t G = c->ctxs.size();
-    std::vector<std::vector<mg_result>> part(G);
-    const int rc = sharded_blocks(c, rb, re, triangle, ncols, [&](int g, uint64_t lo, uint64_t hi, uint64_t) {
-        std::vector<mg_result> &v = part[(size_t)g];
-        v.resize(1u << 16);
-        uint64_t n = 0;
-        int r = call(g, lo, hi, v.data(), (uint64_t)v.size(), &n);
-        if (r == MG_ERR_NOMEM && n > v.size()) {
-            v.resize(n);
-            r = call(g, lo, hi, v.data(), (uint64_t)v.size(), &n);
-        }
-        v.resize(r == MG_OK ? n : 0);
-        return r;
+    std::vector<std::vector<mg_result>> part(c->ctxs.size());
+    int rc = sharded_blocks(c, rb, re, triangle, ncols, [&](int g, uint64_t lo, uint64_t hi, uint64_t) {
+        return collect_results(part[(size_t)g], [&](mg_result *o, uint64_t cap, uint64_t *n) { return call(g, lo, hi, o, cap, n); });
     }, row_weight);
+    if (rc == MG_OK) rc = results_total(c, part, capacity, count_out);
     if (rc != MG_OK) return rc;
-    uint64_t total = 0;
-    for (auto &v : part) total += v.size();
-    *count_out = total;
-    if (total > capacity) return comm_fail(c, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
     uint64_t at = 0;
     for (auto &v : part) {
         if (!v.empty()) memcpy(out_host + at, v.data(), v.size() * sizeof(mg_result));
@@ -618,37 +622,18 @@ int mg_compare_rect_results_sharded_host(mg_comm *c, const mg_dtable *ref, const
         const size_t G = c->ctxs.size();
         std::vector<std::vector<mg_result>> part(G);
         std::vector<uint64_t> lo_of(G, 0);
-        std::vector<int> rcs(G, MG_OK);
-        std::vector<std::thread> th;
-        auto work = [&](size_t g) {
+        rc = per_device(c, [&](size_t g) {
             const mg_table *blk = nullptr;
-            uint64_t lo = 0, hi = 0;
-            int r = ref_block(c, ref, g, &blk, &lo, &hi);
-            lo_of[g] = lo;
-            if (r != MG_OK || lo >= hi) { rcs[g] = r; return; }
-            std::vector<mg_result> &v = part[g];
-            v.resize(1u << 16);
-            uint64_t n = 0;
-            r = mg_compare_rect_results_host(c->ctxs[g], blk, qry->t[g], q_begin, q_end, kmer_size, kmer_space, max_distance, max_p_value,
-                                             v.data(), (uint64_t)v.size(), &n);
-            if (r == MG_ERR_NOMEM && n > v.size()) {
-                v.resize(n);
-                r = mg_compare_rect_results_host(c->ctxs[g], blk, qry->t[g], q_begin, q_end, kmer_size, kmer_space, max_distance, max_p_value,
-                                                 v.data(), (uint64_t)v.size(), &n);
-            }
-            v.resize(r == MG_OK ? n : 0);
-            rcs[g] = r;
-        };
-        for (size_t g = 0; g < G; g++) {
-            if (G == 1) work(g); else th.emplace_back(work, g);
-        }
-        for (auto &t : th) t.join();
-        for (size_t g = 0; g < G; g++)
-            if (rcs[g] != MG_OK) { c->err = c->ctxs[g]->err; return rcs[g]; }
-        uint64_t total = 0;
-        for (auto &v : part) total += v.size();
-        *count_out = total;
-        if (total > capacity) return comm_fail(c, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
+            uint64_t hi = 0;
+            const int r = ref_block(c, ref, g, &blk, &lo_of[g], &hi);
+            if (r != MG_OK || lo_of[g] >= hi) return r;
+            return collect_results(part[g], [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                return mg_compare_rect_results_host(c->ctxs[g], blk, qry->t[g], q_begin, q_end, kmer_size, kmer_space, max_distance,
+                                                    max_p_value, o, cap, n);
+            });
+        });
+        if (rc == MG_OK) rc = results_total(c, part, capacity, count_out);
+        if (rc != MG_OK) return rc;
         std::vector<size_t> cur(G, 0);
         uint64_t at = 0;
         for (uint64_t q = q_begin; q < q_end; q++)                 // (rows of the results are query indices)
@@ -691,23 +676,14 @@ int mg_sketch_sharded_host(mg_comm *c, const mg_params *p, const uint8_t *bases,
         b[g] = (uint64_t)(std::lower_bound(sketch_off, sketch_off + nsketch, want) - sketch_off);
         if (b[g] < b[g - 1]) b[g] = b[g - 1];
     }
-    std::vector<int> rcs(G, MG_OK);
-    std::vector<std::thread> th;
-    auto work = [&](size_t g) {
+    return per_device(c, [&](size_t g) {
         const uint64_t k0 = b[g], k1 = b[g + 1];
-        if (k0 >= k1) return;
+        if (k0 >= k1) return MG_OK;
         const uint64_t base = sketch_off[k0];
         std::vector<uint64_t> off(k1 - k0 + 1);
         for (uint64_t k = k0; k <= k1; k++) off[k - k0] = sketch_off[k] - base;
-        rcs[g] = mg_sketch_host(c->ctxs[g], p, bases + base, off.back(), off.data(), k1 - k0, hashes_out + k0 * s, nhash_out + k0,
-                                counts_out ? counts_out + k0 * s : nullptr);
-    };
-    for (size_t g = 0; g < G; g++) {
-        if (G == 1) work(g); else th.emplace_back(work, g);
-    }
-    for (auto &t : th) t.join();
-    for (size_t g = 0; g < G; g++)
-        if (rcs[g] != MG_OK) { c->err = c->ctxs[g]->err; return rcs[g]; }
-    return MG_OK;
+        return mg_sketch_host(c->ctxs[g], p, bases + base, off.back(), off.data(), k1 - k0, hashes_out + k0 * s, nhash_out + k0,
+                              counts_out ? counts_out + k0 * s : nullptr);
+    });
 }
 

@@ -1479,47 +1479,75 @@ int mg_compare_rect_dev(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, u
     return MG_OK;
 }
 
-// host-output variants: bounded device staging, processed in row blocks
-static int compare_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re,
-                        bool triangle, mg_counts *out_host)
+/* ------------------------------------------------- host outputs: range set-up, row blocks */
+
+// What every host-output call starts from: [rb, re) clamped to the rows, the view a triangle of one table is served from
+// (tri_view: the first re rows are all such a call looks at), s, and the pairs of the range.
+struct OutRange {
+    const mg_table *rows, *cols;
+    uint64_t rb, re, pairs;
+    uint32_t s;
+    bool triangle;
+    bool empty() const { return rb >= re; }
+};
+
+static int out_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle, OutRange *o,
+                     uint64_t max_s = 0xFFFFFFFEull)
 {
-    if (re > rows->n) re = rows->n;
-    if (rb >= re) return MG_OK;
-    if (triangle && rows == cols) rows = cols = tri_view(ctx, cols, rb, re);
+    *o = {rows, cols, rb, std::min(re, rows->n), 0, 0, triangle};
+    if (o->empty()) return MG_OK;
+    if (triangle && rows == cols) o->rows = o->cols = tri_view(ctx, cols, rb, o->re);
+    const uint64_t s64 = std::min(o->rows->s, o->cols->s);
+    if (s64 > max_s) return fail(ctx, MG_ERR_INVALID, "compare: sketch size too large");
+    o->s = (uint32_t)s64;
+    o->pairs = triangle ? tri_pairs(rb, o->re) : (o->re - rb) * o->cols->n;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t max_pairs = 1ull << 27;                 // 1 GiB of {numer,denom}
-    mg_counts *d_out = nullptr;
-    uint64_t done = 0, r = rb;
-    uint64_t cap_pairs = 0;
-    int rc = MG_OK;
-    while (r < re && rc == MG_OK) {
+    return MG_OK;
+}
+
+// rows [r, r2): `pairs` pairs, `before` pairs of the range ahead of them
+struct RowBlock { uint64_t r, r2, pairs, before; };
+
+// The range in blocks of whole rows of at most max_pairs pairs (a block always takes its first row); *largest: the pairs of the
+// largest block, which the caller's device buffers hold
+static std::vector<RowBlock> row_blocks(const OutRange &R, uint64_t max_pairs, uint64_t *largest)
+{
+    std::vector<RowBlock> v;
+    *largest = 0;
+    for (uint64_t r = R.rb, before = 0; r < R.re;) {
         uint64_t r2 = r, pairs = 0;
-        while (r2 < re) {
-            const uint64_t add = triangle ? r2 : cols->n;
+        while (r2 < R.re) {
+            const uint64_t add = R.triangle ? r2 : R.cols->n;
             if (pairs && pairs + add > max_pairs) break;
             pairs += add;
             r2++;
         }
-        if (pairs > cap_pairs) {
-            if (d_out) ctx_free(ctx, d_out);
-            d_out = nullptr;
-            if (ctx_malloc(ctx, (void **)&d_out, std::max<uint64_t>(pairs, 1) * sizeof(mg_counts)) != hipSuccess) {
-                rc = fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
-                break;
-            }
-            cap_pairs = pairs;
-        }
-        rc = run_compare(ctx, rows, cols, r, r2, triangle, d_out);
-        if (rc == MG_OK && pairs) {
-            if (hipMemcpyAsync(out_host + done, d_out, pairs * sizeof(mg_counts), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                rc = fail(ctx, MG_ERR_HIP, "compare: D2H copy failed");
-        }
-        done += pairs;
+        v.push_back({r, r2, pairs, before});
+        *largest = std::max(*largest, pairs);
+        before += pairs;
         r = r2;
     }
-    if (d_out) ctx_free(ctx, d_out);
-    return rc;
+    return v;
+}
+
+// host-output variants: bounded device staging, processed in row blocks
+static int compare_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re,
+                        bool triangle, mg_counts *out_host)
+{
+    OutRange R;
+    int rc = out_range(ctx, rows, cols, rb, re, triangle, &R, 0xFFFFFFFFull);
+    if (rc != MG_OK || R.empty()) return rc;
+    uint64_t largest = 0;
+    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 27, &largest);          // 1 GiB of {numer,denom}
+    DevBuf<mg_counts> d_out(ctx);
+    if (d_out.alloc(largest) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
+    for (const RowBlock &b : blocks) {
+        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_out)) != MG_OK) return rc;
+        if (b.pairs && (hipMemcpyAsync(out_host + b.before, d_out, b.pairs * sizeof(mg_counts), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                        hipStreamSynchronize(ctx->stream) != hipSuccess))
+            return fail(ctx, MG_ERR_HIP, "compare: D2H copy failed");
+    }
+    return MG_OK;
 }
 
 int mg_compare_tri_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, mg_counts *out_host)
@@ -1639,97 +1667,68 @@ static void build_min_numer(uint32_t s, int k, double max_d, std::vector<uint32_
     }
 }
 
+
 // kmer_size == 0: no distance filter -- every pair that shares a hash inside its first s union elements (numer >= 1) passes
 static int compare_filter(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re,
                           bool triangle, int kmer_size, double max_distance, mg_edge *out_host, uint64_t capacity,
                           uint64_t *count_out)
 {
     *count_out = 0;
-    if (re > rows->n) re = rows->n;
-    if (triangle && rows == cols) rows = cols = tri_view(ctx, cols, rb, re);     // (the first re rows are all this call looks at)
-    if (rb >= re) return MG_OK;
+    OutRange R;
+    int rc = out_range(ctx, rows, cols, rb, re, triangle, &R);
+    if (rc != MG_OK || R.empty()) return rc;
     if (kmer_size < 0) return fail(ctx, MG_ERR_INVALID, "compare filter: bad k-mer size");
-    const uint64_t s64 = std::min(rows->s, cols->s);
-    if (s64 > 0xFFFFFFFEull) return fail(ctx, MG_ERR_INVALID, "compare: sketch size too large");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!R.pairs) return MG_OK;
     std::vector<uint32_t> min_numer;
-    if (kmer_size == 0) min_numer.assign((size_t)s64 + 1, 1u);
-    else build_min_numer((uint32_t)s64, kmer_size, max_distance, min_numer);
+    if (kmer_size == 0) min_numer.assign((size_t)R.s + 1, 1u);
+    else build_min_numer(R.s, kmer_size, max_distance, min_numer);
 
     // row blocks of up to 2^30 pairs (8 GiB of counts): large launches keep the
     // tail of the compare kernel short; survivors leave in windows of 2^26 edges
-    const uint64_t max_pairs = 1ull << 30, window = 1ull << 26;
-    const uint64_t all_pairs = triangle ? tri_pairs(rb, re) : (re - rb) * cols->n;
-    const uint64_t blk_pairs = std::min(all_pairs, max_pairs + (triangle ? re : cols->n));
-    mg_counts *d_counts = nullptr;
-    uint4 *d_edges = nullptr;
-    uint32_t *d_min = nullptr, *d_segc = nullptr;
-    unsigned long long *d_sego = nullptr, *d_n = nullptr;
-    uint64_t total = 0, r = rb;
-    int rc = MG_OK;
-    auto cleanup = [&]() {
-        hipStreamSynchronize(ctx->stream);
-        for (void *p : {(void *)d_counts, (void *)d_edges, (void *)d_min, (void *)d_segc, (void *)d_sego, (void *)d_n})
-            if (p) hipFree(p);
-    };
-    if (all_pairs == 0) return MG_OK;
-    const uint64_t nseg_max = mg::filter_segments(blk_pairs);
-    if (hipMalloc(&d_min, min_numer.size() * 4) != hipSuccess || hipMalloc(&d_n, 8) != hipSuccess ||
-        hipMalloc(&d_counts, blk_pairs * sizeof(mg_counts)) != hipSuccess ||
-        hipMalloc(&d_edges, std::min(blk_pairs, window) * sizeof(uint4)) != hipSuccess ||
-        hipMalloc(&d_segc, nseg_max * 4) != hipSuccess || hipMalloc(&d_sego, nseg_max * 8) != hipSuccess ||
-        hipMemcpyAsync(d_min, min_numer.data(), min_numer.size() * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        cleanup();
+    const uint64_t window = 1ull << 26;
+    uint64_t largest = 0;
+    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 30, &largest);
+    const uint64_t nseg_max = mg::filter_segments(largest);
+    DevBuf<mg_counts> d_counts;
+    DevBuf<uint4> d_edges;
+    DevBuf<uint32_t> d_min, d_segc;
+    DevBuf<unsigned long long> d_sego, d_n;
+    if (d_min.alloc(min_numer.size()) != hipSuccess || d_n.alloc(1) != hipSuccess || d_counts.alloc(largest) != hipSuccess ||
+        d_edges.alloc(std::min(largest, window)) != hipSuccess || d_segc.alloc(nseg_max) != hipSuccess || d_sego.alloc(nseg_max) != hipSuccess ||
+        hipMemcpyAsync(d_min, min_numer.data(), min_numer.size() * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         return fail(ctx, MG_ERR_NOMEM, "compare filter: device allocation failed");
-    }
-    while (r < re && rc == MG_OK) {
-        uint64_t r2 = r, pairs = 0;
-        while (r2 < re) {
-            const uint64_t add = triangle ? r2 : cols->n;
-            if (pairs && pairs + add > max_pairs) break;
-            pairs += add;
-            r2++;
+    uint64_t total = 0;
+    for (const RowBlock &b : blocks) {
+        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_counts)) != MG_OK) return rc;
+        mg::FilterArgs f;
+        f.counts = reinterpret_cast<const uint2 *>(d_counts.p);
+        f.min_numer = d_min;
+        f.seg_count = d_segc;
+        f.seg_off = d_sego;
+        f.edges = d_edges;
+        f.pairs = b.pairs;
+        f.first_row = b.r;
+        f.ncols = R.cols->n;
+        f.win_lo = 0; f.win_n = 0;
+        f.s = R.s;
+        f.triangle = triangle ? 1 : 0;
+        unsigned long long n_blk = 0;
+        if (mg::launch_filter_count(f, d_n, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(&n_blk, d_n, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            return fail(ctx, MG_ERR_HIP, "compare filter: kernel failed");
+        // survivors already rank in reference order; skip the copy once `capacity` is exceeded
+        for (uint64_t lo = 0; lo < n_blk && total + n_blk <= capacity; lo += window) {
+            f.win_lo = lo;
+            f.win_n = std::min<uint64_t>(window, n_blk - lo);
+            if (mg::launch_filter_write(f, ctx->stream) != hipSuccess ||
+                hipMemcpyAsync(out_host + total + lo, d_edges, f.win_n * sizeof(mg_edge), hipMemcpyDeviceToHost,
+                               ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess)
+                return fail(ctx, MG_ERR_HIP, "compare filter: compaction failed");
         }
-        if (pairs) {
-            rc = run_compare(ctx, rows, cols, r, r2, triangle, d_counts);
-            if (rc != MG_OK) break;
-            mg::FilterArgs f;
-            f.counts = reinterpret_cast<const uint2 *>(d_counts);
-            f.min_numer = d_min;
-            f.seg_count = d_segc;
-            f.seg_off = d_sego;
-            f.edges = d_edges;
-            f.pairs = pairs;
-            f.first_row = r;
-            f.ncols = cols->n;
-            f.win_lo = 0; f.win_n = 0;
-            f.s = (uint32_t)s64;
-            f.triangle = triangle ? 1 : 0;
-            unsigned long long n_blk = 0;
-            if (mg::launch_filter_count(f, d_n, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(&n_blk, d_n, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess) {
-                rc = fail(ctx, MG_ERR_HIP, "compare filter: kernel failed");
-                break;
-            }
-            // survivors already rank in reference order; skip the copy once `capacity` is exceeded
-            for (uint64_t lo = 0; lo < n_blk && total + n_blk <= capacity; lo += window) {
-                f.win_lo = lo;
-                f.win_n = std::min<uint64_t>(window, n_blk - lo);
-                if (mg::launch_filter_write(f, ctx->stream) != hipSuccess ||
-                    hipMemcpyAsync(out_host + total + lo, d_edges, f.win_n * sizeof(mg_edge), hipMemcpyDeviceToHost,
-                                   ctx->stream) != hipSuccess ||
-                    hipStreamSynchronize(ctx->stream) != hipSuccess) {
-                    rc = fail(ctx, MG_ERR_HIP, "compare filter: compaction failed");
-                    break;
-                }
-            }
-            total += n_blk;
-        }
-        r = r2;
+        total += n_blk;
     }
-    cleanup();
-    if (rc != MG_OK) return rc;
     *count_out = total;
     if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare filter: more passing pairs than `capacity` (see *count_out)");
     return MG_OK;
@@ -1798,6 +1797,28 @@ static int build_finish_tables(mg_ctx *ctx, uint32_t s, int k, double max_d, con
     return MG_OK;
 }
 
+// The FinishArgs fields every device finish fills: `pairs` counts from row first_row on, the tables' lengths, the distance
+// table and filters of `ft`
+static mg::FinishArgs finish_args(const mg_table *rows, const mg_table *cols, uint32_t s, bool triangle, const void *counts, uint64_t pairs,
+                                  uint64_t first_row, const FinishTables &ft, double kmer_space, double max_p)
+{
+    mg::FinishArgs a{};
+    a.counts = reinterpret_cast<const uint2 *>(counts);
+    a.pairs = pairs;
+    a.first_row = first_row;
+    a.ncols = cols->n;
+    a.len_row = rows->lengths;
+    a.len_col = cols->lengths;
+    a.min_numer = ft.d_min;
+    a.lut_start = ft.d_start;
+    a.lut = ft.d_lut;
+    a.kmer_space = kmer_space;
+    a.max_p = max_p;
+    a.s = s;
+    a.triangle = triangle ? 1 : 0;
+    return a;
+}
+
 // counts (device) of `pairs` pairs starting at row `first_row` -> mg_pair (device)
 static int finish_pairs_dev(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, const mg_counts *counts_dev, uint64_t pairs,
                             uint64_t first_row, bool triangle, int kmer_size, double kmer_space, double max_d, double max_p,
@@ -1820,20 +1841,7 @@ static int finish_pairs_dev(mg_ctx *ctx, const mg_table *rows, const mg_table *c
     FinishTables ft(ctx);
     int rc = build_finish_tables(ctx, s, kmer_size, max_d, seen, ft);
     if (rc != MG_OK) return rc;
-    mg::FinishArgs a{};
-    a.counts = reinterpret_cast<const uint2 *>(counts_dev);
-    a.pairs = pairs;
-    a.first_row = first_row;
-    a.ncols = cols->n;
-    a.len_row = rows->lengths;
-    a.len_col = cols->lengths;
-    a.min_numer = ft.d_min;
-    a.lut_start = ft.d_start;
-    a.lut = ft.d_lut;
-    a.kmer_space = kmer_space;
-    a.max_p = max_p;
-    a.s = s;
-    a.triangle = triangle ? 1 : 0;
+    mg::FinishArgs a = finish_args(rows, cols, s, triangle, counts_dev, pairs, first_row, ft, kmer_space, max_p);
     a.pairs_out = reinterpret_cast<mg::FinishPair *>(out_dev);
     HIP_TRY(ctx, mg::launch_finish_pairs(a, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the tables are released on return
@@ -1868,66 +1876,47 @@ int mg_finish_rect_dev(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, co
                             max_distance, max_p_value, out_dev, nullptr);
 }
 
+
 // compare + finish on the device, full PairOutput records to the host (32 B per pair), in row blocks
 static int compare_pairs_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle,
                               int kmer_size, double kmer_space, double max_d, double max_p, mg_pair *out_host)
 {
-    if (re > rows->n) re = rows->n;
-    if (triangle && rows == cols) rows = cols = tri_view(ctx, cols, rb, re);     // (the first re rows are all this call looks at)
-    if (rb >= re) return MG_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t max_pairs = 1ull << 26;                   // 2 GiB of records, 512 MiB of counts
+    OutRange R;
+    int rc = out_range(ctx, rows, cols, rb, re, triangle, &R);
+    if (rc != MG_OK || !R.pairs) return rc;
+    uint64_t largest = 0;
+    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 26, &largest);         // 2 GiB of records, 512 MiB of counts
     DevBuf<mg_counts> d_counts(ctx);
     DevBuf<mg_pair> d_pairs(ctx);
-    uint64_t cap = 0, done = 0, r = rb;
+    if (d_counts.alloc(largest) != hipSuccess || d_pairs.alloc(largest) != hipSuccess)
+        return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
     std::vector<uint64_t> len_rows, len_cols;                // host copies, only if a block must be patched
-    while (r < re) {
-        uint64_t r2 = r, pairs = 0;
-        while (r2 < re) {
-            const uint64_t add = triangle ? r2 : cols->n;
-            if (pairs && pairs + add > max_pairs) break;
-            pairs += add;
-            r2++;
-        }
-        if (pairs > cap) {
-            if (d_counts.p) { ctx_free(ctx, d_counts.release()); }
-            if (d_pairs.p) { ctx_free(ctx, d_pairs.release()); }
-            if (d_counts.alloc(pairs) != hipSuccess || d_pairs.alloc(pairs) != hipSuccess)
-                return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
-            cap = pairs;
-        }
-        int rc = pairs ? run_compare(ctx, rows, cols, r, r2, triangle, d_counts) : MG_OK;
-        if (rc != MG_OK) return rc;
+    for (const RowBlock &b : blocks) {
+        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_counts)) != MG_OK) return rc;
         bool complete = true;
-        if (pairs) {
-            rc = finish_pairs_dev(ctx, rows, cols, d_counts, pairs, r, triangle, kmer_size, kmer_space, max_d, max_p, d_pairs, &complete);
-            if (rc != MG_OK) return rc;
-            if (hipMemcpyAsync(out_host + done, d_pairs, pairs * sizeof(mg_pair), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
+        rc = finish_pairs_dev(ctx, R.rows, R.cols, d_counts, b.pairs, b.r, triangle, kmer_size, kmer_space, max_d, max_p, d_pairs, &complete);
+        if (rc != MG_OK) return rc;
+        mg_pair *out = out_host + b.before;
+        if (hipMemcpyAsync(out, d_pairs, b.pairs * sizeof(mg_pair), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            return fail(ctx, MG_ERR_HIP, "compare: D2H copy failed");
+        if (complete) continue;
+        // a denominator beyond the device table's budget left NaN distances: those pairs are finished here
+        if (len_rows.empty()) {
+            len_rows.resize(R.rows->n);
+            len_cols.resize(R.cols->n);
+            if (hipMemcpy(len_rows.data(), R.rows->lengths, R.rows->n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(len_cols.data(), R.cols->lengths, R.cols->n * 8, hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(ctx, MG_ERR_HIP, "compare: D2H copy failed");
-            if (!complete) {
-                // a denominator beyond the device table's budget left NaN distances: those pairs are finished here
-                if (len_rows.empty()) {
-                    len_rows.resize(rows->n);
-                    len_cols.resize(cols->n);
-                    if (hipMemcpy(len_rows.data(), rows->lengths, rows->n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(len_cols.data(), cols->lengths, cols->n * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                        return fail(ctx, MG_ERR_HIP, "compare: D2H copy failed");
-                }
-                uint64_t idx = 0;
-                for (uint64_t i = r; i < r2; i++) {
-                    const uint64_t ncol = triangle ? i : cols->n;
-                    for (uint64_t j = 0; j < ncol; j++, idx++) {
-                        mg_pair &pr = out_host[done + idx];
-                        if (pr.distance == pr.distance) continue;
-                        const mg_counts c{pr.numer, pr.denom};
-                        finish_one(c, len_rows[i], len_cols[j], kmer_size, kmer_space, max_d, max_p, &pr);
-                    }
-                }
+        }
+        for (uint64_t i = b.r; i < b.r2; i++) {
+            const uint64_t ncol = triangle ? i : R.cols->n;
+            for (uint64_t j = 0; j < ncol; j++, out++) {
+                if (out->distance == out->distance) continue;
+                const mg_counts c{out->numer, out->denom};
+                finish_one(c, len_rows[i], len_cols[j], kmer_size, kmer_space, max_d, max_p, out);
             }
         }
-        done += pairs;
-        r = r2;
     }
     return MG_OK;
 }
@@ -1952,7 +1941,7 @@ int mg_compare_rect_pairs_host(mg_ctx *ctx, const mg_table *ref, const mg_table 
     return compare_pairs_host(ctx, qry, ref, q_begin, q_end, false, kmer_size, kmer_space, max_distance, max_p_value, out_host);
 }
 
-// compare + both filters + compaction on the device: survivors only, as full records, in reference order
+
 // The lists of a finished list job in REFERENCE order (rows ascending, a row's pairs by column): the candidates' {row, col}
 // and {common, denom} gathered row by row, and behind a grouped row's candidates -- they all lie below its group -- its pairs
 // inside the group, computed into their places by the dense kernel.  K = job.cand + job.dense_pairs entries.
@@ -1975,187 +1964,149 @@ static int job_lists(mg_ctx *ctx, const SparseJob &job, uint32_t nrows, uint32_t
     return MG_OK;
 }
 
+struct CandLists {
+    uint64_t K = 0;
+    DevBuf<uint2> rc, cnt;
+    DevBuf<uint32_t> byrow, base;
+    DevBuf<unsigned char> temp;
+    size_t tb = 0;
+    explicit CandLists(mg_ctx *c) : rc(c), cnt(c), byrow(c), base(c), temp(c) {}
+};
+
+// The inverted-index engine's job over R as lists (job_lists) instead of a matrix.  *ok false: no lists -- the engine is forced
+// off or leaves the job to the matrix (copies of rows, empty rows, nearly every pair related), or the lists do not fit: 2^32
+// entries and more, or scratch the device cannot give.  That is no error: the caller's own fallback does the job.
+// extra(K, temp bytes) allocates the caller's buffers for K entries (false: they do not fit) and may ask for more scratch.
+template <class Extra>
+static int cand_lists(mg_ctx *ctx, const OutRange &R, CandLists &L, bool *ok, Extra extra)
+{
+    *ok = false;
+    const char *force = ctx_opt(ctx, "MASHGPU_COMPARE_KERNEL");
+    if ((force && strcmp(force, "sparse") != 0) || ctx_opt(ctx, "MASHGPU_RESULTS_MATRIX")) return MG_OK;
+    SparseJob job;
+    bool handled = false;
+    const int rc = run_compare_sparse(ctx, R.rows, R.cols, R.rb, R.re, R.triangle, R.s, nullptr, force != nullptr, &handled, &job);
+    if (rc != MG_OK) return rc;
+    L.K = handled ? job.cand + job.dense_pairs : 0;
+    if (handled && L.K == 0) { *ok = true; return MG_OK; }
+    const uint32_t nrows = (uint32_t)(R.re - R.rb);
+    L.tb = mg::sparse_gather_temp_bytes(nrows);
+    if (!handled || L.K >= (1ull << 32) || L.rc.alloc(L.K) != hipSuccess || L.cnt.alloc(L.K) != hipSuccess || L.byrow.alloc(nrows) != hipSuccess ||
+        L.base.alloc(nrows) != hipSuccess || !extra(L.K, L.tb) || L.temp.alloc(std::max<size_t>(L.tb, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return MG_OK;
+    }
+    *ok = true;
+    return job_lists(ctx, job, nrows, R.triangle ? 0u : (uint32_t)R.rb, R.s, L.byrow, L.base, L.temp, L.tb, L.rc, L.cnt);
+}
+
+static const uint64_t kResultsWindow = 1ull << 25;          // survivors leave the device in windows of 2^25 records
+
+// What finish_survivors needs on the device for up to `pairs` entries: pass A's ballots and segments, the survivors' count and
+// denominators, one window of records
+struct SurvivorBufs {
+    DevBuf<unsigned long long> masks, seg_off, n;
+    DevBuf<uint32_t> seg_count, seen;
+    DevBuf<mg::FinishEdge> edges;
+    explicit SurvivorBufs(mg_ctx *owner) : masks(owner), seg_off(owner), n(owner), seg_count(owner), seen(owner), edges(owner) {}
+    bool alloc(uint64_t pairs, uint32_t s)
+    {
+        return masks.alloc(mg::finish_mask_words(pairs)) == hipSuccess && seg_count.alloc(mg::finish_segments(pairs)) == hipSuccess &&
+               seg_off.alloc(mg::finish_segments(pairs)) == hipSuccess && n.alloc(1) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess &&
+               edges.alloc(std::min(pairs, kResultsWindow)) == hipSuccess;
+    }
+};
+
+// The two finish passes over f's counts -- one matrix block, or the candidate list (f.list_rc).  Pass A needs the distance filter
+// but no distances: f carries tables without any extra denominator row.  It marks the survivors, counts them and flags their
+// denominators; only then are the distance rows of exactly those known, so the tables are built a second time for pass B, which
+// writes the survivors in reference order.
+// *n_out: the survivors, always; they are written to out_host only when they fit `room`.
+static int finish_survivors(mg_ctx *ctx, mg::FinishArgs f, const SurvivorBufs &b, int kmer_size, double max_d, uint64_t room,
+                            mg_result *out_host, uint64_t *n_out)
+{
+    f.masks = b.masks;
+    f.seg_count = b.seg_count;
+    f.seg_off = b.seg_off;
+    f.denom_seen = b.seen;
+    f.edges = b.edges;
+    std::vector<uint32_t> seen((size_t)f.s + 1);
+    unsigned long long n = 0;
+    HIP_TRY(ctx, hipMemsetAsync(b.seen, 0, seen.size() * 4, ctx->stream));
+    HIP_TRY(ctx, mg::launch_finish_mark(f, b.n, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&n, b.n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(seen.data(), b.seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_out = n;
+    if (n == 0 || n > room) return MG_OK;
+    FinishTables fb(ctx);
+    const int rc = build_finish_tables(ctx, f.s, kmer_size, max_d, seen, fb);
+    if (rc != MG_OK) return rc;
+    f.lut_start = fb.d_start;
+    f.lut = fb.d_lut;
+    f.min_numer = fb.d_min;
+    for (uint64_t lo = 0; lo < n; lo += kResultsWindow) {
+        f.win_lo = lo;
+        f.win_n = std::min<uint64_t>(kResultsWindow, n - lo);
+        HIP_TRY(ctx, mg::launch_finish_write(f, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out_host + lo, b.edges, f.win_n * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (!fb.complete)                                         // a denominator beyond the table's budget left NaN distances
+        for (uint64_t i = 0; i < n; i++) {
+            mg_result &e = out_host[i];
+            if (e.distance != e.distance) e.distance = mg::mash_distance(e.numer, e.denom, kmer_size);
+        }
+    return MG_OK;
+}
+
+// compare + both filters + compaction on the device: survivors only, as full records, in reference order
 static int compare_results(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle,
                            int kmer_size, double kmer_space, double max_d, double max_p, mg_result *out_host, uint64_t capacity,
                            uint64_t *count_out)
 {
     *count_out = 0;
-    if (re > rows->n) re = rows->n;
-    if (triangle && rows == cols) rows = cols = tri_view(ctx, cols, rb, re);     // (the first re rows are all this call looks at)
-    if (rb >= re) return MG_OK;
+    OutRange R;
+    int rc = out_range(ctx, rows, cols, rb, re, triangle, &R);
+    if (rc != MG_OK || R.empty()) return rc;
     if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
-    const uint64_t s64 = std::min(rows->s, cols->s);
-    if (s64 > 0xFFFFFFFEull) return fail(ctx, MG_ERR_INVALID, "compare: sketch size too large");
-    const uint32_t s = (uint32_t)s64;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t max_pairs = 1ull << 30, window = 1ull << 25;
-    const uint64_t all_pairs = triangle ? tri_pairs(rb, re) : (re - rb) * cols->n;
-    if (all_pairs == 0) return MG_OK;
+    if (!R.pairs) return MG_OK;
     // ---- a filter is on: only pairs that share a hash can pass (numer = 0 means distance 1 and p-value 1), and
     // those are the inverted-index engine's candidates -- no matrix is filled, no 8 B per pair read back by
     // the filter pass: discover + merge, the candidates put into reference order, the same two finish passes
     // over that list.
-    const char *force_kernel = ctx_opt(ctx, "MASHGPU_COMPARE_KERNEL");
-    if (((max_d >= 0.0 && max_d < 1.0) || (max_p >= 0.0 && max_p < 1.0)) && (!force_kernel || strcmp(force_kernel, "sparse") == 0) &&
-        !ctx_opt(ctx, "MASHGPU_RESULTS_MATRIX")) {
-        SparseJob job;
-        bool handled = false;
-        int rc = run_compare_sparse(ctx, rows, cols, rb, re, triangle, s, nullptr, force_kernel != nullptr, &handled, &job);
-        if (rc != MG_OK) return rc;
-        // (a list of 2^32 candidates and more, or one whose scratch does not fit, is no error: the blocked matrix path
-        //  below does the job in 2^30-pair blocks -- ADVICE r3)
-        const uint64_t K = handled ? job.cand + job.dense_pairs : 0;
-        if (handled && K == 0) return MG_OK;
-        const uint32_t nrows = (uint32_t)(re - rb);
-        DevBuf<uint2> d_rc(ctx), d_cnt(ctx);
-        DevBuf<uint32_t> d_byrow(ctx), d_base(ctx), d_segc2(ctx), d_seen2(ctx);
-        DevBuf<unsigned long long> d_masks2(ctx), d_sego2(ctx), d_n2(ctx);
-        DevBuf<mg::FinishEdge> d_edges2(ctx);
-        DevBuf<unsigned char> d_temp(ctx);
-        const size_t tb = mg::sparse_gather_temp_bytes(nrows);
-        bool list_ok = handled && K < (1ull << 32);
-        if (list_ok && (d_rc.alloc(K) != hipSuccess || d_cnt.alloc(K) != hipSuccess || d_byrow.alloc(nrows) != hipSuccess || d_base.alloc(nrows) != hipSuccess ||
-                        d_temp.alloc(std::max<size_t>(tb, 16)) != hipSuccess || d_masks2.alloc(mg::finish_mask_words(K)) != hipSuccess ||
-                        d_segc2.alloc(mg::finish_segments(K)) != hipSuccess || d_sego2.alloc(mg::finish_segments(K)) != hipSuccess || d_n2.alloc(1) != hipSuccess ||
-                        d_seen2.alloc((uint64_t)s + 1) != hipSuccess || d_edges2.alloc(std::min(K, window)) != hipSuccess)) {
-            (void)hipGetLastError();
-            list_ok = false;
-        }
-        if (list_ok) {
-            rc = job_lists(ctx, job, nrows, triangle ? 0u : (uint32_t)rb, s, d_byrow, d_base, d_temp, tb, d_rc, d_cnt);
-            if (rc != MG_OK) return rc;
-            std::vector<uint32_t> seen2((size_t)s + 1, 0);
+    if ((max_d >= 0.0 && max_d < 1.0) || (max_p >= 0.0 && max_p < 1.0)) {
+        CandLists L(ctx);
+        SurvivorBufs sb(ctx);
+        bool lists = false;
+        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return sb.alloc(K, R.s); });
+        if (rc != MG_OK || (lists && L.K == 0)) return rc;
+        if (lists) {
             FinishTables fa(ctx);
-            rc = build_finish_tables(ctx, s, kmer_size, max_d, seen2, fa);
+            if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
+            mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, triangle, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
+            f.list_rc = L.rc;
+            rc = finish_survivors(ctx, f, sb, kmer_size, max_d, capacity, out_host, count_out);
             if (rc != MG_OK) return rc;
-            mg::FinishArgs f{};
-            f.counts = d_cnt;
-            f.list_rc = d_rc;
-            f.pairs = K;
-            f.first_row = rb;
-            f.ncols = cols->n;
-            f.len_row = rows->lengths;
-            f.len_col = cols->lengths;
-            f.min_numer = fa.d_min;
-            f.lut_start = fa.d_start;
-            f.lut = fa.d_lut;
-            f.kmer_space = kmer_space;
-            f.max_p = max_p;
-            f.s = s;
-            f.triangle = triangle ? 1 : 0;
-            f.masks = d_masks2;
-            f.seg_count = d_segc2;
-            f.seg_off = d_sego2;
-            f.denom_seen = d_seen2;
-            f.edges = d_edges2;
-            unsigned long long n_all = 0;
-            HIP_TRY(ctx, hipMemsetAsync(d_seen2, 0, ((uint64_t)s + 1) * 4, ctx->stream));
-            HIP_TRY(ctx, mg::launch_finish_mark(f, d_n2, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(&n_all, d_n2, 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(seen2.data(), d_seen2, seen2.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            *count_out = n_all;
-            if (n_all > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
-            if (n_all) {
-                FinishTables fb(ctx);
-                rc = build_finish_tables(ctx, s, kmer_size, max_d, seen2, fb);
-                if (rc != MG_OK) return rc;
-                f.lut_start = fb.d_start;
-                f.lut = fb.d_lut;
-                f.min_numer = fb.d_min;
-                for (uint64_t lo = 0; lo < n_all; lo += window) {
-                    f.win_lo = lo;
-                    f.win_n = std::min<uint64_t>(window, n_all - lo);
-                    HIP_TRY(ctx, mg::launch_finish_write(f, ctx->stream));
-                    HIP_TRY(ctx, hipMemcpyAsync(out_host + lo, d_edges2, f.win_n * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                }
-                if (!fb.complete)
-                    for (uint64_t i = 0; i < n_all; i++) {
-                        mg_result &e = out_host[i];
-                        if (e.distance != e.distance) e.distance = mg::mash_distance(e.numer, e.denom, kmer_size);
-                    }
-            }
+            if (*count_out > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
             return MG_OK;
         }
     }
-    const uint64_t blk_pairs = std::min(all_pairs, max_pairs + (triangle ? re : cols->n));
+    uint64_t largest = 0;
+    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 30, &largest);
     DevBuf<mg_counts> d_counts;
-    DevBuf<mg::FinishEdge> d_edges;
-    DevBuf<unsigned long long> d_masks, d_sego, d_n;
-    DevBuf<uint32_t> d_segc, d_seen;
-    if (d_counts.alloc(blk_pairs) != hipSuccess || d_edges.alloc(std::min(blk_pairs, window)) != hipSuccess ||
-        d_masks.alloc(mg::finish_mask_words(blk_pairs)) != hipSuccess || d_segc.alloc(mg::finish_segments(blk_pairs)) != hipSuccess ||
-        d_sego.alloc(mg::finish_segments(blk_pairs)) != hipSuccess || d_n.alloc(1) != hipSuccess || d_seen.alloc((uint64_t)s + 1) != hipSuccess)
-        return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
-    // pass A needs the distance filter but no distances: tables without any extra denominator row
-    std::vector<uint32_t> seen((size_t)s + 1, 0);
-    uint64_t total = 0, r = rb;
-    std::vector<uint64_t> len_rows, len_cols;
-    while (r < re) {
-        uint64_t r2 = r, pairs = 0;
-        while (r2 < re) {
-            const uint64_t add = triangle ? r2 : cols->n;
-            if (pairs && pairs + add > max_pairs) break;
-            pairs += add;
-            r2++;
-        }
-        if (pairs) {
-            int rc = run_compare(ctx, rows, cols, r, r2, triangle, d_counts);
-            if (rc != MG_OK) return rc;
-            FinishTables fa(ctx);
-            std::fill(seen.begin(), seen.end(), 0u);
-            rc = build_finish_tables(ctx, s, kmer_size, max_d, seen, fa);
-            if (rc != MG_OK) return rc;
-            mg::FinishArgs a{};
-            a.counts = reinterpret_cast<const uint2 *>(d_counts.p);
-            a.pairs = pairs;
-            a.first_row = r;
-            a.ncols = cols->n;
-            a.len_row = rows->lengths;
-            a.len_col = cols->lengths;
-            a.min_numer = fa.d_min;
-            a.lut_start = fa.d_start;
-            a.lut = fa.d_lut;
-            a.kmer_space = kmer_space;
-            a.max_p = max_p;
-            a.s = s;
-            a.triangle = triangle ? 1 : 0;
-            a.masks = d_masks;
-            a.seg_count = d_segc;
-            a.seg_off = d_sego;
-            a.denom_seen = d_seen;
-            a.edges = d_edges;
-            unsigned long long n_blk = 0;
-            HIP_TRY(ctx, hipMemsetAsync(d_seen, 0, ((uint64_t)s + 1) * 4, ctx->stream));
-            HIP_TRY(ctx, mg::launch_finish_mark(a, d_n, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(&n_blk, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(seen.data(), d_seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (n_blk && total + n_blk <= capacity) {
-                FinishTables fb(ctx);                        // now with the rows of the survivors' denominators
-                rc = build_finish_tables(ctx, s, kmer_size, max_d, seen, fb);
-                if (rc != MG_OK) return rc;
-                a.lut_start = fb.d_start;
-                a.lut = fb.d_lut;
-                a.min_numer = fb.d_min;
-                for (uint64_t lo = 0; lo < n_blk; lo += window) {
-                    a.win_lo = lo;
-                    a.win_n = std::min<uint64_t>(window, n_blk - lo);
-                    HIP_TRY(ctx, mg::launch_finish_write(a, ctx->stream));
-                    HIP_TRY(ctx, hipMemcpyAsync(out_host + total + lo, d_edges, a.win_n * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                }
-                if (!fb.complete) {
-                    for (uint64_t i = 0; i < n_blk; i++) {
-                        mg_result &e = out_host[total + i];
-                        if (e.distance != e.distance) e.distance = mg::mash_distance(e.numer, e.denom, kmer_size);
-                    }
-                }
-            }
-            total += n_blk;
-        }
-        r = r2;
+    SurvivorBufs sb(nullptr);
+    if (d_counts.alloc(largest) != hipSuccess || !sb.alloc(largest, R.s)) return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
+    FinishTables fa(ctx);
+    uint64_t total = 0;
+    for (const RowBlock &b : blocks) {
+        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_counts)) != MG_OK) return rc;
+        if (&b == &blocks.front() && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;  // (once: behind the first compare)
+        uint64_t n = 0;
+        rc = finish_survivors(ctx, finish_args(R.rows, R.cols, R.s, triangle, d_counts, b.pairs, b.r, fa, kmer_space, max_p), sb, kmer_size, max_d,
+                              total <= capacity ? capacity - total : 0, out_host + total, &n);
+        if (rc != MG_OK) return rc;
+        total += n;
     }
     *count_out = total;
     if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
@@ -2167,53 +2118,37 @@ static int compare_sparse_matrix(mg_ctx *ctx, const mg_table *rows, const mg_tab
                                  uint64_t capacity, uint64_t *count_out)
 {
     *count_out = 0;
-    if (re > rows->n) re = rows->n;
-    if (triangle && rows == cols) rows = cols = tri_view(ctx, cols, rb, re);     // (the first re rows are all this call looks at)
-    if (rb >= re) return MG_OK;
-    const uint64_t s64 = std::min(rows->s, cols->s);
-    if (s64 > 0xFFFFFFFEull) return fail(ctx, MG_ERR_INVALID, "compare: sketch size too large");
-    const uint32_t s = (uint32_t)s64;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t all_pairs = triangle ? tri_pairs(rb, re) : (re - rb) * cols->n;
-    if (all_pairs == 0) return MG_OK;
-    const char *force_kernel = ctx_opt(ctx, "MASHGPU_COMPARE_KERNEL");
-    if ((!force_kernel || strcmp(force_kernel, "sparse") == 0) && !ctx_opt(ctx, "MASHGPU_RESULTS_MATRIX")) {
-        // the index engine's lists ARE the answer: its candidates (pairs that share a hash) and the pairs inside its dense
-        // groups, in reference order, minus the few that share a hash only behind their first s union elements
-        SparseJob job;
-        bool handled = false;
-        int rc = run_compare_sparse(ctx, rows, cols, rb, re, triangle, s, nullptr, force_kernel != nullptr, &handled, &job);
-        if (rc != MG_OK) return rc;
-        const uint64_t K = handled ? job.cand + job.dense_pairs : 0;
-        if (handled && K == 0) return MG_OK;
-        const uint32_t nrows = (uint32_t)(re - rb);
-        DevBuf<uint2> d_rc(ctx), d_cnt(ctx);
-        DevBuf<uint32_t> d_byrow(ctx), d_base(ctx), d_bc(ctx), d_bo(ctx);
-        DevBuf<uint4> d_edges(ctx);
-        DevBuf<unsigned long long> d_total(ctx);
-        DevBuf<unsigned char> d_temp(ctx);
-        const size_t tb = std::max(mg::sparse_gather_temp_bytes(nrows), mg::sparse_edges_temp_bytes(K));
-        if (handled && K < (1ull << 32) && d_rc.alloc(K) == hipSuccess && d_cnt.alloc(K) == hipSuccess && d_byrow.alloc(nrows) == hipSuccess &&
-            d_base.alloc(nrows) == hipSuccess && d_temp.alloc(std::max<size_t>(tb, 16)) == hipSuccess && d_bc.alloc(mg::sparse_edges_blocks(K)) == hipSuccess &&
-            d_bo.alloc(mg::sparse_edges_blocks(K)) == hipSuccess && d_edges.alloc(K) == hipSuccess && d_total.alloc(1) == hipSuccess) {
-            rc = job_lists(ctx, job, nrows, triangle ? 0u : (uint32_t)rb, s, d_byrow, d_base, d_temp, tb, d_rc, d_cnt);
-            if (rc != MG_OK) return rc;
-            unsigned long long total = 0;
-            HIP_TRY(ctx, mg::launch_sparse_list_edges(d_rc, d_cnt, K, d_bc, d_bo, d_temp, tb, d_edges, d_total, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    OutRange R;
+    int rc = out_range(ctx, rows, cols, rb, re, triangle, &R);
+    if (rc != MG_OK || !R.pairs) return rc;
+    // the index engine's lists ARE the answer: its candidates (pairs that share a hash) and the pairs inside its dense
+    // groups, in reference order, minus the few that share a hash only behind their first s union elements
+    CandLists L(ctx);
+    DevBuf<uint32_t> d_bc(ctx), d_bo(ctx);
+    DevBuf<uint4> d_edges(ctx);
+    DevBuf<unsigned long long> d_total(ctx);
+    bool lists = false;
+    rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &tb) {
+        tb = std::max(tb, mg::sparse_edges_temp_bytes(K));
+        return d_bc.alloc(mg::sparse_edges_blocks(K)) == hipSuccess && d_bo.alloc(mg::sparse_edges_blocks(K)) == hipSuccess &&
+               d_edges.alloc(K) == hipSuccess && d_total.alloc(1) == hipSuccess;
+    });
+    if (rc != MG_OK || (lists && L.K == 0)) return rc;
+    if (lists) {
+        unsigned long long total = 0;
+        HIP_TRY(ctx, mg::launch_sparse_list_edges(L.rc, L.cnt, L.K, d_bc, d_bo, L.temp, L.tb, d_edges, d_total, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *count_out = total;
+        if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more pairs that share a hash than `capacity` (see *count_out)");
+        if (total) {
+            HIP_TRY(ctx, hipMemcpyAsync(out_host, d_edges, total * sizeof(mg_edge), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            *count_out = total;
-            if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more pairs that share a hash than `capacity` (see *count_out)");
-            if (total) {
-                HIP_TRY(ctx, hipMemcpyAsync(out_host, d_edges, total * sizeof(mg_edge), hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            }
-            return MG_OK;
         }
-        (void)hipGetLastError();
+        return MG_OK;
     }
     // tables the list engine leaves alone (copies of rows, empty rows, nearly every pair related): the matrix in blocks, filtered on the device
-    return compare_filter(ctx, rows, cols, rb, re, triangle, 0, 0.0, out_host, capacity, count_out);
+    return compare_filter(ctx, R.rows, R.cols, R.rb, R.re, triangle, 0, 0.0, out_host, capacity, count_out);
 }
 
 int mg_compare_tri_sparse_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, mg_edge *out_host, uint64_t capacity,

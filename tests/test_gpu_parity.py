@@ -1997,10 +1997,19 @@ def test_device_finish_equals_host_finish(eng, oracle, golden_dir, max_d, max_p,
         n2[i] = rng.integers(1, 300)
         t2[i, n2[i]:] = np.uint64(abi.HASH_PAD)
     cases.append((t2, n2, rng.integers(500, 10 ** 6, 120).astype(np.uint64), 16, 4.0 ** 16))
+    # more distinct denominators than the device distance table holds (2^26 doubles): s = 20 000 and 5 000 - 10 000 hashes
+    # a row, so most pairs have |A| + |B| < s -- the rows past the budget come out NaN and are finished on the host
+    t3, n3, _ = synth.clustered_sketches(150, 20000, clusters=5, seed=6, pool=8000, private=8000)
+    n3 = rng.integers(5000, 10001, 150).astype(np.uint32)
+    for i in range(150):
+        t3[i, n3[i]:] = np.uint64(abi.HASH_PAD)
+    cases.append((t3, n3, rng.integers(10 ** 5, 10 ** 7, 150).astype(np.uint64), 21, KSPACE21))
     for table, nh, lengths, k, ks in cases:
         n = len(nh)
         t = eng.table_upload(table, nh, lengths)
         counts = eng.compare_tri_host(t)
+        if table is t3:
+            assert sum(int(d) + 1 for d in np.unique(counts["denom"])) > 1 << 26      # over the budget, as meant
         host = eng.finish_tri(counts, lengths, 0, n, k, ks, max_d, max_p)
         dev = eng.compare_tri_pairs(t, k, ks, max_d, max_p)
         assert np.array_equal(dev["numer"], host["numer"]) and np.array_equal(dev["denom"], host["denom"])
