@@ -498,6 +498,46 @@ int  mg_screen_finish_sparse_host(mg_screen *sc, mg_screen_hit *hits_out, uint64
                                   uint64_t *mix_hashes_out, uint32_t *mix_nhash_out, uint64_t *distinct_out);
 const char *mg_screen_tier_note(const mg_screen *sc);
 void mg_screen_free(mg_screen *sc);
+/* ---- taxonomy of a screen (`mash taxscreen`) ------------------------------------------
+ * Replaces the data-parallel part of CommandTaxScreen.cpp below its report: the LCA of the references that hold
+ * each database hash (:411-425, TaxDB::getLowestCommonAncestor taxdb.hpp:162-196), the per-taxon histograms
+ * counts[taxID].taxHashCount / .taxCount (:427-432) and the clade sums (:437-464).  One device: the sharded
+ * screen (mg_dscreen_*) has no taxon call.
+ *
+ * mg_taxonomy_create (replaces TaxDB's entries / parent links, taxdb.hpp:87-125): a forest over dense node indices
+ * 0 .. n_nodes-1, parent[i] == i for a root.  MG_ERR_INVALID for an index out of range or a cycle.  parent and depth
+ * stay on the device.  The taxonomy must outlive every screen bound to it.
+ *
+ * mg_screen_set_taxa (replaces :411-428, once per database instead of once per run): row_node[n_rows] = the node of
+ * every database row or MG_TAX_NONE (the reference's taxID 0: skipped in the fold); n_rows must be the table's row
+ * count.  Builds the rows-by-hash index if needed, the LCA node of every distinct hash and the database histogram;
+ * both stay resident over mg_screen_reset.  A hash whose rows lie under different roots gets MG_TAX_DISJOINT (the
+ * caller maps it to the reference's answer, taxID 1), a hash whose rows all carry MG_TAX_NONE gets MG_TAX_NONE.
+ * MG_ERR_UNSUPPORTED beyond 2^31 database hashes, as for mg_screen_finish_sparse_host.
+ *
+ * mg_screen_tax_finish_host (replaces :429-464 for one mixture): over the touched hashes, tax_count[node] += 1 for
+ * every hash observed at least once (minCov is 1, :235), then the clade sums -- every node's own counts added once
+ * to itself and to each ancestor -- and one mg_taxon_count for every node with clade_hash_count > 0, ordered by node
+ * index; MG_TAX_DISJOINT and MG_TAX_NONE follow at the end when they hold hashes, each its own clade.
+ * *n_out = their number, the first min(capacity, *n_out) are written (capacity 0 sizes the buffer).
+ * *total_count / *total_hash_count: the sums of the tax_count / tax_hash_count columns (totalCount /
+ * totalHashCount, :440-444).  The mixture outputs are those of mg_screen_finish_host.  mg_screen_reset also clears
+ * the mixture's taxon counters.
+ *
+ * mg_screen_hash_taxa_host (the reference's hashTaxIDs, :426): every distinct database hash with its LCA node,
+ * ordered by hash; capacity / *n_out as above.
+ * mg_screen_tax_note: what set_taxa built and how often (for logs and tests). */
+#define MG_TAX_NONE     0xFFFFFFFFu
+#define MG_TAX_DISJOINT 0xFFFFFFFEu
+typedef struct mg_taxonomy mg_taxonomy;
+typedef struct mg_taxon_count { uint32_t node, tax_count, tax_hash_count, clade_count, clade_hash_count; } mg_taxon_count;
+int  mg_taxonomy_create(mg_ctx *ctx, const uint32_t *parent, uint64_t n_nodes, mg_taxonomy **out);
+void mg_taxonomy_free(mg_taxonomy *tax);
+int  mg_screen_set_taxa(mg_screen *sc, const mg_taxonomy *tax, const uint32_t *row_node, uint64_t n_rows);
+int  mg_screen_tax_finish_host(mg_screen *sc, mg_taxon_count *out, uint64_t capacity, uint64_t *n_out, uint64_t *total_count,
+                               uint64_t *total_hash_count, uint64_t *mix_hashes_out, uint32_t *mix_nhash_out, uint64_t *distinct_out);
+int  mg_screen_hash_taxa_host(mg_screen *sc, uint64_t *hashes_out, uint32_t *nodes_out, uint64_t capacity, uint64_t *n_out);
+const char *mg_screen_tax_note(const mg_screen *sc);
 /* estimateIdentity (CommandScreen.cpp:463-482) and pValueWithin (:601-615), host arithmetic. */
 double mg_identity(uint64_t common, uint64_t denom, int kmer_size);
 double mg_p_value_within(uint64_t x, uint64_t set_size, double kmer_space, uint64_t sketch_size);

@@ -35,6 +35,7 @@ EXPORTS = [
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
+    "mg_taxonomy_create", "mg_taxonomy_free", "mg_screen_set_taxa", "mg_screen_tax_finish_host", "mg_screen_hash_taxa_host", "mg_screen_tax_note",
     "mg_identity", "mg_p_value_within",
     "mg_comm_create_local", "mg_comm_unique_id", "mg_comm_create_rank", "mg_comm_destroy", "mg_comm_size", "mg_comm_rank",
     "mg_comm_uses_rccl", "mg_comm_ctx", "mg_comm_last_error", "mg_shard_tri_rows", "mg_shard_tri_rows_weighted", "mg_shard_tri_rows_costed", "mg_shard_rows", "mg_dtable_upload",
@@ -140,6 +141,64 @@ class ScreenSession:
 
     def tier_note(self):
         return self.eng.lib.mg_screen_tier_note(self.h).decode()
+
+    def set_taxa(self, tax, row_node):
+        """bind the database to a Taxonomy: row_node[i] = node index of row i or TAX_NONE.  Computes the LCA node of
+        every distinct hash and the database histogram once; both stay over reset()."""
+        row_node = np.ascontiguousarray(row_node, dtype=np.uint32)
+        self.tax = tax                       # (the taxonomy must outlive the binding)
+        self.eng._check(self.eng.lib.mg_screen_set_taxa(self.h, tax.h, row_node.ctypes.data, len(row_node)))
+
+    def tax_finish(self, capacity=None):
+        """(taxa TAXON_DTYPE[n] ordered by node, total_count, total_hash_count, mixture sketch, distinct table hashes)
+        for the mixture added so far.  capacity: size of the buffer handed to the library (None: sized by a first
+        call); the returned array holds min(capacity, n) entries and `n` is returned as a sixth value then."""
+        lib, s = self.eng.lib, int(self.p.sketch_size)
+        n = C.c_uint64(0)
+        if capacity is None:
+            self.eng._check(lib.mg_screen_tax_finish_host(self.h, None, 0, C.byref(n), None, None, None, None, None))
+        cap = n.value if capacity is None else int(capacity)
+        taxa = np.empty(cap, dtype=TAXON_DTYPE)
+        mix = np.zeros(s, dtype=np.uint64)
+        mn, dist, tot, tot_h = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self.eng._check(lib.mg_screen_tax_finish_host(self.h, taxa.ctypes.data if cap else None, cap, C.byref(n), C.byref(tot), C.byref(tot_h),
+                                                      mix.ctypes.data, C.byref(mn), C.byref(dist)))
+        res = (taxa[: min(cap, n.value)], int(tot.value), int(tot_h.value), mix[: mn.value].copy(), int(dist.value))
+        return res if capacity is None else res + (int(n.value),)
+
+    def hash_taxa(self):
+        """(hashes u64[distinct] ascending, nodes u32[distinct]): the LCA node of every distinct database hash"""
+        lib = self.eng.lib
+        n = C.c_uint64(0)
+        self.eng._check(lib.mg_screen_hash_taxa_host(self.h, None, None, 0, C.byref(n)))
+        hashes, nodes = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self.eng._check(lib.mg_screen_hash_taxa_host(self.h, hashes.ctypes.data, nodes.ctypes.data, n.value, C.byref(n)))
+        return hashes, nodes
+
+    def tax_note(self):
+        return self.eng.lib.mg_screen_tax_note(self.h).decode()
+
+
+TAX_NONE = 0xFFFFFFFF          # MG_TAX_NONE: a row without a node / a hash none of whose rows has one
+TAX_DISJOINT = 0xFFFFFFFE      # MG_TAX_DISJOINT: a hash whose rows lie under different roots
+TAXON_DTYPE = np.dtype([("node", np.uint32), ("tax_count", np.uint32), ("tax_hash_count", np.uint32), ("clade_count", np.uint32),
+                        ("clade_hash_count", np.uint32)])
+
+
+class Taxonomy:
+    """One mg_taxonomy: a forest over dense node indices, parent[i] == i for a root; parent and depth live on the device."""
+
+    def __init__(self, eng, parent):
+        self.eng = eng
+        self.parent = np.ascontiguousarray(parent, dtype=np.uint32)
+        self.h = C.c_void_p()
+        eng._check(eng.lib.mg_taxonomy_create(eng.ctx, self.parent.ctypes.data, len(self.parent), C.byref(self.h)))
+
+    def free(self):
+        if self.h:
+            self.eng.lib.mg_taxonomy_free(self.h)
+            self.h = C.c_void_p()
 
 
 HIT_DTYPE = np.dtype([("row", np.uint32), ("count", np.uint32), ("hash", np.uint64)])
@@ -300,6 +359,14 @@ def load_library():
     lib.mg_screen_finish_sparse_host.argtypes = [vp, vp, u64, C.POINTER(u64), vp, C.POINTER(u32), C.POINTER(u64)]
     lib.mg_screen_tier_note.argtypes = [vp]
     lib.mg_screen_tier_note.restype = C.c_char_p
+    lib.mg_taxonomy_create.argtypes = [vp, vp, u64, C.POINTER(vp)]
+    lib.mg_taxonomy_free.argtypes = [vp]
+    lib.mg_taxonomy_free.restype = None
+    lib.mg_screen_set_taxa.argtypes = [vp, vp, vp, u64]
+    lib.mg_screen_tax_finish_host.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u32), C.POINTER(u64)]
+    lib.mg_screen_hash_taxa_host.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    lib.mg_screen_tax_note.argtypes = [vp]
+    lib.mg_screen_tax_note.restype = C.c_char_p
     lib.mg_dscreen_finish_sparse_host.argtypes = [vp, vp, u64, C.POINTER(u64), vp, C.POINTER(u32), C.POINTER(u64)]
     lib.mg_dscreen_reset.argtypes = [vp]
     lib.mg_identity.argtypes = [u64, u64, i32]
@@ -893,6 +960,11 @@ class MashGpu:
         """incremental screen against table `db` (see ScreenSession); translate=True: amino-acid
         sketches against a nucleotide mixture, translated in six frames on the device"""
         return ScreenSession(self, db, p, translate)
+
+    def taxonomy(self, parent):
+        """a Taxonomy (device-resident parent / depth arrays) for ScreenSession.set_taxa; raises for a cycle or an index
+        out of range"""
+        return Taxonomy(self, parent)
 
     def screen(self, db, p, batches):
         """Containment counts of every hash of table `db` in a mixture given as batches of

@@ -5,6 +5,7 @@
 // host_compare.cpp comparing: tile engine, inverted-index engine, finishing, thresholded and list outputs
 // host_comm.cpp    several GPUs: communicator, replicated / row-sharded tables, sharded calls
 // host_screen.cpp  screening, on one GPU and on several
+// host_taxscreen.cpp  taxonomy of a screen: per-hash LCA, per-taxon counts
 // The entry points of include/mashgpu.h get their C linkage from that header; everything declared here is C++.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include "pvalue.h"
 #include "screen_internal.h"
 #include "sketch_internal.h"
+#include "taxscreen_internal.h"
 
 struct ProfRec { hipEvent_t a, b; };
 
@@ -321,3 +323,45 @@ struct mg_dtable {
 int comm_fail(mg_comm *c, int code, const std::string &msg);
 int dtable_check(mg_comm *c, const mg_dtable *t, const char *who, bool rows_ok = false);
 int comm_sync_all(mg_comm *c);          // every context of a local communicator: wait for its stream
+
+// ---- host_screen.cpp
+struct mg_screen {
+    mg_ctx *ctx = nullptr;
+    mg_params p;
+    const mg_table *db = nullptr;
+    unsigned long long *keys = nullptr;
+    uint32_t *obs = nullptr;
+    uint64_t slots = 0;
+    uint64_t key_max = 0;
+    bool translate = false;             // mixture is nucleotide, queries are amino-acid sketches
+    std::vector<uint64_t> mix;          // running bottom-s of the mixture (host, ascending, distinct)
+    uint64_t distinct = 0;              // distinct hashes of the database (counted while the table is built)
+    // what a job touched: slots whose counter left 0 (device list), so that results and reset are O(touched)
+    uint32_t *touched = nullptr;
+    unsigned long long *ntouched = nullptr;      // device; [1] = cursor of the hit list
+    uint64_t touched_cap = 0;
+    // rows by slot (built at the first sparse finish): slot_end[slot] = end of its run in ent
+    uint32_t *slot_end = nullptr, *ent = nullptr;
+    // second tier of the key bound (SketchArgs::probe_tier): keys above `tier` are announced by a bitmap
+    uint64_t tier = 0, bits_scale = 0;
+    uint32_t *bits = nullptr;
+    std::string tier_note;
+    // taxonomy bound to the database (mg_screen_set_taxa, host_taxscreen.cpp); all of it stays over mg_screen_reset but tax_count
+    struct Tax {
+        const mg_taxonomy *tax = nullptr;
+        uint32_t *slot_node = nullptr;        // per slot: LCA node of the rows holding its key (mg::TAX_* beside node indices)
+        uint32_t *hash_count = nullptr;       // [n_nodes + 2] distinct hashes per bucket (database histogram)
+        uint32_t *count = nullptr;            // [n_nodes + 2] observed hashes per bucket (this mixture)
+        uint32_t *list = nullptr, *vals = nullptr;   // buckets that carry hashes, ascending (m of them); gather target
+        std::vector<uint32_t> nodes, hash_counts, clade_hash_counts;   // host copy of the list, its database columns
+        std::vector<int32_t> up;              // position of a list entry's parent in the list (-1: none)
+        uint64_t long_runs = 0, builds = 0;
+        std::string note;
+    } tx;
+};
+int screen_touched(mg_screen *sc, uint64_t *nt);      // number of touched slots (one 8-byte read-back)
+int screen_ensure_index(mg_screen *sc);               // rows by slot, once per database
+
+// ---- host_taxscreen.cpp
+hipError_t screen_tax_clear(mg_screen *sc, uint64_t nt);   // zero the mixture's taxon counters over the first nt touched slots
+void screen_tax_release(mg_screen *sc);

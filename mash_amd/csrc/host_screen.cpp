@@ -3,29 +3,6 @@
 
 /* ------------------------------------------------------------------ screening */
 
-struct mg_screen {
-    mg_ctx *ctx = nullptr;
-    mg_params p;
-    const mg_table *db = nullptr;
-    unsigned long long *keys = nullptr;
-    uint32_t *obs = nullptr;
-    uint64_t slots = 0;
-    uint64_t key_max = 0;
-    bool translate = false;             // mixture is nucleotide, queries are amino-acid sketches
-    std::vector<uint64_t> mix;          // running bottom-s of the mixture (host, ascending, distinct)
-    uint64_t distinct = 0;              // distinct hashes of the database (counted while the table is built)
-    // what a job touched: slots whose counter left 0 (device list), so that results and reset are O(touched)
-    uint32_t *touched = nullptr;
-    unsigned long long *ntouched = nullptr;      // device; [1] = cursor of the hit list
-    uint64_t touched_cap = 0;
-    // rows by slot (built at the first sparse finish): slot_end[slot] = end of its run in ent
-    uint32_t *slot_end = nullptr, *ent = nullptr;
-    // second tier of the key bound (SketchArgs::probe_tier): keys above `tier` are announced by a bitmap
-    uint64_t tier = 0, bits_scale = 0;
-    uint32_t *bits = nullptr;
-    std::string tier_note;
-};
-
 // Two-tier key bound.  A k-mer hash above the table's largest key cannot be a key; that bound is only as
 // good as the database's SMALLEST genome (bottom-s hashes of a 30 kbp virus reach 1/30 of the hash range, those
 // of a 5 Mbp bacterium 1/5000).  So the range is cut at `tier`: below it a hash goes to the table as before,
@@ -275,7 +252,7 @@ int mg_screen_finish_host(mg_screen *sc, uint32_t *counts_out, uint64_t *mix_has
     return MG_OK;
 }
 
-static int screen_touched(mg_screen *sc, uint64_t *nt)
+int screen_touched(mg_screen *sc, uint64_t *nt)
 {
     unsigned long long v = 0;
     if (hipMemcpyAsync(&v, sc->ntouched, 8, hipMemcpyDeviceToHost, sc->ctx->stream) != hipSuccess || hipStreamSynchronize(sc->ctx->stream) != hipSuccess)
@@ -294,7 +271,8 @@ int mg_screen_reset(mg_screen *sc)
     uint64_t nt = 0;
     const int rc = screen_touched(sc, &nt);
     if (rc != MG_OK) return rc;
-    hipError_t e = mg::launch_screen_reset(sc->touched, nt, sc->obs, ctx->stream);
+    hipError_t e = screen_tax_clear(sc, nt);                // (per-mixture taxon counters, while the touched list still says where they are)
+    if (e == hipSuccess) e = mg::launch_screen_reset(sc->touched, nt, sc->obs, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(sc->ntouched, 0, 8, ctx->stream);
     if (e != hipSuccess) return fail(ctx, MG_ERR_HIP, std::string("mg_screen_reset: ") + hipGetErrorString(e));
     sc->mix.clear();
@@ -304,7 +282,7 @@ int mg_screen_reset(mg_screen *sc)
 const char *mg_screen_tier_note(const mg_screen *sc) { return sc ? sc->tier_note.c_str() : ""; }
 
 // rows by slot, once per database
-static int screen_ensure_index(mg_screen *sc)
+int screen_ensure_index(mg_screen *sc)
 {
     if (sc->slot_end) return MG_OK;
     mg_ctx *ctx = sc->ctx;
@@ -398,6 +376,7 @@ void mg_screen_free(mg_screen *sc)
     hipSetDevice(sc->ctx->device);
     for (void *q : {(void *)sc->keys, (void *)sc->obs, (void *)sc->touched, (void *)sc->ntouched, (void *)sc->slot_end, (void *)sc->ent, (void *)sc->bits})
         if (q) hipFree(q);
+    screen_tax_release(sc);
     delete sc;
 }
 

@@ -1,4 +1,4 @@
-// mash_main.cpp — `mash sketch | dist | triangle | info | paste | screen` on the MI355X hot path.
+// mash_main.cpp — `mash sketch | dist | triangle | info | paste | screen | taxscreen | bounds` on the MI355X hot path.
 //
 // Host C++ above the C ABI (include/mashgpu.h).  Option letters, defaults, file naming,
 // stdout/stderr text and output order follow the reference commands
@@ -37,6 +37,8 @@
 #include "fastx.h"
 #include "msh_file.h"
 #include "parse_pool.h"
+#include "taxdb.h"
+#include "../csrc/pvalue.h"
 
 using std::cerr;
 using std::cout;
@@ -1724,6 +1726,56 @@ int cmd_paste(int argc, const char **argv)
     return 0;
 }
 
+// The pool of `mash screen` and `mash taxscreen`: args[1..] are its files ("-" = stdin, first only); records are read round
+// robin over the inputs (CommandScreen.cpp:197-270), those shorter than k dropped, and handed to `add` in batches joined
+// with MG_RECORD_SEP.  Returns the number of records seen.
+uint64_t stream_pools(const vector<string> &args, int kmer, const std::function<void(const uint8_t *, size_t)> &add)
+{
+    const int nq = (int)args.size() - 1;
+    vector<fastx::Reader *> readers;
+    for (int f = 1; f <= nq; f++) {
+        if (args[f] == "-" && f > 1) { cerr << "ERROR: '-' for stdin must be first query" << endl; exit(1); }
+        fastx::Reader *r = new fastx::Reader;
+        if (!r->open(args[f])) { cerr << "ERROR: could not open " << args[f] << endl; exit(1); }
+        readers.push_back(r);
+    }
+    vector<uint8_t> batch;
+    batch.reserve(256u << 20);
+    size_t screen_batch_bytes = 255u << 20;
+    if (const char *e = getenv("MASH_AMD_SCREEN_BATCH")) screen_batch_bytes = std::max<size_t>(64, strtoull(e, nullptr, 10));   // test knob
+    auto flush = [&]() {
+        if (batch.empty()) return;
+        add(batch.data(), batch.size());
+        batch.clear();
+    };
+    fastx::Record rec;
+    size_t it = 0;
+    long l = -1;
+    uint64_t count = 0;
+    while (!readers.empty()) {
+        l = readers[it]->next(rec);
+        if (l < -1) break;
+        if (l == -1) {
+            delete readers[it];
+            readers.erase(readers.begin() + it);
+            if (it == readers.size()) it = 0;
+            continue;
+        }
+        count++;
+        if (l >= kmer) {
+            batch.insert(batch.end(), rec.seq.begin(), rec.seq.end());
+            batch.push_back((uint8_t)MG_RECORD_SEP);
+            if (batch.size() > screen_batch_bytes) flush();
+        }
+        it++;
+        if (it == readers.size()) it = 0;
+    }
+    for (auto *r : readers) delete r;
+    if (l != -1) { cerr << "\nERROR: reading inputs" << endl; exit(1); }
+    flush();
+    return count;
+}
+
 // mash screen (CommandScreen.cpp:54-461), nucleotide query sketches
 int cmd_screen(int argc, const char **argv)
 {
@@ -1759,48 +1811,9 @@ int cmd_screen(int argc, const char **argv)
         return 1;
     }
     const int nq = (int)c.args.size() - 1;
-    vector<fastx::Reader *> readers;
-    for (int f = 1; f <= nq; f++) {
-        if (c.args[f] == "-" && f > 1) { cerr << "ERROR: '-' for stdin must be first query" << endl; exit(1); }
-        fastx::Reader *r = new fastx::Reader;
-        if (!r->open(c.args[f])) { cerr << "ERROR: could not open " << c.args[f] << endl; exit(1); }
-        readers.push_back(r);
-    }
-    // mixture records, round robin over the inputs (CommandScreen.cpp:197-270); records < k are dropped
-    vector<uint8_t> batch;
-    batch.reserve(256u << 20);
-    size_t screen_batch_bytes = 255u << 20;
-    if (const char *e = getenv("MASH_AMD_SCREEN_BATCH")) screen_batch_bytes = std::max<size_t>(64, strtoull(e, nullptr, 10));   // test knob
-    auto flush = [&]() {
-        if (batch.empty()) return;
-        if (mg_dscreen_add_host(sc, batch.data(), batch.size()) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; exit(1); }
-        batch.clear();
-    };
-    fastx::Record rec;
-    size_t it = 0;
-    long l = -1;
-    uint64_t count = 0;
-    while (!readers.empty()) {
-        l = readers[it]->next(rec);
-        if (l < -1) break;
-        if (l == -1) {
-            delete readers[it];
-            readers.erase(readers.begin() + it);
-            if (it == readers.size()) it = 0;
-            continue;
-        }
-        count++;
-        if (l >= set.p.kmer) {
-            batch.insert(batch.end(), rec.seq.begin(), rec.seq.end());
-            batch.push_back((uint8_t)MG_RECORD_SEP);
-            if (batch.size() > screen_batch_bytes) flush();
-        }
-        it++;
-        if (it == readers.size()) it = 0;
-    }
-    for (auto *r : readers) delete r;
-    if (l != -1) { cerr << "\nERROR: reading inputs" << endl; exit(1); }
-    flush();
+    const uint64_t count = stream_pools(c.args, set.p.kmer, [&](const uint8_t *b, size_t nb) {
+        if (mg_dscreen_add_host(sc, b, nb) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; exit(1); }
+    });
     // what the mixture touched: one hit per (sketch, hash) that was observed -- not the n x s matrix of
     // counters, of which a mixture leaves all but a fraction of a per cent at zero
     vector<uint64_t> mix(s);
@@ -1861,6 +1874,137 @@ int cmd_screen(int argc, const char **argv)
             cout << identity << '\t' << shared[i] << '/' << denom << '\t' << (shared[i] > 0 ? depths[i].at(shared[i] / 2) : 0)
                  << '\t' << pv << '\t' << set.refs[i].name << '\t' << set.refs[i].comment << endl;
         }
+    }
+    return 0;
+}
+
+// mash taxscreen (CommandTaxScreen.cpp:57-474): a screen whose result is a Kraken-style report over a taxonomy.  One device:
+// the per-hash LCA, the per-taxon histograms and the clade sums are libmashgpu's (mg_screen_set_taxa / mg_screen_tax_finish_host).
+int cmd_taxscreen(int argc, const char **argv)
+{
+    Cmd c;
+    c.name = "taxscreen";
+    c.add("help", Opt::Boolean, "h");
+    c.add("threads", Opt::Integer, "p", "1");
+    c.add("identity", Opt::Number, "i", "0", -1., 1.);      // read and never used by the reference (:75-76): accepted, no effect
+    c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
+    c.add("mapping-file", Opt::String, "m", "");
+    c.add("taxonomy-dir", Opt::String, "t", ".");
+    if (c.parse(argc, argv)) return 1;
+    if (c.args.size() < 2 || c.o("help").active) {
+        cout << "\nUsage:\n\n  mash taxscreen [options] <queries>.msh <pool> [<pool>] ...\n\n"
+                "Kraken-style taxonomic report of how well the query sketches are contained in a pool of sequences.\n"
+                "Output fields: [total percent of hashes, contained hashes in the clade, contained hashes in the taxon,\n"
+                "hashes in the clade, hashes in the taxon, rank, taxonomy ID, padded name].\n"
+                "Options: -m <mapping file: taxid, one separator, reference name> -t <directory with nodes.dmp and names.dmp>\n"
+                "         -p <threads> -i <min identity> -v <max p-value> (the last three are accepted and change nothing)\n\n";
+        return 0;
+    }
+    if (!has_suffix(c.args[0], kSuffix)) { cerr << "ERROR: " << c.args[0] << " does not look like a sketch (.msh)" << endl; exit(1); }
+    SketchSet set;
+    load_msh_into(set, c.args[0], true);
+    const bool trans = set.p.alphabet == normalise_alphabet(kAlphabetProtein, false);
+    const string dir = c.o("taxonomy-dir").arg, names_file = dir + "/names.dmp", nodes_file = dir + "/nodes.dmp";
+    if (!std::ifstream(names_file).good() || !std::ifstream(nodes_file).good()) {
+        cerr << "Could not find a file names.dmp or nodes.dmp in directory " << dir << "\n"
+             << " The NCBI taxonomy dump (taxdump.tar.gz, pub/taxonomy on the NCBI FTP server) holds both.\n" << endl;
+        exit(1);
+    }
+    cerr << "Loading taxonomy files ..." << endl;
+    taxdb::Taxonomy tax;
+    string err;
+    if (!tax.load(nodes_file, names_file, &err)) { cerr << "ERROR: " << err << endl; exit(1); }
+    cerr << "   " << tax.nodes.size() << " distinct taxa\n";
+    cerr << "Reading mapping file ..." << endl;
+    const uint64_t n = set.refs.size(), s = set.p.sketch_size;
+    vector<string> names(n), comments(n);
+    for (uint64_t i = 0; i < n; i++) { names[i] = set.refs[i].name; comments[i] = set.refs[i].comment; }
+    vector<uint64_t> row_taxid;
+    if (!taxdb::reference_taxids(names, comments, c.o("mapping-file").arg, &row_taxid)) { cerr << "ERROR: unable to open mapping file" << endl; exit(1); }
+    for (uint64_t i = 0; i < n; i++)
+        if (row_taxid[i] == 0) cerr << "Could not find taxID for reference " << names[i] << " in comment field or mapping file!" << endl;
+    const taxdb::Binding bind(tax, row_taxid);
+    Gpu gpu;
+    cerr << "Loading " << c.args[0] << "..." << endl;
+    mg_dtable *t = upload_all(gpu, set, s);
+    mg_params mp;
+    mg_params_init(&mp, set.p.kmer, s, set.p.seed, set.p.alphabet.c_str(), set.p.noncanonical, set.p.preserve_case);
+    auto die = [&]() { cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl; exit(1); };
+    mg_screen *sc = nullptr;
+    mg_taxonomy *mt = nullptr;
+    if ((trans ? mg_screen_create_translated(gpu.ctx, &mp, mg_dtable_local(t, 0), &sc) : mg_screen_create(gpu.ctx, &mp, mg_dtable_local(t, 0), &sc)) != MG_OK) die();
+    cerr << "Assigning LCA taxIDs to hashes ..." << endl;    // (once per database, before the pool is read: it does not depend on it)
+    if (mg_taxonomy_create(gpu.ctx, bind.parent.data(), bind.parent.size(), &mt) != MG_OK) die();
+    if (mg_screen_set_taxa(sc, mt, bind.row_node.data(), n) != MG_OK) die();
+    const int nq = (int)c.args.size() - 1;
+    cerr << (trans ? "Translating from " : "Streaming from ");
+    if (nq == 1) cerr << c.args[1]; else cerr << nq << " inputs";
+    cerr << "..." << endl;
+    const uint64_t count = stream_pools(c.args, set.p.kmer, [&](const uint8_t *b, size_t nb) { if (mg_screen_add_host(sc, b, nb) != MG_OK) die(); });
+    vector<uint64_t> mix(s);
+    uint32_t mix_n = 0;
+    uint64_t distinct = 0, ntaxa = 0, total = 0, total_hash = 0;
+    if (mg_screen_tax_finish_host(sc, nullptr, 0, &ntaxa, nullptr, nullptr, nullptr, nullptr, nullptr) != MG_OK) die();
+    vector<mg_taxon_count> taxa(ntaxa);
+    if (mg_screen_tax_finish_host(sc, taxa.data(), ntaxa, &ntaxa, &total, &total_hash, mix.data(), &mix_n, &distinct) != MG_OK) die();
+    mg_screen_free(sc);
+    mg_taxonomy_free(mt);
+    mg_dtable_free(t);
+    cerr << "   " << distinct << " distinct hashes." << endl;
+    if (count == 0) { cerr << "\nERROR: Did not find sequence records in inputs" << endl; exit(1); }
+    double est = 0;
+    if (mix_n) est = std::pow(2.0, set.p.use64 ? 64.0 : 32.0) * (double)mix_n / (double)mix[mix_n - 1];
+    cerr << "   Estimated distinct" << (trans ? " (translated)" : "") << " k-mers in pool: " << (uint64_t)est << endl;
+    if ((uint64_t)est == 0) cerr << "WARNING: no valid k-mers in input." << endl;
+    cerr << "Writing output..." << endl;
+    taxdb::write_report(stdout, tax, taxdb::counts_by_taxid(tax, bind, taxa.data(), ntaxa), total);
+    return 0;
+}
+
+// mash bounds (CommandBounds.cpp:33-136): a table of error bounds, host arithmetic only
+int cmd_bounds(int argc, const char **argv)
+{
+    Cmd c;
+    c.name = "bounds";
+    c.add("help", Opt::Boolean, "h");
+    c.add("kmer", Opt::Integer, "k", "21", 1, 32);
+    c.add("prob", Opt::Number, "p", "0.99", 0, 1);
+    if (c.parse(argc, argv)) return 1;
+    if (c.o("help").active) {
+        cout << "\nUsage:\n\n  mash bounds [options]\n\nPrint a table of Mash error bounds for various sketch sizes and Mash distances.\n"
+                "Options: -k <k-mer size> -p <probability that an estimate is within the bounds>\n\n";
+        return 0;
+    }
+    const int sketch_sizes[] = {100, 500, 1000, 5000, 10000, 50000, 100000, 500000, 1000000};
+    const double dists[] = {0.05, 0.1, 0.15, 0.2, 0.25, 0.3, 0.35, 0.4};
+    const int k = (int)c.o("kmer").num;
+    const double q2 = (1.0 - c.o("prob").num) / 2.0;
+    cout << endl << "Parameters (run with -h for details):" << endl;
+    cout << "   k:   " << k << endl;
+    cout << "   p:   " << c.o("prob").num << endl << endl;
+    for (int cont = 0; cont < 2; cont++) {
+        cout << (cont ? "\tScreen distance" : "\tMash distance") << endl;
+        cout << "Sketch";
+        for (double d : dists) cout << '\t' << d;
+        cout << endl;
+        for (int s : sketch_sizes) {
+            cout << s;
+            for (double d : dists) {
+                const double m2j = cont ? pow(1.0 - d, k) : 1.0 / (2.0 * exp(k * d) - 1.0);
+                // the least x < s with P(X <= x) > q2, else s.  P(X <= x) = 1 - P(X > x) does not fall as x grows, so the
+                // reference's scan from 0 and a bisection find the same x.
+                int lo = 0, hi = s;
+                while (lo < hi) {
+                    const int x = lo + (hi - lo) / 2;
+                    if (1.0 - mg::binomial_q((uint64_t)x, m2j, (uint64_t)s) > q2) hi = x; else lo = x + 1;
+                }
+                const double je = double(lo) / s;
+                const double j2m = cont ? 1.0 - pow(je, 1. / k) : -1.0 / k * log(2.0 * je / (1.0 + je));
+                cout << '\t' << j2m - d;
+            }
+            cout << endl;
+        }
+        cout << endl;
     }
     return 0;
 }
@@ -1930,7 +2074,9 @@ int main(int argc, const char **argv)
         "  dist      Estimate the distance of query sequences to references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
-        "  screen    Determine whether query sequences are within a larger mixture of sequences.\n\n";
+        "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
+        "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"
+        "  bounds    Print a table of Mash error bounds.\n\n";
     if (argc < 2) { cout << usage; return 0; }
     const string cmd = argv[1];
     const bool timing = getenv("MASH_AMD_TIMING") != nullptr;
@@ -1947,6 +2093,8 @@ int main(int argc, const char **argv)
     else if (cmd == "info") rc = cmd_info(argc - 2, argv + 2);
     else if (cmd == "paste") rc = cmd_paste(argc - 2, argv + 2);
     else if (cmd == "screen") rc = cmd_screen(argc - 2, argv + 2);
+    else if (cmd == "taxscreen") rc = cmd_taxscreen(argc - 2, argv + 2);
+    else if (cmd == "bounds") rc = cmd_bounds(argc - 2, argv + 2);
     else if (cmd == "json2msh") rc = cmd_json2msh(argc - 2, argv + 2);
     else if (cmd == "--version") { cout << "2.3-mi355x" << endl; rc = 0; }
     else {
