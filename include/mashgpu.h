@@ -538,6 +538,38 @@ int  mg_screen_tax_finish_host(mg_screen *sc, mg_taxon_count *out, uint64_t capa
                                uint64_t *total_hash_count, uint64_t *mix_hashes_out, uint32_t *mix_nhash_out, uint64_t *distinct_out);
 int  mg_screen_hash_taxa_host(mg_screen *sc, uint64_t *hashes_out, uint32_t *nodes_out, uint64_t capacity, uint64_t *n_out);
 const char *mg_screen_tax_note(const mg_screen *sc);
+/* ---- finished rows of a screen (`mash screen` from "Summing shared..." to its last output line) ------------
+ * mg_screen_results_host replaces CommandScreen.cpp:331-455 for the mixture added so far; one record per output line
+ * (:418-455).  One device: the sharded screen (mg_dscreen_*) has no such call either.
+ *   denom    the row's number of hashes (hashesSorted.size()); shared = how many of them were observed at least once
+ *            (minCov is 1, :235, :338-355).
+ *   winner   != 0 is -w (:357-407): a row's score is mg_identity(shared, denom, k) of the counts above; every observed
+ *            hash is then given to ONE of its holders -- the highest score, among equal scores the larger
+ *            Reference::length, among those the LOWEST ROW INDEX -- and shared and the depths are recounted from that
+ *            assignment.  The reference walks an unordered_set of holders there, so its choice among full ties (equal
+ *            score and equal length) is unspecified; this call's is not.  Lengths are the table's (mg_table_upload's
+ *            `lengths`): MG_ERR_INVALID when winner is asked of a table without them.
+ *   median   the sorted observation counts of the row's (re)assigned hashes at index shared / 2; 0 when shared == 0
+ *            (:409-414, :436).
+ *   identity mg_identity(shared, denom, k); p_value = mg_p_value_within(shared, set_size, kmer_space, denom) with
+ *            set_size = (uint64_t)(2^bits * mix_n / mix[mix_n - 1]), 0 for an empty mixture sketch, bits = 64 or 32 as the
+ *            screen's parameters say (:322, MinHashHeap.h:45); *set_size_out returns it.  Both doubles are bit-equal to
+ *            what the two host functions below return for the same arguments.
+ * A row is emitted when (shared != 0 or min_identity < 0) and identity >= min_identity and p_value <= max_p_value
+ * (:420-434); rows come in ascending row order.  *n_out = their number; the first min(capacity, *n_out) are written
+ * (capacity 0 sizes the buffer).  The mixture outputs are those of mg_screen_finish_host, each optional.
+ * The call does not consume the mixture: it may be repeated with other filters or `winner` and mixed with
+ * mg_screen_finish_sparse_host and mg_screen_tax_finish_host; mg_screen_reset readies the next mixture.  Translated
+ * screens work unchanged.  Cost proportional to what the mixture touched (hits and holders) plus passes over per-row
+ * arrays of 4 bytes.  MG_ERR_UNSUPPORTED beyond 2^31 database hashes, as for mg_screen_finish_sparse_host, and for a
+ * database whose distinct sketch lengths need an identity table of more than 2^24 entries. */
+typedef struct mg_screen_result {      /* one output line of `mash screen`, CommandScreen.cpp:418-455 */
+    uint32_t row, shared, denom, median;
+    double identity, p_value;
+} mg_screen_result;                    /* 32 bytes */
+int  mg_screen_results_host(mg_screen *sc, double kmer_space, int winner, double min_identity, double max_p_value,
+                            mg_screen_result *out, uint64_t capacity, uint64_t *n_out, uint64_t *set_size_out,
+                            uint64_t *mix_hashes_out, uint32_t *mix_nhash_out, uint64_t *distinct_out);
 /* estimateIdentity (CommandScreen.cpp:463-482) and pValueWithin (:601-615), host arithmetic. */
 double mg_identity(uint64_t common, uint64_t denom, int kmer_size);
 double mg_p_value_within(uint64_t x, uint64_t set_size, double kmer_space, uint64_t sketch_size);

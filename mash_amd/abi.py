@@ -36,6 +36,7 @@ EXPORTS = [
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
     "mg_taxonomy_create", "mg_taxonomy_free", "mg_screen_set_taxa", "mg_screen_tax_finish_host", "mg_screen_hash_taxa_host", "mg_screen_tax_note",
+    "mg_screen_results_host",
     "mg_identity", "mg_p_value_within",
     "mg_comm_create_local", "mg_comm_unique_id", "mg_comm_create_rank", "mg_comm_destroy", "mg_comm_size", "mg_comm_rank",
     "mg_comm_uses_rccl", "mg_comm_ctx", "mg_comm_last_error", "mg_shard_tri_rows", "mg_shard_tri_rows_weighted", "mg_shard_tri_rows_costed", "mg_shard_rows", "mg_dtable_upload",
@@ -166,6 +167,24 @@ class ScreenSession:
         res = (taxa[: min(cap, n.value)], int(tot.value), int(tot_h.value), mix[: mn.value].copy(), int(dist.value))
         return res if capacity is None else res + (int(n.value),)
 
+    def results(self, kmer_space, winner=False, min_identity=0.0, max_p=1.0, capacity=None):
+        """(rows SCREEN_RESULT_DTYPE[n] in row order, set_size, mixture sketch, distinct table hashes): the finished rows of
+        `mash screen` for the mixture added so far.  capacity: size of the buffer handed to the library (None: sized by
+        a first call); the returned array holds min(capacity, n) entries and `n` is returned as a fifth value then."""
+        lib, s = self.eng.lib, int(self.p.sketch_size)
+        n = C.c_uint64(0)
+        args = (self.h, C.c_double(kmer_space), int(bool(winner)), C.c_double(min_identity), C.c_double(max_p))
+        if capacity is None:
+            self.eng._check(lib.mg_screen_results_host(*args, None, 0, C.byref(n), None, None, None, None))
+        cap = n.value if capacity is None else int(capacity)
+        rows = np.zeros(cap, dtype=SCREEN_RESULT_DTYPE)
+        mix = np.zeros(s, dtype=np.uint64)
+        mn, dist, ss = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self.eng._check(lib.mg_screen_results_host(*args, rows.ctypes.data if cap else None, cap, C.byref(n), C.byref(ss),
+                                                   mix.ctypes.data, C.byref(mn), C.byref(dist)))
+        res = (rows[: min(cap, n.value)], int(ss.value), mix[: mn.value].copy(), int(dist.value))
+        return res if capacity is None else res + (int(n.value),)
+
     def hash_taxa(self):
         """(hashes u64[distinct] ascending, nodes u32[distinct]): the LCA node of every distinct database hash"""
         lib = self.eng.lib
@@ -180,6 +199,7 @@ class ScreenSession:
         return self.eng.lib.mg_screen_tax_note(self.h).decode()
 
 
+SCREEN_RESULT_DTYPE = np.dtype([("row", "<u4"), ("shared", "<u4"), ("denom", "<u4"), ("median", "<u4"), ("identity", "<f8"), ("p_value", "<f8")])
 TAX_NONE = 0xFFFFFFFF          # MG_TAX_NONE: a row without a node / a hash none of whose rows has one
 TAX_DISJOINT = 0xFFFFFFFE      # MG_TAX_DISJOINT: a hash whose rows lie under different roots
 TAXON_DTYPE = np.dtype([("node", np.uint32), ("tax_count", np.uint32), ("tax_hash_count", np.uint32), ("clade_count", np.uint32),
@@ -363,6 +383,7 @@ def load_library():
     lib.mg_taxonomy_free.argtypes = [vp]
     lib.mg_taxonomy_free.restype = None
     lib.mg_screen_set_taxa.argtypes = [vp, vp, vp, u64]
+    lib.mg_screen_results_host.argtypes = [vp, C.c_double, C.c_int, C.c_double, C.c_double, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u32), C.POINTER(u64)]
     lib.mg_screen_tax_finish_host.argtypes = [vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u32), C.POINTER(u64)]
     lib.mg_screen_hash_taxa_host.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     lib.mg_screen_tax_note.argtypes = [vp]

@@ -34,6 +34,7 @@
 #include "compare_internal.h"
 #include "finish_internal.h"
 #include "pvalue.h"
+#include "screen_finish_internal.h"
 #include "screen_internal.h"
 #include "sketch_internal.h"
 #include "taxscreen_internal.h"
@@ -125,6 +126,7 @@ struct mg_table {
     const uint64_t *hashes = nullptr;
     const uint32_t *nhash = nullptr;
     const uint64_t *lengths = nullptr;
+    bool has_lengths = true;              // false: uploaded without lengths (the array holds zeros)
     uint64_t n = 0, s = 0;
     bool owns = false;
     // lazily built by the compare path (cached across calls; the table is immutable)
@@ -358,9 +360,23 @@ struct mg_screen {
         uint64_t long_runs = 0, builds = 0;
         std::string note;
     } tx;
+    // finished rows (mg_screen_results_host, screen_finish.hip): all of it is sized by the database, built at the first call
+    // and kept over mg_screen_reset; the per-row counters are zero between calls (dirty: a call failed half way, clear them whole)
+    struct Fin {
+        bool ready = false, dirty = false;
+        double *lut = nullptr;                // mg_identity(x, denom, k) of the host's libm for every denominator of the database
+        uint32_t *lut_start = nullptr;        // [s + 1] first entry of a denominator's row
+        uint32_t *rowbuf = nullptr;           // 7 x n: shared, shared_w, fill | row_off, median, rows, long_rows
+        double *score = nullptr;              // [n]
+        unsigned long long *ctr = nullptr, *masks = nullptr, *seg_off = nullptr;
+        uint32_t *seg_count = nullptr;
+        void *scan_temp = nullptr;
+        size_t scan_temp_bytes = 0;
+    } fin;
 };
 int screen_touched(mg_screen *sc, uint64_t *nt);      // number of touched slots (one 8-byte read-back)
 int screen_ensure_index(mg_screen *sc);               // rows by slot, once per database
+void screen_fin_release(mg_screen *sc);               // what mg_screen_results_host keeps per database
 
 // ---- host_taxscreen.cpp
 hipError_t screen_tax_clear(mg_screen *sc, uint64_t nt);   // zero the mixture's taxon counters over the first nt touched slots

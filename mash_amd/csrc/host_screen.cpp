@@ -356,6 +356,146 @@ int mg_screen_finish_sparse_host(mg_screen *sc, mg_screen_hit *hits_out, uint64_
     return MG_OK;
 }
 
+// what mg_screen_results_host keeps per database: the identity table and the per-row arrays
+static int screen_fin_ensure(mg_screen *sc)
+{
+    mg_screen::Fin &f = sc->fin;
+    if (f.ready) return MG_OK;
+    mg_ctx *ctx = sc->ctx;
+    const mg_table *db = sc->db;
+    const uint64_t n = db->n, s = db->s, nn = std::max<uint64_t>(n, 1);
+    // mg_identity is pow() of the host's libm: tabulated here, one row of denom + 1 entries per denominator that occurs
+    // (nearly always one, denom == s), indexed by the kernels -- finish.hip's scheme for distances
+    std::vector<uint32_t> nh(n);
+    if (n && (hipMemcpyAsync(nh.data(), db->nhash, n * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
+        return fail(ctx, MG_ERR_HIP, "mg_screen_results: D2H copy failed");
+    std::vector<uint32_t> start(s + 1, mg::SRF_NO_LUT);
+    for (uint64_t i = 0; i < n; i++) start[std::min<uint64_t>(nh[i], s)] = 0;
+    uint64_t entries = 0;
+    for (uint64_t d = 0; d <= s; d++)
+        if (start[d] == 0) { start[d] = (uint32_t)entries; entries += d + 1; if (entries > (1ull << 24)) break; }
+    if (entries > (1ull << 24))
+        return fail(ctx, MG_ERR_UNSUPPORTED, "mg_screen_results: the identity table of this database's distinct sketch lengths exceeds 2^24 entries");
+    std::vector<double> lut(std::max<uint64_t>(entries, 1), 0.0);
+    for (uint64_t d = 0; d <= s; d++)
+        if (start[d] != mg::SRF_NO_LUT)
+            for (uint64_t x = 0; x <= d; x++) lut[start[d] + x] = mg_identity(x, d, sc->p.kmer_size);
+    const uint64_t nseg = std::max<uint64_t>(mg::screen_finish_segments(n), 1), words = std::max<uint64_t>(mg::screen_finish_mask_words(n), 1);
+    f.scan_temp_bytes = std::max<size_t>(mg::screen_finish_scan_temp_bytes(nn), 1);
+    hipError_t e = hipMalloc(&f.lut, lut.size() * 8);
+    if (e == hipSuccess) e = hipMalloc(&f.lut_start, (s + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc(&f.rowbuf, 7 * nn * 4);
+    if (e == hipSuccess) e = hipMalloc(&f.score, nn * 8);
+    if (e == hipSuccess) e = hipMalloc(&f.ctr, mg::SRF_CTRS * 8);
+    if (e == hipSuccess) e = hipMalloc(&f.masks, words * 8);
+    if (e == hipSuccess) e = hipMalloc(&f.seg_off, nseg * 8);
+    if (e == hipSuccess) e = hipMalloc(&f.seg_count, nseg * 4);
+    if (e == hipSuccess) e = hipMalloc(&f.scan_temp, f.scan_temp_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.lut, lut.data(), lut.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f.lut_start, start.data(), (s + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(f.rowbuf, 0, 7 * nn * 4, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (the host tables go out of scope)
+    if (e != hipSuccess) {
+        screen_fin_release(sc);
+        return fail(ctx, MG_ERR_HIP, std::string("mg_screen_results (tables): ") + hipGetErrorString(e));
+    }
+    f.ready = true;
+    return MG_OK;
+}
+
+void screen_fin_release(mg_screen *sc)
+{
+    mg_screen::Fin &f = sc->fin;
+    for (void *q : {(void *)f.lut, (void *)f.lut_start, (void *)f.rowbuf, (void *)f.score, (void *)f.ctr, (void *)f.masks, (void *)f.seg_off,
+                    (void *)f.seg_count, f.scan_temp})
+        if (q) hipFree(q);
+    f = mg_screen::Fin();
+}
+
+// estimateSetSize of the mixture's bottom-s (MinHashHeap.h:45, CommandScreen.cpp:322)
+static uint64_t screen_set_size(const mg_screen *sc)
+{
+    if (sc->mix.empty()) return 0;
+    const double est = std::pow(2.0, sc->p.use64 ? 64.0 : 32.0) * (double)sc->mix.size() / (double)sc->mix.back();
+    return (uint64_t)est;
+}
+
+int mg_screen_results_host(mg_screen *sc, double kmer_space, int winner, double min_identity, double max_p_value,
+                           mg_screen_result *out, uint64_t capacity, uint64_t *n_out, uint64_t *set_size_out,
+                           uint64_t *mix_hashes_out, uint32_t *mix_nhash_out, uint64_t *distinct_out)
+{
+    if (!sc) return MG_ERR_INVALID;
+    mg_ctx *ctx = sc->ctx;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!n_out || (!out && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_screen_results_host: NULL argument");
+    if (!sc->touched) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_screen_results_host: databases of more than 2^31 hashes have dense results only (mg_screen_finish_host)");
+    if (winner && (!sc->db->lengths || !sc->db->has_lengths)) return fail(ctx, MG_ERR_INVALID, "mg_screen_results_host: winner needs a table uploaded with lengths");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = screen_ensure_index(sc);
+    if (rc == MG_OK) rc = screen_fin_ensure(sc);
+    uint64_t nt = 0;
+    if (rc == MG_OK) rc = screen_touched(sc, &nt);
+    if (rc != MG_OK) return rc;
+    static_assert(sizeof(mg_screen_result) == sizeof(mg::ScreenResult) && sizeof(mg_screen_result) == 32, "mg_screen_result layout");
+    const uint64_t set_size = screen_set_size(sc), n = sc->db->n;
+    mg_screen::Fin &f = sc->fin;
+    *n_out = 0;
+    if (n) {
+        auto bad = [&](hipError_t e) { return fail(ctx, MG_ERR_HIP, std::string("mg_screen_results: ") + hipGetErrorString(e)); };
+        mg::ScreenFinishArgs a{};
+        a.touched = sc->touched; a.nt = nt; a.obs = sc->obs; a.slot_end = sc->slot_end; a.ent = sc->ent;
+        a.nhash = sc->db->nhash; a.lengths = sc->db->lengths; a.n = n; a.s = (uint32_t)sc->db->s;
+        a.lut = f.lut; a.lut_start = f.lut_start;
+        a.shared = f.rowbuf; a.shared_w = f.rowbuf + n; a.fill = f.rowbuf + 2 * n; a.row_off = f.rowbuf + 3 * n; a.median = f.rowbuf + 4 * n;
+        a.rows = f.rowbuf + 5 * n; a.long_rows = f.rowbuf + 6 * n;
+        a.score = f.score; a.ctr = f.ctr;
+        a.r = (double)set_size / kmer_space; a.min_identity = min_identity; a.max_p = max_p_value; a.all_rows = min_identity < 0.0 ? 1u : 0u;
+        a.masks = f.masks; a.seg_count = f.seg_count; a.seg_off = f.seg_off;
+        hipError_t e = hipSuccess;
+        if (f.dirty) e = hipMemsetAsync(f.rowbuf, 0, 3 * n * 4, ctx->stream);
+        f.dirty = true;
+        if (e == hipSuccess) e = hipMemsetAsync(f.ctr, 0, mg::SRF_CTRS * 8, ctx->stream);
+        unsigned long long ctr[mg::SRF_CTRS] = {0, 0, 0, 0};
+        if (e == hipSuccess && nt) {                              // sizes: hits and touched rows (the one wait before the last)
+            e = mg::launch_srf_shared(a, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(ctr, f.ctr, 2 * 8, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        }
+        if (e != hipSuccess) return bad(e);
+        const uint64_t hits = ctr[mg::SRF_CTR_HITS], nrows = std::min<uint64_t>(ctr[mg::SRF_CTR_ROWS], n);
+        const uint64_t vals_cap = winner ? nt : hits, cand = a.all_rows ? n : nrows;
+        a.out_cap = std::min(capacity, cand);
+        DevBuf<uint32_t> d_vals(ctx), d_win(ctx);
+        DevBuf<mg::ScreenResult> d_out(ctx);
+        if (d_vals.alloc(vals_cap) != hipSuccess || d_win.alloc(winner ? nt : 1) != hipSuccess || d_out.alloc(a.out_cap) != hipSuccess)
+            return fail(ctx, MG_ERR_NOMEM, "mg_screen_results: device allocation failed");
+        a.vals = d_vals; a.winner_row = d_win; a.out = d_out;
+        if (winner) e = mg::launch_srf_winners(a, nrows, ctx->stream);
+        if (e == hipSuccess && nrows) e = mg::launch_srf_offsets(a, winner != 0, f.scan_temp, f.scan_temp_bytes, ctx->stream);
+        if (e == hipSuccess && nrows) e = mg::launch_srf_scatter(a, winner != 0, vals_cap, ctx->stream);
+        if (e == hipSuccess) e = mg::launch_srf_medians(a, winner != 0, nrows, ctx->stream);
+        if (e == hipSuccess) e = mg::launch_srf_rows(a, winner != 0, ctx->stream);
+        if (e == hipSuccess) e = mg::launch_srf_clear(a, nrows, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctr + mg::SRF_CTR_OUT, f.ctr + mg::SRF_CTR_OUT, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return bad(e);
+        f.dirty = false;
+        *n_out = ctr[mg::SRF_CTR_OUT];
+        const uint64_t take = std::min<uint64_t>(*n_out, a.out_cap);
+        if (take) {
+            e = hipMemcpyAsync(out, d_out, take * sizeof(mg_screen_result), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (e != hipSuccess) return bad(e);
+        }
+    }
+    if (set_size_out) *set_size_out = set_size;
+    const uint64_t s = sc->p.sketch_size;
+    if (mix_hashes_out) for (uint64_t i = 0; i < s; i++) mix_hashes_out[i] = i < sc->mix.size() ? sc->mix[i] : MG_HASH_PAD;
+    if (mix_nhash_out) *mix_nhash_out = (uint32_t)sc->mix.size();
+    if (distinct_out) *distinct_out = sc->distinct;
+    return MG_OK;
+}
+
 double mg_identity(uint64_t common, uint64_t denom, int kmer_size)
 {
     if (common == denom) return 1.;                       // avoid -0
@@ -377,6 +517,7 @@ void mg_screen_free(mg_screen *sc)
     for (void *q : {(void *)sc->keys, (void *)sc->obs, (void *)sc->touched, (void *)sc->ntouched, (void *)sc->slot_end, (void *)sc->ent, (void *)sc->bits})
         if (q) hipFree(q);
     screen_tax_release(sc);
+    screen_fin_release(sc);
     delete sc;
 }
 

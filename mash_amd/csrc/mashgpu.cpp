@@ -309,6 +309,7 @@ int mg_table_upload(mg_ctx *ctx, const uint64_t *hashes, const uint32_t *nhash, 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     mg_table *t = new mg_table;
     t->ctx = ctx; t->hashes = dh.release(); t->nhash = dn.release(); t->lengths = dl.release(); t->n = n; t->s = s; t->owns = true;
+    t->has_lengths = lengths != nullptr;
     *out = t;
     return MG_OK;
 }

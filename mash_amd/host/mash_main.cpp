@@ -1776,7 +1776,9 @@ uint64_t stream_pools(const vector<string> &args, int kmer, const std::function<
     return count;
 }
 
-// mash screen (CommandScreen.cpp:54-461), nucleotide query sketches
+// mash screen (CommandScreen.cpp:54-461).  One device: the rows come finished from libmashgpu (mg_screen_results_host: shared,
+// winners, medians, identity, p-value and both filters on the device).  Several devices, or MASH_AMD_HOST_SCREEN_FINISH=1
+// (test knob, the counterpart of MASH_AMD_HOST_FINISH): the sharded screen's sparse hits and the tail on the host.
 int cmd_screen(int argc, const char **argv)
 {
     Cmd c;
@@ -1798,6 +1800,7 @@ int cmd_screen(int argc, const char **argv)
     SketchSet set;
     load_msh_into(set, c.args[0], true);
     const bool trans = set.p.alphabet == normalise_alphabet(kAlphabetProtein, false);   // CommandScreen.cpp:120
+    StageClock clk;
     Gpu gpu;
     cerr << "Loading " << c.args[0] << "..." << endl;
     const uint64_t n = set.refs.size(), s = set.p.sketch_size;
@@ -1805,12 +1808,47 @@ int cmd_screen(int argc, const char **argv)
     mg_dtable *t = upload_all(gpu, set, s);
     mg_params mp;
     mg_params_init(&mp, set.p.kmer, s, set.p.seed, set.p.alphabet.c_str(), set.p.noncanonical, set.p.preserve_case);
+    clk.lap("device");
+    const int nq = (int)c.args.size() - 1;
+    const double kspace = set.kmer_space();
+    const bool winner = c.o("winning!").active;
+    auto announce = [&](uint64_t distinct, uint64_t count, uint64_t set_size) {
+        cerr << "   " << distinct << " distinct hashes." << endl;
+        cerr << (trans ? "Translating from " : "Streaming from ");
+        if (nq == 1) cerr << c.args[1]; else cerr << nq << " inputs";
+        cerr << "..." << endl;
+        if (count == 0) { cerr << "\nERROR: Did not find sequence records in inputs" << endl; exit(1); }
+        cerr << "   Estimated distinct" << (trans ? " (translated)" : "") << " k-mers in mixture: " << set_size << endl;
+        if (set_size == 0) cerr << "WARNING: no valid k-mers in input." << endl;
+    };
+    if (mg_comm_size(gpu.comm) == 1 && !getenv("MASH_AMD_HOST_SCREEN_FINISH")) {
+        auto die = [&]() { cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl; exit(1); };
+        mg_screen *sc = nullptr;
+        if ((trans ? mg_screen_create_translated(gpu.ctx, &mp, mg_dtable_local(t, 0), &sc) : mg_screen_create(gpu.ctx, &mp, mg_dtable_local(t, 0), &sc)) != MG_OK) die();
+        const uint64_t count = stream_pools(c.args, set.p.kmer, [&](const uint8_t *b, size_t nb) { if (mg_screen_add_host(sc, b, nb) != MG_OK) die(); });
+        clk.lap("screen");
+        uint64_t nrows = 0, set_size = 0, distinct = 0;
+        if (mg_screen_results_host(sc, kspace, winner ? 1 : 0, identity_min, p_max, nullptr, 0, &nrows, &set_size, nullptr, nullptr, &distinct) != MG_OK) die();
+        vector<mg_screen_result> rows(nrows);
+        if (nrows && mg_screen_results_host(sc, kspace, winner ? 1 : 0, identity_min, p_max, rows.data(), nrows, &nrows, nullptr, nullptr, nullptr, nullptr) != MG_OK) die();
+        mg_screen_free(sc);
+        mg_dtable_free(t);
+        clk.lap("results");
+        announce(distinct, count, set_size);
+        cerr << "Summing shared..." << endl;
+        if (winner) cerr << "Reallocating to winners..." << endl;
+        cerr << "Computing coverage medians..." << endl;
+        cerr << "Writing output..." << endl;
+        for (const mg_screen_result &r : rows)
+            cout << r.identity << '\t' << r.shared << '/' << r.denom << '\t' << r.median << '\t' << r.p_value << '\t' << set.refs[r.row].name << '\t'
+                 << set.refs[r.row].comment << endl;
+        return 0;
+    }
     mg_dscreen *sc = nullptr;
     if (mg_dscreen_create(gpu.comm, &mp, t, trans ? 1 : 0, &sc) != MG_OK) {
         cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl;
         return 1;
     }
-    const int nq = (int)c.args.size() - 1;
     const uint64_t count = stream_pools(c.args, set.p.kmer, [&](const uint8_t *b, size_t nb) {
         if (mg_dscreen_add_host(sc, b, nb) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; exit(1); }
     });
@@ -1824,23 +1862,17 @@ int cmd_screen(int argc, const char **argv)
     if (nhits && mg_dscreen_finish_sparse_host(sc, hits.data(), nhits, &nhits, nullptr, nullptr, nullptr) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; return 1; }
     mg_dscreen_free(sc);
     mg_dtable_free(t);
-    cerr << "   " << distinct << " distinct hashes." << endl;
-    cerr << (trans ? "Translating from " : "Streaming from ");
-    if (nq == 1) cerr << c.args[1]; else cerr << nq << " inputs";
-    cerr << "..." << endl;
-    if (count == 0) { cerr << "\nERROR: Did not find sequence records in inputs" << endl; exit(1); }
+    clk.lap("screen");
     // estimateSetSize of the mixture's bottom-s (MinHashHeap.h:45, CommandScreen.cpp:322)
     double est = 0;
     if (mix_n) est = std::pow(2.0, set.p.use64 ? 64.0 : 32.0) * (double)mix_n / (double)mix[mix_n - 1];
     const uint64_t set_size = (uint64_t)est;
-    cerr << "   Estimated distinct" << (trans ? " (translated)" : "") << " k-mers in mixture: " << set_size << endl;
-    if (set_size == 0) cerr << "WARNING: no valid k-mers in input." << endl;
+    announce(distinct, count, set_size);
     cerr << "Summing shared..." << endl;
     vector<uint64_t> shared(n, 0);
     vector<vector<uint64_t>> depths(n);
     for (const mg_screen_hit &h : hits) { shared[h.row]++; depths[h.row].push_back(h.count); }       // (ordered by sketch, then hash)
-    const double kspace = set.kmer_space();
-    if (c.o("winning!").active) {
+    if (winner) {
         cerr << "Reallocating to winners..." << endl;
         vector<double> scores(n);
         for (uint64_t i = 0; i < n; i++) scores[i] = mg_identity(shared[i], set.refs[i].hashes.size(), set.p.kmer);
@@ -1875,6 +1907,7 @@ int cmd_screen(int argc, const char **argv)
                  << '\t' << pv << '\t' << set.refs[i].name << '\t' << set.refs[i].comment << endl;
         }
     }
+    clk.lap("host tail");
     return 0;
 }
 
