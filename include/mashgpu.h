@@ -363,6 +363,24 @@ int mg_compare_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_tabl
                                  uint64_t q_end, int kmer_size, double kmer_space, double max_distance,
                                  double max_p_value, mg_result *out_host, uint64_t capacity,
                                  uint64_t *count_out);
+/* The k nearest references of every query, chosen ON THE DEVICE (topk.hip) -- `mash dist -N`.  The reference has no such
+ * option (its user pipes the lines of CommandDistance.cpp:247-304 through sort | head); every record is the reference's
+ * record of that pair, and the order is defined on the exact fraction it prints in column 5 (:289):
+ *   eligible : the pairs mg_compare_rect_pairs_host marks `pass` under the same max_distance / max_p_value conventions;
+ *   order    : pair a before pair b iff numer_a * denom_b > numer_b * denom_a in 64-bit integers (a pair of two empty
+ *              sketches, 0/0, is compared as 0/1: numer == 0 ranks as zero whatever its denom); equal fractions by
+ *              ascending reference index;
+ *   result   : per query its first min(k, eligible) pairs in that order, queries ascending, as mg_result{row = query,
+ *              col = reference, ...} whose doubles are bit-equal to mg_compare_rect_pairs_host's.
+ * capacity / *count_out / MG_ERR_NOMEM as for mg_compare_*_results_host; (q_end - q_begin) * min(k, nref) always suffices.
+ * k == 0: MG_ERR_INVALID; k > MG_TOPK_MAX: MG_ERR_UNSUPPORTED (the selection keeps a query's best k and one chunk of its row
+ * in the LDS of one workgroup); k > nref is clamped.  Both tables must carry lengths.  No distance or p-value is computed for
+ * a pair that is neither tested for eligibility nor selected, and no matrix crosses PCIe. */
+#define MG_TOPK_MAX 1024u
+int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin,
+                              uint64_t q_end, int kmer_size, double kmer_space, double max_distance,
+                              double max_p_value, uint32_t k, mg_result *out_host, uint64_t capacity,
+                              uint64_t *count_out);
 /* Scalar helpers (same arithmetic as the bulk calls). */
 double mg_distance(uint32_t numer, uint32_t denom, int kmer_size);
 double mg_p_value(uint64_t x, uint64_t len_ref, uint64_t len_qry, double kmer_space,
@@ -446,6 +464,13 @@ int mg_compare_tri_results_sharded_host(mg_comm *c, const mg_dtable *t, uint64_t
 int mg_compare_rect_results_sharded_host(mg_comm *c, const mg_dtable *ref, const mg_dtable *qry, uint64_t q_begin,
                                          uint64_t q_end, int kmer_size, double kmer_space, double max_distance,
                                          double max_p_value, mg_result *out_host, uint64_t capacity, uint64_t *count_out);
+/* mg_compare_rect_topk_host over the devices: replicated tables cut the queries and join the lists; a row-sharded reference
+ * gives every device the top k of its reference block, merged per query on the host by the same comparison (columns are
+ * indices into the whole reference).  Output identical to the single-device call. */
+int mg_compare_rect_topk_sharded_host(mg_comm *c, const mg_dtable *ref, const mg_dtable *qry, uint64_t q_begin,
+                                      uint64_t q_end, int kmer_size, double kmer_space, double max_distance,
+                                      double max_p_value, uint32_t k, mg_result *out_host, uint64_t capacity,
+                                      uint64_t *count_out);
 
 /* ---- screening (containment of sketches in a mixture) -----------------------------
  * Replaces, for nucleotide query sketches, the data-parallel part of `mash screen`:

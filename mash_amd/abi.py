@@ -31,7 +31,7 @@ EXPORTS = [
     "mg_compare_tri_filter_host", "mg_compare_rect_filter_host", "mg_compare_tri_sparse_host", "mg_compare_rect_sparse_host", "mg_expand_tri_sparse",
     "mg_finish_tri_host", "mg_finish_rect_host", "mg_distance", "mg_p_value",
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
-    "mg_compare_tri_results_host", "mg_compare_rect_results_host",
+    "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
@@ -43,6 +43,7 @@ EXPORTS = [
     "mg_dtable_free", "mg_dtable_local", "mg_table_broadcast", "mg_comm_allreduce_u32_sum", "mg_dtable_upload_rows", "mg_sketch_sharded_host",
     "mg_compare_tri_sharded_host", "mg_compare_rect_sharded_host", "mg_compare_tri_pairs_sharded_host",
     "mg_compare_rect_pairs_sharded_host", "mg_compare_tri_results_sharded_host", "mg_compare_rect_results_sharded_host",
+    "mg_compare_rect_topk_sharded_host",
     "mg_dscreen_create", "mg_dscreen_add_host", "mg_dscreen_finish_host", "mg_dscreen_free",
 ]
 
@@ -318,6 +319,7 @@ def load_library():
     lib.mg_compare_rect_pairs_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp]
     lib.mg_compare_tri_results_host.argtypes = [vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
     lib.mg_compare_rect_results_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
+    lib.mg_compare_rect_topk_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_comm_create_local.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
     lib.mg_comm_unique_id.argtypes = [vp, C.c_size_t]
     lib.mg_comm_create_rank.argtypes = [vp, vp, C.c_size_t, i32, i32, C.POINTER(vp)]
@@ -353,6 +355,7 @@ def load_library():
     lib.mg_compare_rect_pairs_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp]
     lib.mg_compare_tri_results_sharded_host.argtypes = [vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
     lib.mg_compare_rect_results_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
+    lib.mg_compare_rect_topk_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_dscreen_create.argtypes = [vp, C.POINTER(MgParams), vp, i32, C.POINTER(vp)]
     lib.mg_dscreen_add_host.argtypes = [vp, vp, u64]
     lib.mg_dscreen_finish_host.argtypes = [vp, vp, vp, C.POINTER(u32), C.POINTER(u64)]
@@ -595,6 +598,12 @@ class LocalComm:
     def rect_results(self, dref, dqry, nq, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=1 << 16):
         return self._results(lambda o, c, cnt: self.lib.mg_compare_rect_results_sharded_host(
             self.h, dref, dqry, 0, nq, k, kmer_space, max_d, max_p, o, c, cnt), capacity)
+
+    def compare_rect_topk(self, dref, dqry, k, kmer_space, topk, max_d=-1.0, max_p=-1.0, q_begin=0, q_end=None, capacity=1 << 16):
+        """the `topk` nearest references of every query over the devices (mg_compare_rect_topk_sharded_host); q_end None: every query"""
+        q_end = (1 << 63) if q_end is None else q_end
+        return self._results(lambda o, c, cnt: self.lib.mg_compare_rect_topk_sharded_host(
+            self.h, dref, dqry, q_begin, q_end, k, kmer_space, max_d, max_p, topk, o, c, cnt), capacity)
 
 
 class RankComm:
@@ -950,6 +959,15 @@ class MashGpu:
         q_end = qry.rows if q_end is None else min(q_end, qry.rows)
         return self._filter(lambda o, c, n: self.lib.mg_compare_rect_results_host(
             self.ctx, ref.handle, qry.handle, q_begin, q_end, k, kmer_space, max_d, max_p, o, c, n), capacity, RESULT_DTYPE)
+
+    def compare_rect_topk(self, ref, qry, k, kmer_space, topk, max_d=-1.0, max_p=-1.0, q_begin=0, q_end=None, capacity=None):
+        """per query its `topk` nearest references among the pairs that pass the filters, chosen on the device: best first by the
+        exact fraction numer/denom, equal fractions by reference index, queries ascending (mg_compare_rect_topk_host)"""
+        q_end = qry.rows if q_end is None else min(q_end, qry.rows)
+        if capacity is None:
+            capacity = max(q_end - q_begin, 0) * max(min(int(topk), ref.rows), 0)
+        return self._filter(lambda o, c, n: self.lib.mg_compare_rect_topk_host(
+            self.ctx, ref.handle, qry.handle, q_begin, q_end, k, kmer_space, max_d, max_p, topk, o, c, n), capacity, RESULT_DTYPE)
 
     def finish_tri_dev(self, table, counts_ptr, row_begin, row_end, k, kmer_space, max_d, max_p, out_ptr):
         self._check(self.lib.mg_finish_tri_dev(self.ctx, table.handle, counts_ptr, row_begin, row_end, k, kmer_space,

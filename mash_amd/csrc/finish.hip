@@ -45,15 +45,6 @@ __device__ __forceinline__ void pair_rc(const FinishArgs &a, uint64_t idx, uint6
     }
 }
 
-__device__ __forceinline__ double lut_distance(const FinishArgs &a, uint32_t numer, uint32_t denom)
-{
-    if (numer == denom) return 0.0;                                       // CommandDistance.cpp:389-392
-    if (numer == 0) return 1.0;                                           // :393-396
-    const uint32_t st = denom <= a.s ? a.lut_start[denom] : 0xFFFFFFFFu;
-    if (st == 0xFFFFFFFFu) return __builtin_nan("");                      // not tabulated: the host patches it
-    return a.lut[(uint64_t)st + numer];
-}
-
 __device__ __forceinline__ bool passes_distance(const FinishArgs &a, uint32_t numer, uint32_t denom)
 {
     if (!a.min_numer) return true;

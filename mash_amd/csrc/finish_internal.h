@@ -41,6 +41,16 @@ struct FinishArgs {
     const uint2 *list_rc;          // list mode: counts[idx] belongs to pair {row, col} = list_rc[idx] (reference order); nullptr: flat order
 };
 
+// distance of a pair from the host-libm table (finish.hip, topk.hip)
+__device__ __forceinline__ double lut_distance(const FinishArgs &a, uint32_t numer, uint32_t denom)
+{
+    if (numer == denom) return 0.0;                                       // CommandDistance.cpp:389-392
+    if (numer == 0) return 1.0;                                           // :393-396
+    const uint32_t st = denom <= a.s ? a.lut_start[denom] : 0xFFFFFFFFu;
+    if (st == 0xFFFFFFFFu) return __builtin_nan("");                      // not tabulated: the host patches it
+    return a.lut[(uint64_t)st + numer];
+}
+
 uint64_t finish_segments(uint64_t pairs);
 uint64_t finish_mask_words(uint64_t pairs);
 hipError_t launch_finish_pairs(const FinishArgs &a, hipStream_t stream);

@@ -543,12 +543,12 @@ int mg_compare_rect_pairs_sharded_host(mg_comm *c, const mg_dtable *ref, const m
     });
 }
 
-// One device's survivors: call(out, capacity, count) into 2^16 records, once more with exactly the count reported if that was
-// too few.  v holds the list (nothing after an error).
+// One device's survivors: call(out, capacity, count) into `first` records (2^16 where the number is not known beforehand),
+// once more with exactly the count reported if that was too few.  v holds the list (nothing after an error).
 template <class Call>
-static int collect_results(std::vector<mg_result> &v, Call call)
+static int collect_results(std::vector<mg_result> &v, Call call, uint64_t first = 1u << 16)
 {
-    v.resize(1u << 16);
+    v.resize(std::max<uint64_t>(first, 1));
     uint64_t n = 0;
     int r = call(v.data(), (uint64_t)v.size(), &n);
     if (r == MG_ERR_NOMEM && n > v.size()) {
@@ -570,13 +570,15 @@ static int results_total(mg_comm *c, const std::vector<std::vector<mg_result>> &
 }
 
 // survivors of both filters: every GPU collects its block's list, the lists are joined in block (= reference) order
+// (per_row: a bound on the records of one row where the caller knows one -- the first call then always suffices)
 template <class Call>
 static int sharded_results(mg_comm *c, uint64_t rb, uint64_t re, bool triangle, uint64_t ncols, mg_result *out_host,
-                           uint64_t capacity, uint64_t *count_out, Call call, double row_weight = 0.0)
+                           uint64_t capacity, uint64_t *count_out, Call call, double row_weight = 0.0, uint64_t per_row = 0)
 {
     std::vector<std::vector<mg_result>> part(c->ctxs.size());
     int rc = sharded_blocks(c, rb, re, triangle, ncols, [&](int g, uint64_t lo, uint64_t hi, uint64_t) {
-        return collect_results(part[(size_t)g], [&](mg_result *o, uint64_t cap, uint64_t *n) { return call(g, lo, hi, o, cap, n); });
+        return collect_results(part[(size_t)g], [&](mg_result *o, uint64_t cap, uint64_t *n) { return call(g, lo, hi, o, cap, n); },
+                               per_row ? (hi - lo) * per_row : 1u << 16);
     }, row_weight);
     if (rc == MG_OK) rc = results_total(c, part, capacity, count_out);
     if (rc != MG_OK) return rc;
@@ -652,6 +654,66 @@ int mg_compare_rect_results_sharded_host(mg_comm *c, const mg_dtable *ref, const
         return mg_compare_rect_results_host(c->ctxs[(size_t)g], ref->t[(size_t)g], qry->t[(size_t)g], lo, hi, kmer_size, kmer_space,
                                             max_distance, max_p_value, o, cap, n);
     });
+}
+
+int mg_compare_rect_topk_sharded_host(mg_comm *c, const mg_dtable *ref, const mg_dtable *qry, uint64_t q_begin, uint64_t q_end,
+                                      int kmer_size, double kmer_space, double max_distance, double max_p_value, uint32_t k,
+                                      mg_result *out_host, uint64_t capacity, uint64_t *count_out)
+{
+    int rc = dtable_check(c, ref, "mg_compare_rect_topk_sharded_host", true);
+    if (rc == MG_OK) rc = dtable_check(c, qry, "mg_compare_rect_topk_sharded_host");
+    if (rc != MG_OK) return rc;
+    if (!count_out || (!out_host && capacity)) return comm_fail(c, MG_ERR_INVALID, "mg_compare_rect_topk_sharded_host: NULL argument");
+    *count_out = 0;
+    if (k == 0) return comm_fail(c, MG_ERR_INVALID, "mg_compare_rect_topk_sharded_host: k is 0");
+    if (k > MG_TOPK_MAX) return comm_fail(c, MG_ERR_UNSUPPORTED, "mg_compare_rect_topk_sharded_host: k exceeds MG_TOPK_MAX");
+    if (q_end > qry->t[0]->n) q_end = qry->t[0]->n;
+    if (q_begin >= q_end) return MG_OK;
+    if (rect_split_refs(c->ctxs[0], ref, q_end - q_begin)) {
+        // every device lists the top k of its reference block (query major, columns relative to the block); a query's answer is
+        // the first k of its blocks' lists merged by the order of the single-device call, on indices into the whole reference
+        const size_t G = c->ctxs.size();
+        std::vector<std::vector<mg_result>> part(G);
+        std::vector<uint64_t> lo_of(G, 0);
+        rc = per_device(c, [&](size_t g) {
+            const mg_table *blk = nullptr;
+            uint64_t hi = 0;
+            const int r = ref_block(c, ref, g, &blk, &lo_of[g], &hi);
+            if (r != MG_OK || lo_of[g] >= hi) return r;
+            return collect_results(part[g], [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                return mg_compare_rect_topk_host(c->ctxs[g], blk, qry->t[g], q_begin, q_end, kmer_size, kmer_space, max_distance, max_p_value, k,
+                                                 o, cap, n);
+            }, (q_end - q_begin) * std::min<uint64_t>(k, blk->n));                  // (the largest possible answer: one call)
+        });
+        if (rc != MG_OK) return rc;
+        std::vector<mg_result> merged, one;
+        std::vector<size_t> cur(G, 0);
+        for (uint64_t q = q_begin; q < q_end; q++) {
+            one.clear();
+            for (size_t g = 0; g < G; g++) {
+                std::vector<mg_result> &v = part[g];
+                while (cur[g] < v.size() && v[cur[g]].row == q) {
+                    mg_result r = v[cur[g]++];
+                    r.col += (uint32_t)lo_of[g];
+                    one.push_back(r);
+                }
+            }
+            std::sort(one.begin(), one.end(), [](const mg_result &a, const mg_result &b) {
+                const uint64_t l = (uint64_t)a.numer * (b.denom ? b.denom : 1u), r = (uint64_t)b.numer * (a.denom ? a.denom : 1u);
+                return l > r || (l == r && a.col < b.col);
+            });
+            merged.insert(merged.end(), one.begin(), one.begin() + (ptrdiff_t)std::min<size_t>(one.size(), k));
+        }
+        *count_out = merged.size();
+        if (merged.size() > capacity) return comm_fail(c, MG_ERR_NOMEM, "top-k: more records than `capacity` (see *count_out)");
+        if (!merged.empty()) memcpy(out_host, merged.data(), merged.size() * sizeof(mg_result));
+        return MG_OK;
+    }
+    return sharded_results(c, q_begin, q_end, false, ref->t[0]->n, out_host, capacity, count_out,
+                           [&](int g, uint64_t lo, uint64_t hi, mg_result *o, uint64_t cap, uint64_t *n) {
+        return mg_compare_rect_topk_host(c->ctxs[(size_t)g], ref->t[(size_t)g], qry->t[(size_t)g], lo, hi, kmer_size, kmer_space, max_distance,
+                                         max_p_value, k, o, cap, n);
+    }, 0.0, std::min<uint64_t>(k, ref->t[0]->n));
 }
 
 /* Sketching on every GPU of a local communicator (independent units, no collective; the

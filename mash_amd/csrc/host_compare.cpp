@@ -5,6 +5,7 @@
 namespace mg { void index_dump_clocks(); }
 #endif
 #include "sort_bits.h"
+#include "topk_internal.h"
 
 /* ------------------------------------------------------------------ comparing */
 
@@ -2217,3 +2218,163 @@ int mg_compare_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_tabl
     return compare_results(ctx, qry, ref, q_begin, q_end, false, kmer_size, kmer_space, max_distance, max_p_value, out_host, capacity, count_out);
 }
 
+
+/* ------------------------------------------------- the k nearest references per query (topk.hip) */
+
+static_assert(MG_TOPK_MAX == mg::TOPK_MAX, "MG_TOPK_MAX");
+
+// What one selection needs on the device: pass A's ballots when a filter is on (eligibility), the rows' lists as indices into
+// the counts, their lengths and offsets, the denominators they carry, the records.
+struct TopkBufs {
+    DevBuf<uint32_t> sel, row_n, seen, seg_count;
+    DevBuf<unsigned long long> row_off, total, masks, seg_off;
+    DevBuf<mg::FinishEdge> edges;
+    explicit TopkBufs(mg_ctx *c) : sel(c), row_n(c), seen(c), seg_count(c), row_off(c), total(c), masks(c), seg_off(c), edges(c) {}
+    bool alloc(uint64_t nrows, uint32_t k, uint32_t s, uint64_t pairs, bool filtered)
+    {
+        if (filtered && (masks.alloc(mg::finish_mask_words(pairs)) != hipSuccess || seg_count.alloc(mg::finish_segments(pairs)) != hipSuccess ||
+                         seg_off.alloc(mg::finish_segments(pairs)) != hipSuccess))
+            return false;
+        return sel.alloc(nrows * k) == hipSuccess && row_n.alloc(nrows) == hipSuccess && row_off.alloc(nrows) == hipSuccess &&
+               total.alloc(2) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess && edges.alloc(nrows * k) == hipSuccess;
+    }
+};
+
+// One selection over f's counts -- a block of the matrix (seg_base == nullptr) or the candidate lists (f.list_rc, seg_base / seg_cnt):
+// eligibility by finish_mark_kernel when a filter is on (f carries tables without any extra denominator row, as in
+// finish_survivors), the rows' best k, and only then -- the denominators of the selected are known -- the distance table and the
+// records.  *n_out: the records of these rows, always; they are written to out_host only when they fit `room`.
+static int topk_select_finish(mg_ctx *ctx, mg::FinishArgs f, const TopkBufs &b, const uint32_t *seg_base, const uint32_t *seg_cnt, uint32_t nrows,
+                              uint32_t k, bool filtered, int kmer_size, double max_d, uint64_t room, mg_result *out_host, uint64_t *n_out)
+{
+    *n_out = 0;
+    if (!nrows || !f.pairs) return MG_OK;
+    if (filtered) {
+        f.masks = b.masks;
+        f.seg_count = b.seg_count;
+        f.seg_off = b.seg_off;
+        f.denom_seen = b.seen;
+        HIP_TRY(ctx, mg::launch_finish_mark(f, b.total + 1, ctx->stream));
+    }
+    mg::TopkArgs a{};
+    a.counts = f.counts;
+    a.masks = filtered ? b.masks.p : nullptr;
+    a.seg_base = seg_base;
+    a.seg_cnt = seg_cnt;
+    a.ncols = (uint32_t)f.ncols;
+    a.nrows = nrows;
+    a.k = k;
+    a.sel = b.sel;
+    a.row_n = b.row_n;
+    a.denom_seen = b.seen;
+    a.s = f.s;
+    std::vector<uint32_t> seen((size_t)f.s + 1);
+    unsigned long long n = 0;
+    HIP_TRY(ctx, hipMemsetAsync(b.seen, 0, seen.size() * 4, ctx->stream));
+    HIP_TRY(ctx, mg::launch_topk_select(a, ctx->stream));
+    HIP_TRY(ctx, mg::launch_topk_scan(b.row_n, b.row_off, nrows, b.total, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&n, b.total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(seen.data(), b.seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_out = n;
+    if (n == 0 || n > room) return MG_OK;
+    FinishTables fb(ctx);
+    const int rc = build_finish_tables(ctx, f.s, kmer_size, max_d, seen, fb);
+    if (rc != MG_OK) return rc;
+    f.lut_start = fb.d_start;
+    f.lut = fb.d_lut;
+    HIP_TRY(ctx, mg::launch_topk_finish(f, a, b.row_off, b.edges, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, b.edges, n * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!fb.complete)                                         // a denominator beyond the table's budget left NaN distances
+        for (uint64_t i = 0; i < n; i++) {
+            mg_result &e = out_host[i];
+            if (e.distance != e.distance) e.distance = mg::mash_distance(e.numer, e.denom, kmer_size);
+        }
+    return MG_OK;
+}
+
+// queries [rb, re): few enough that rows * k records fit the device buffers
+static int topk_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, int kmer_size, double kmer_space,
+                      double max_d, double max_p, uint32_t k, uint64_t room, mg_result *out_host, uint64_t *n_out)
+{
+    *n_out = 0;
+    OutRange R;
+    int rc = out_range(ctx, rows, cols, rb, re, false, &R);
+    if (rc != MG_OK || !R.pairs) return rc;
+    const bool filtered = (max_d >= 0.0 && max_d < 1.0) || (max_p >= 0.0 && max_p < 1.0);
+    const uint32_t nrows = (uint32_t)(R.re - R.rb);
+    TopkBufs tb(ctx);
+    // ---- a filter is on: only pairs that share a hash can pass, and those are the inverted-index engine's candidates, a row's in
+    // column order (compare_results).  With the filters off a row is completed by its numer = 0 pairs in index order, and a
+    // candidate can itself have numer = 0 (a hash shared behind the first s union elements): it ties with the pairs that are
+    // no candidates and has to fall into index order among them, which only the full row gives -- those jobs take the matrix route.
+    if (filtered) {
+        CandLists L(ctx);
+        bool lists = false;
+        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return K <= 0xFFFFFFFFull - mg::TOPK_CHUNK && tb.alloc(nrows, k, R.s, K, true); });
+        if (rc != MG_OK || (lists && L.K == 0)) return rc;
+        if (lists) {
+            FinishTables fa(ctx);
+            if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
+            mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, false, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
+            f.list_rc = L.rc;
+            return topk_select_finish(ctx, f, tb, L.base, L.byrow, nrows, k, true, kmer_size, max_d, room, out_host, n_out);
+        }
+    }
+    // ---- the matrix in row blocks of counts (never as records): a workgroup per row streams its nref x 8 B once
+    uint64_t block_pairs = 1ull << 26;                       // 512 MiB of counts
+    if (const char *o = ctx_opt(ctx, "MASHGPU_TOPK_BLOCK_PAIRS")) block_pairs = std::max<uint64_t>(1, strtoull(o, nullptr, 10));
+    block_pairs = std::min<uint64_t>(block_pairs, 1ull << 31);              // (the lists hold 32-bit indices into a block)
+    uint64_t largest = 0, most_rows = 0;
+    const std::vector<RowBlock> blocks = row_blocks(R, block_pairs, &largest);
+    // (a row's positions and a block's indices are 32-bit, and the streaming loop steps past the row's end by up to one chunk)
+    if (largest > 0xFFFFFFFFull - mg::TOPK_CHUNK) return fail(ctx, MG_ERR_UNSUPPORTED, "top-k: more than 2^32 - 1025 references");
+    for (const RowBlock &b : blocks) most_rows = std::max(most_rows, b.r2 - b.r);
+    DevBuf<mg_counts> d_counts(ctx);
+    if (d_counts.alloc(largest) != hipSuccess || !tb.alloc(most_rows, k, R.s, largest, filtered))
+        return fail(ctx, MG_ERR_NOMEM, "top-k: device allocation failed");
+    FinishTables fa(ctx);
+    uint64_t total = 0;
+    for (const RowBlock &b : blocks) {
+        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, false, d_counts)) != MG_OK) return rc;
+        if (&b == &blocks.front() && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
+        uint64_t n = 0;
+        rc = topk_select_finish(ctx, finish_args(R.rows, R.cols, R.s, false, d_counts, b.pairs, b.r, fa, kmer_space, max_p), tb, nullptr, nullptr,
+                                (uint32_t)(b.r2 - b.r), k, filtered, kmer_size, max_d, total <= room ? room - total : 0, out_host + std::min(total, room), &n);
+        if (rc != MG_OK) return rc;
+        total += n;
+    }
+    *n_out = total;
+    return MG_OK;
+}
+
+int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin, uint64_t q_end, int kmer_size,
+                              double kmer_space, double max_distance, double max_p_value, uint32_t k, mg_result *out_host, uint64_t capacity,
+                              uint64_t *count_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!ref || !qry || !count_out || (!out_host && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_topk_host: NULL argument");
+    *count_out = 0;
+    if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
+        return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_topk_host: the tables carry no lengths");
+    if (k == 0) return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_topk_host: k is 0");
+    if (k > MG_TOPK_MAX) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_compare_rect_topk_host: k exceeds MG_TOPK_MAX");
+    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    q_end = std::min(q_end, qry->n);
+    if (q_begin >= q_end || ref->n == 0) return MG_OK;
+    k = (uint32_t)std::min<uint64_t>(k, ref->n);
+    const uint64_t step = std::max<uint64_t>(1, (1ull << 24) / k);          // at most 2^24 records (512 MiB) on the device at a time
+    uint64_t total = 0;
+    for (uint64_t q0 = q_begin; q0 < q_end; q0 += step) {
+        uint64_t n = 0;
+        const int rc = topk_range(ctx, qry, ref, q0, std::min(q_end, q0 + step), kmer_size, kmer_space, max_distance, max_p_value, k,
+                                  total <= capacity ? capacity - total : 0, out_host + std::min(total, capacity), &n);
+        if (rc != MG_OK) return rc;
+        total += n;
+    }
+    *count_out = total;
+    if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "top-k: more records than `capacity` (see *count_out)");
+    return MG_OK;
+}

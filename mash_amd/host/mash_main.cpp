@@ -1136,14 +1136,22 @@ int cmd_dist(int argc, const char **argv)
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "1.0", 0., 1.);
     c.add("comment", Opt::Boolean, "C");
+    c.add("nearest", Opt::Integer, "N", "", 1, (float)MG_TOPK_MAX);          // (not in the reference: its user pipes through sort | head)
     c.use_sketch_options();
     if (c.parse(argc, argv)) return 1;
     if (c.args.size() < 2 || c.o("help").active) {
         cout << "\nUsage:\n\n  mash dist [options] <reference> <query> [<query>] ...\n\n"
                 "Output fields: [reference-ID, query-ID, distance, p-value, shared-hashes].\n"
-                "Options: -l -t -v <max p> -d <max dist> -C and the sketch options of `mash sketch`.\n\n";
+                "Options: -l -t -v <max p> -d <max dist> -C -N <int> and the sketch options of `mash sketch`.\n"
+                "  -N <int>  Per query at most <int> lines (1-" << MG_TOPK_MAX << "): its nearest references among those that pass -d and -v,\n"
+                "            best first by shared-hashes as an exact fraction, equal fractions in reference order.\n\n";
         return 0;
     }
+    if (c.o("nearest").active && c.o("table").active) {
+        cerr << "ERROR: The option -" << c.o("nearest").id << " cannot be used with -" << c.o("table").id << "." << endl;
+        return 1;
+    }
+    const uint32_t nearest = c.o("nearest").active ? (uint32_t)c.o("nearest").num : 0;
     const bool table = c.o("table").active, comment = c.o("comment").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
     Params p;
@@ -1201,6 +1209,55 @@ int cmd_dist(int argc, const char **argv)
     vector<mg_counts> counts;
     vector<mg_pair> pairs;
     FastOut out;
+    if (nearest) {
+        // -N: per query its nearest references, ranked and cut on the device (mg_compare_rect_topk_sharded_host): N records per
+        // query cross PCIe.  MASH_AMD_HOST_FINISH=1: the matrix of counts, the host tail, and the same selection here.
+        vector<mg_result> res;
+        const uint64_t keep = std::min<uint64_t>(nearest, nref);
+        const uint64_t nblock = host_finish_wanted() ? qblock : std::max<uint64_t>(1, (1ull << 22) / keep);
+        for (uint64_t q0 = 0; q0 < nq; q0 += nblock) {
+            const uint64_t q1 = std::min(nq, q0 + nblock);
+            if (!host_finish_wanted()) {
+                if (res.size() < (q1 - q0) * keep) res.resize((q1 - q0) * keep);        // the largest possible answer: one call
+                if (!fetch_results(gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                        return mg_compare_rect_topk_sharded_host(gpu.comm, dr, dq, q0, q1, ref.p.kmer, kspace, d_max, p_max, nearest, o, cap, n); }))
+                    return 1;
+            } else {
+                counts.resize((q1 - q0) * nref);
+                if (mg_compare_rect_sharded_host(gpu.comm, dr, dq, q0, q1, counts.data()) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; return 1; }
+                pairs.resize(counts.size());
+                mg_finish_rect_host(counts.data(), len_ref.data(), nref, len_qry.data() + q0, q1 - q0, ref.p.kmer, kspace, d_max, p_max, pairs.data());
+                res.clear();
+                vector<uint32_t> order;
+                for (uint64_t q = q0; q < q1; q++) {
+                    const mg_pair *row = pairs.data() + (q - q0) * nref;
+                    order.clear();
+                    for (uint64_t r = 0; r < nref; r++)
+                        if (row[r].pass) order.push_back((uint32_t)r);
+                    const size_t take = std::min<size_t>(order.size(), keep);
+                    std::partial_sort(order.begin(), order.begin() + (ptrdiff_t)take, order.end(), [&](uint32_t x, uint32_t y) {
+                        const mg_pair &a = row[x], &b = row[y];           // the order of mg_compare_rect_topk_host
+                        const uint64_t l = (uint64_t)a.numer * (b.denom ? b.denom : 1u), r = (uint64_t)b.numer * (a.denom ? a.denom : 1u);
+                        return l > r || (l == r && x < y);
+                    });
+                    for (size_t i = 0; i < take; i++) {
+                        const mg_pair &a = row[order[i]];
+                        res.push_back(mg_result{(uint32_t)q, order[i], a.numer, a.denom, a.distance, a.p_value});
+                    }
+                }
+            }
+            emit_rows(out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
+                const mg_result &e = res[x];
+                mg_pair pr;
+                pr.numer = e.numer; pr.denom = e.denom; pr.distance = e.distance; pr.p_value = e.p_value; pr.pass = 1;
+                print_pair_line(o, ref.refs[e.col], qry.refs[e.row], comment, pr);
+            });
+        }
+        mg_dtable_free(dr);
+        mg_dtable_free(dq);
+        if (w.count > 0 && !p.reads) warn_kmer_size(ref, w);
+        return 0;
+    }
     if (!table && edge_filter_wanted(d_max, p_max)) {
         vector<mg_edge> edges;
         vector<mg_result> res;
