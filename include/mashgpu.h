@@ -381,6 +381,23 @@ int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *
                               uint64_t q_end, int kmer_size, double kmer_space, double max_distance,
                               double max_p_value, uint32_t k, mg_result *out_host, uint64_t capacity,
                               uint64_t *count_out);
+/* Single-linkage clusters of the thresholded all-vs-all, found ON THE DEVICE (cluster.hip) -- `mash cluster`.  The reference
+ * has no such command (its user feeds the lines of `mash triangle -E` to a union-find of their own); the definition stands on
+ * those lines:
+ *   edge       : exactly a pair {row, col} that mg_compare_tri_results_host(ctx, t, 0, rows, kmer_size, kmer_space,
+ *                max_distance, max_p_value, ...) returns -- the filters of CommandDistance.cpp:409-422 under the same conventions;
+ *   cluster    : a connected component of that graph;
+ *   label[i]   : the smallest row index in i's cluster (a row with no edge is its own cluster);
+ *   n_edges    : the number of edges;  n_clusters : the number of i with label[i] == i.
+ * Nothing here depends on execution order.  The whole table only.  Both filters disabled (each < 0 or >= 1): MG_ERR_INVALID,
+ * every pair would be an edge; everything else fails as mg_compare_tri_results_host does.  A table of 0 or 1 rows: MG_OK.
+ * No distance is computed, no record written, and only rows x 4 bytes cross PCIe; _dev leaves the labels on the device. */
+int mg_cluster_tri_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                        double max_p_value, uint32_t *label_out_host /* [rows] */, uint64_t *n_clusters_out,
+                        uint64_t *n_edges_out);
+int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                       double max_p_value, uint32_t *label_out_dev /* [rows] */, uint64_t *n_clusters_out,
+                       uint64_t *n_edges_out);
 /* Scalar helpers (same arithmetic as the bulk calls). */
 double mg_distance(uint32_t numer, uint32_t denom, int kmer_size);
 double mg_p_value(uint64_t x, uint64_t len_ref, uint64_t len_qry, double kmer_space,

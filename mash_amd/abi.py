@@ -32,6 +32,7 @@ EXPORTS = [
     "mg_finish_tri_host", "mg_finish_rect_host", "mg_distance", "mg_p_value",
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host",
+    "mg_cluster_tri_host", "mg_cluster_tri_dev",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
@@ -355,6 +356,8 @@ def load_library():
     lib.mg_compare_rect_pairs_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp]
     lib.mg_compare_tri_results_sharded_host.argtypes = [vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
     lib.mg_compare_rect_results_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
+    lib.mg_cluster_tri_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_tri_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_compare_rect_topk_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_dscreen_create.argtypes = [vp, C.POINTER(MgParams), vp, i32, C.POINTER(vp)]
     lib.mg_dscreen_add_host.argtypes = [vp, vp, u64]
@@ -968,6 +971,20 @@ class MashGpu:
             capacity = max(q_end - q_begin, 0) * max(min(int(topk), ref.rows), 0)
         return self._filter(lambda o, c, n: self.lib.mg_compare_rect_topk_host(
             self.ctx, ref.handle, qry.handle, q_begin, q_end, k, kmer_space, max_d, max_p, topk, o, c, n), capacity, RESULT_DTYPE)
+
+    def cluster_tri_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0):
+        """single-linkage clusters of the pairs compare_tri_results returns for the whole table, found on the device: (label u32[rows]
+        = smallest row of each row's cluster, clusters, edges) (mg_cluster_tri_host)"""
+        label = np.zeros(table.rows, dtype=np.uint32)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_host(self.ctx, table.handle, k, kmer_space, max_d, max_p, label.ctypes.data, C.byref(nc), C.byref(ne)))
+        return label, int(nc.value), int(ne.value)
+
+    def cluster_tri_dev(self, table, k, kmer_space, label_ptr, max_d=-1.0, max_p=-1.0):
+        """cluster_tri_host with the labels left on the device at label_ptr (u32[rows]): (clusters, edges)"""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, label_ptr, C.byref(nc), C.byref(ne)))
+        return int(nc.value), int(ne.value)
 
     def finish_tri_dev(self, table, counts_ptr, row_begin, row_end, k, kmer_space, max_d, max_p, out_ptr):
         self._check(self.lib.mg_finish_tri_dev(self.ctx, table.handle, counts_ptr, row_begin, row_end, k, kmer_space,

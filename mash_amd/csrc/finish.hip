@@ -24,27 +24,6 @@ constexpr int FN_NT = 256;
 constexpr int FN_PER = 16;
 constexpr int FN_SEG = FN_NT * FN_PER;       // pairs per workgroup of the mark / write passes
 
-__device__ __forceinline__ void pair_rc(const FinishArgs &a, uint64_t idx, uint64_t &row, uint64_t &col)
-{
-    if (a.list_rc) {                                       // a list of pairs (the sparse engine's candidates), not a block of the matrix
-        const uint2 rc = a.list_rc[idx];
-        row = rc.x;
-        col = rc.y;
-        return;
-    }
-    if (a.triangle) {
-        const uint64_t f = a.first_row;
-        const uint64_t g = (f ? f * (f - 1) / 2 : 0) + idx;               // index in the whole triangle
-        row = (uint64_t)((1.0 + sqrt(1.0 + 8.0 * (double)g)) * 0.5);
-        while (row * (row - 1) / 2 > g) row--;
-        while ((row + 1) * row / 2 <= g) row++;
-        col = g - row * (row - 1) / 2;
-    } else {
-        row = a.first_row + idx / a.ncols;
-        col = idx % a.ncols;
-    }
-}
-
 __device__ __forceinline__ bool passes_distance(const FinishArgs &a, uint32_t numer, uint32_t denom)
 {
     if (!a.min_numer) return true;

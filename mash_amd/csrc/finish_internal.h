@@ -1,6 +1,11 @@
 // finish_internal.h — launch interface between host_compare.cpp and finish.hip.
 #pragma once
+#ifdef MG_HIP_EMU                    // tools/hipemu: cluster.hip on host fibers (tests/test_cluster_emu.py)
+#include <math.h>
+#include "hipemu.h"
+#else
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 namespace mg {
@@ -49,6 +54,28 @@ __device__ __forceinline__ double lut_distance(const FinishArgs &a, uint32_t num
     const uint32_t st = denom <= a.s ? a.lut_start[denom] : 0xFFFFFFFFu;
     if (st == 0xFFFFFFFFu) return __builtin_nan("");                      // not tabulated: the host patches it
     return a.lut[(uint64_t)st + numer];
+}
+
+// {row, col} of pair idx of a finish job (finish.hip, cluster.hip)
+__device__ __forceinline__ void pair_rc(const FinishArgs &a, uint64_t idx, uint64_t &row, uint64_t &col)
+{
+    if (a.list_rc) {                                       // a list of pairs (the sparse engine's candidates), not a block of the matrix
+        const uint2 rc = a.list_rc[idx];
+        row = rc.x;
+        col = rc.y;
+        return;
+    }
+    if (a.triangle) {
+        const uint64_t f = a.first_row;
+        const uint64_t g = (f ? f * (f - 1) / 2 : 0) + idx;               // index in the whole triangle
+        row = (uint64_t)((1.0 + sqrt(1.0 + 8.0 * (double)g)) * 0.5);
+        while (row * (row - 1) / 2 > g) row--;
+        while ((row + 1) * row / 2 <= g) row++;
+        col = g - row * (row - 1) / 2;
+    } else {
+        row = a.first_row + idx / a.ncols;
+        col = idx % a.ncols;
+    }
 }
 
 uint64_t finish_segments(uint64_t pairs);

@@ -2219,6 +2219,136 @@ int mg_compare_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_tabl
 }
 
 
+/* ------------------------------------------------- single-linkage clusters of the thresholded triangle (cluster.hip) */
+
+// What one mark + union needs on the device for up to `pairs` entries: pass A's ballots and segments, the denominators it flags
+struct ClusterBufs {
+    DevBuf<unsigned long long> masks, seg_off;
+    DevBuf<uint32_t> seg_count, seen;
+    explicit ClusterBufs(mg_ctx *owner) : masks(owner), seg_off(owner), seg_count(owner), seen(owner) {}
+    bool alloc(uint64_t pairs, uint32_t s)
+    {
+        return masks.alloc(mg::finish_mask_words(pairs)) == hipSuccess && seg_count.alloc(mg::finish_segments(pairs)) == hipSuccess &&
+               seg_off.alloc(mg::finish_segments(pairs)) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess;
+    }
+};
+
+// finish_survivors' sibling: pass A over f's counts -- one matrix block, or the candidate list (f.list_rc) -- and the union of
+// every pair it marks.  No pass B, no distance table, no record, no wait: pass A's count goes to *n_dev (device).
+static int cluster_survivors(mg_ctx *ctx, mg::FinishArgs f, const ClusterBufs &b, uint32_t *parent, uint32_t n, unsigned long long *n_dev)
+{
+    f.masks = b.masks;
+    f.seg_count = b.seg_count;
+    f.seg_off = b.seg_off;
+    f.denom_seen = b.seen;
+    HIP_TRY(ctx, mg::launch_finish_mark(f, n_dev, ctx->stream));
+    HIP_TRY(ctx, mg::launch_cluster_union(f, parent, n, ctx->stream));
+    return MG_OK;
+}
+
+// The whole triangle of t: compare_results' two routes, with cluster_survivors in finish_survivors' place, then one label launch
+static int cluster_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_d, double max_p, uint32_t *label_out,
+                       bool label_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    *n_clusters_out = 0;
+    *n_edges_out = 0;
+    OutRange R;
+    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
+    if (rc != MG_OK || R.empty()) return rc;
+    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
+    const uint32_t n = (uint32_t)t->n;
+    DevBuf<uint32_t> parent(ctx), label(ctx);
+    DevBuf<unsigned long long> d_n(ctx);                      // [0]: the clusters, [1 + b]: pass A's count of block b
+    HIP_TRY(ctx, parent.alloc(n));
+    if (!label_on_device) HIP_TRY(ctx, label.alloc(n));
+    uint32_t *d_label = label_on_device ? label_out : label.p;
+    HIP_TRY(ctx, mg::launch_cluster_init(parent, n, ctx->stream));
+    uint64_t nblocks = 0;
+    // finish: the labels, the roots' number and pass A's counts, behind every union queued so far
+    auto finish = [&]() -> int {
+        std::vector<unsigned long long> h(1 + nblocks);
+        HIP_TRY(ctx, mg::launch_cluster_label(parent, n, d_label, d_n, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_n, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (!label_on_device) HIP_TRY(ctx, hipMemcpyAsync(label_out, d_label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *n_clusters_out = h[0];
+        for (uint64_t b = 0; b < nblocks; b++) *n_edges_out += h[1 + b];
+        return MG_OK;
+    };
+    if (!R.pairs) {                                           // (one row)
+        HIP_TRY(ctx, d_n.alloc(1));
+        return finish();
+    }
+    {   // ---- the inverted-index engine's candidates as one list (compare_results): one mark, one union
+        CandLists L(ctx);
+        ClusterBufs cb(ctx);
+        bool lists = false;
+        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return cb.alloc(K, R.s); });
+        if (rc != MG_OK) return rc;
+        if (lists) {
+            HIP_TRY(ctx, d_n.alloc(2));
+            if (L.K) {
+                FinishTables fa(ctx);
+                if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
+                mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, true, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
+                f.list_rc = L.rc;
+                HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+                if ((rc = cluster_survivors(ctx, f, cb, parent, n, d_n + 1)) != MG_OK) return rc;
+                nblocks = 1;
+                return finish();                              // (fa and the lists are released behind finish's wait)
+            }
+            return finish();
+        }
+    }
+    // ---- the matrix in row blocks: a mark and a union per block, `parent` persistent across them
+    uint64_t block_pairs = 1ull << 30;
+    if (const char *o = ctx_opt(ctx, "MASHGPU_CLUSTER_BLOCK_PAIRS")) block_pairs = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
+    uint64_t largest = 0;
+    const std::vector<RowBlock> blocks = row_blocks(R, std::min<uint64_t>(block_pairs, 1ull << 30), &largest);
+    DevBuf<mg_counts> d_counts(ctx);
+    ClusterBufs cb(ctx);
+    if (d_counts.alloc(largest) != hipSuccess || !cb.alloc(largest, R.s) || d_n.alloc(1 + blocks.size()) != hipSuccess)
+        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+    HIP_TRY(ctx, hipMemsetAsync(d_n, 0, (1 + blocks.size()) * 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+    FinishTables fa(ctx);
+    for (const RowBlock &b : blocks) {
+        nblocks++;
+        if (!b.pairs) continue;                               // (row 0)
+        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, true, d_counts)) != MG_OK) return rc;
+        if (!fa.d_start.p && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;  // (once: behind the first compare)
+        rc = cluster_survivors(ctx, finish_args(R.rows, R.cols, R.s, true, d_counts, b.pairs, b.r, fa, kmer_space, max_p), cb, parent, n, d_n + nblocks);
+        if (rc != MG_OK) return rc;
+    }
+    return finish();
+}
+
+static int cluster_entry(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                         uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out, const char *who)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!t || !n_clusters_out || !n_edges_out || (!label_out && t->n)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (!t->lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
+    if (!((max_distance >= 0.0 && max_distance < 1.0) || (max_p_value >= 0.0 && max_p_value < 1.0)))
+        return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
+    return cluster_tri(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out, label_on_device, n_clusters_out, n_edges_out);
+}
+
+int mg_cluster_tri_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                        uint32_t *label_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out_host, false, n_clusters_out, n_edges_out, "mg_cluster_tri_host");
+}
+
+int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                       uint32_t *label_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out_dev, true, n_clusters_out, n_edges_out, "mg_cluster_tri_dev");
+}
+
+
 /* ------------------------------------------------- the k nearest references per query (topk.hip) */
 
 static_assert(MG_TOPK_MAX == mg::TOPK_MAX, "MG_TOPK_MAX");

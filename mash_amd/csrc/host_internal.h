@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/mashgpu.h"
+#include "cluster_internal.h"
 #include "compare_internal.h"
 #include "finish_internal.h"
 #include "pvalue.h"

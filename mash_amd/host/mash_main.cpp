@@ -1,4 +1,4 @@
-// mash_main.cpp — `mash sketch | dist | triangle | info | paste | screen | taxscreen | bounds` on the MI355X hot path.
+// mash_main.cpp — `mash sketch | dist | triangle | cluster | info | paste | screen | taxscreen | bounds` on the MI355X hot path.
 //
 // Host C++ above the C ABI (include/mashgpu.h).  Option letters, defaults, file naming,
 // stdout/stderr text and output order follow the reference commands
@@ -1626,6 +1626,100 @@ int cmd_triangle(int argc, const char **argv)
     return 0;
 }
 
+// `mash cluster`: single-linkage clusters of the pairs `mash triangle -E -d -v` would print (the reference has no such command;
+// include/mashgpu.h: mg_cluster_tri_host).  One line per sketch in input order: cluster number (from 1, in order of the
+// clusters' first members), cluster size, name.  The clusters are found on the device and one label per sketch comes back;
+// MASH_AMD_HOST_FINISH=1 takes cmd_triangle's host edge route and a union-find here.
+int cmd_cluster(int argc, const char **argv)
+{
+    Cmd c;
+    c.name = "cluster";
+    c.add("help", Opt::Boolean, "h");
+    c.add("list", Opt::Boolean, "l");
+    c.add("comment", Opt::Boolean, "C");
+    c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
+    c.add("distance", Opt::Number, "d", "0.05", 0., 1.);
+    c.use_sketch_options();
+    if (c.parse(argc, argv)) return 1;
+    if (c.args.empty() || c.o("help").active) {
+        cout << "\nUsage:\n\n  mash cluster [options] <seq1> [<seq2>] ...\n\n"
+                "Single-linkage clusters of the pairs that `mash triangle -E` prints under the same -d and -v.\n"
+                "Output fields, one line per sketch in input order: [cluster-number, cluster-size, ID]; clusters are\n"
+                "numbered from 1 in order of their first member, which is the cluster's representative.\n"
+                "Options: -l -C and the sketch options of `mash sketch`.\n"
+                "  -d <num>  Maximum distance of an edge (0-1) [0.05]\n"
+                "  -v <num>  Maximum p-value of an edge (0-1) [1.0]\n\n";
+        return 0;
+    }
+    const bool comment = c.o("comment").active;
+    const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
+    if (d_max >= 1.0 && p_max >= 1.0) {
+        cerr << "ERROR: With -" << c.o("distance").id << " 1 and -" << c.o("pvalue").id << " 1 every pair is an edge; give a smaller maximum." << endl;
+        return 1;
+    }
+    Params p;
+    if (sketch_parameter_setup(p, c)) return 1;
+    if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // as `mash triangle` (CommandTriangle.cpp:74-77)
+    vector<string> files;
+    for (const string &a : c.args) { if (c.o("list").active) split_file(a, files); else files.push_back(a); }
+    Gpu gpu;
+    SketchSet set;
+    init_from_files(gpu, set, files, p, 1);
+    const KmerWarning w = scan_kmer_warning(set);
+    const uint64_t n = set.refs.size();
+    if (n == 0) return 0;
+    vector<uint64_t> lengths;
+    mg_dtable *dt = upload_all(gpu, set, set.p.sketch_size, &lengths);
+    mg_table *t = mg_dtable_local(dt, 0);                        // (several devices selected: the first one's replica)
+    const double kspace = set.kmer_space();
+    StageClock clk;
+    vector<uint32_t> lab(n);
+    if (!host_finish_wanted()) {
+        uint64_t n_clusters = 0, n_edges = 0;
+        if (mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges) != MG_OK) {
+            cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl;
+            return 1;
+        }
+        clk.lap("compare+mark+union+label+copy");
+    } else {
+        for (uint64_t i = 0; i < n; i++) lab[i] = (uint32_t)i;
+        auto find = [&](uint32_t x) { while (lab[x] != x) { lab[x] = lab[lab[x]]; x = lab[x]; } return x; };
+        vector<mg_edge> edges;
+        for (uint64_t r0 = 1; r0 < n;) {
+            uint64_t r1 = r0, npairs = 0;
+            while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 31))) { npairs += r1; r1++; }
+            if (!fetch_edges(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                    return mg_compare_tri_filter_host(gpu.ctx, t, r0, r1, set.p.kmer, d_max, o, cap, cnt); }))
+                return 1;
+            for (const mg_edge &e : edges) {
+                mg_pair pr;
+                if (!finish_edge(e, lengths[e.row], lengths[e.col], set.p.kmer, kspace, p_max, pr)) continue;
+                const uint32_t a = find(e.row), b = find(e.col);
+                if (a != b) lab[std::max(a, b)] = std::min(a, b);
+            }
+            r0 = r1;
+        }
+        for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
+        clk.lap("compare+filter+copy+union");
+    }
+    // label = the cluster's first member: numbers in order of first appearance are numbers by ascending label
+    vector<uint32_t> number(n, 0), size(n, 0);
+    uint32_t next = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (lab[i] == i) number[i] = ++next;
+        size[lab[i]]++;
+    }
+    FastOut out;
+    for (uint64_t i = 0; i < n; i++) {
+        out << number[lab[i]] << '\t' << size[lab[i]] << '\t' << (comment ? set.refs[i].comment : set.refs[i].name);
+        out.eol();
+    }
+    clk.lap("format+write");
+    mg_dtable_free(dt);
+    if (w.count > 0 && !p.reads) warn_kmer_size(set, w);
+    return 0;
+}
+
 void print_columns(const vector<vector<string>> &cols, int indent, int spacing, const char *missing)
 {
     vector<size_t> width(cols.size(), 0);
@@ -2162,7 +2256,8 @@ int main(int argc, const char **argv)
     const string usage =
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
         "  dist      Estimate the distance of query sequences to references.\n"
-        "  triangle  Estimate a lower-triangular distance matrix.\n  info      Display information about sketch files.\n"
+        "  triangle  Estimate a lower-triangular distance matrix.\n"
+        "  cluster   Group sequences into single-linkage clusters by distance.\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"
@@ -2180,6 +2275,7 @@ int main(int argc, const char **argv)
     if (cmd == "sketch") rc = cmd_sketch(argc - 2, argv + 2);
     else if (cmd == "dist") rc = cmd_dist(argc - 2, argv + 2);
     else if (cmd == "triangle") rc = cmd_triangle(argc - 2, argv + 2);
+    else if (cmd == "cluster") rc = cmd_cluster(argc - 2, argv + 2);
     else if (cmd == "info") rc = cmd_info(argc - 2, argv + 2);
     else if (cmd == "paste") rc = cmd_paste(argc - 2, argv + 2);
     else if (cmd == "screen") rc = cmd_screen(argc - 2, argv + 2);

@@ -323,3 +323,20 @@ static inline uint32_t atomicMax(uint32_t *p, uint32_t v)
     while (o < v && !__atomic_compare_exchange_n(p, &o, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
     return o;
 }
+static inline uint32_t atomicMin(uint32_t *p, uint32_t v)
+{
+    uint32_t o = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (o > v && !__atomic_compare_exchange_n(p, &o, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return o;
+}
+static inline uint32_t atomicCAS(uint32_t *p, uint32_t expected, uint32_t v)
+{
+    __atomic_compare_exchange_n(p, &expected, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return expected;                                        // (the value found, as on the device)
+}
+// scoped atomic loads and stores: every scope is the process here
+#ifndef __HIP_MEMORY_SCOPE_AGENT
+#define __HIP_MEMORY_SCOPE_AGENT 4
+#endif
+#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
+#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
