@@ -398,6 +398,32 @@ int mg_cluster_tri_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double km
 int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
                        double max_p_value, uint32_t *label_out_dev /* [rows] */, uint64_t *n_clusters_out,
                        uint64_t *n_edges_out);
+/* Greedy representative clusters of the same thresholded all-vs-all, found ON THE DEVICE (cluster_greedy.hip) -- `mash cluster
+ * -R`.  The reference has no such command (its user pipes `mash triangle -E -d` into a script that walks the genomes in input
+ * order, as CD-HIT does); the definition stands on those lines:
+ *   edge            : exactly a pair {row, col} that mg_compare_tri_results_host(ctx, t, 0, rows, kmer_size, kmer_space,
+ *                     max_distance, max_p_value, ...) returns -- the edge of mg_cluster_tri_host;
+ *   representatives : walk the rows in index order; row i is a representative iff no representative j < i has an edge to i
+ *                     (the lexicographically first maximal independent set of the threshold graph: it is unique);
+ *   rep[i]          : i for a representative, else the smallest representative j < i with an edge {i, j} ("joins the first
+ *                     representative within the threshold"); a representative with a larger index never takes a member;
+ *   n_clusters      : the number of i with rep[i] == i;   n_edges : the number of edges, as mg_cluster_tri_host reports it.
+ * So no two representatives are within the threshold of each other and every other row is within it of its representative.
+ * Nothing here depends on execution order, route or blocking.  The whole table only, at most 2^31 - 1 rows.  Both filters
+ * disabled (each < 0 or >= 1): MG_ERR_INVALID; everything else fails as mg_compare_tri_results_host does.  A table of 0 or 1
+ * rows: MG_OK.  The edges are kept on the device as 8 bytes each while the call runs (the list grows on demand; the context
+ * option MASHGPU_GREEDY_EDGE_CAP sets its first capacity in edges, a test knob); if they do not fit the device beside the table
+ * the call returns MG_ERR_NOMEM, it never drops an edge.  Only rows x 4 bytes cross PCIe; _dev leaves rep on the device.
+ * mg_cluster_greedy_stats: what the context's last such call needed -- rounds of its fixpoint (at most rows), batches of
+ * rounds the host waited for, times the edge list was regrown, its final capacity in edges (any pointer may be NULL). */
+int mg_cluster_tri_greedy_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                               double max_p_value, uint32_t *rep_out_host /* [rows] */, uint64_t *n_clusters_out,
+                               uint64_t *n_edges_out);
+int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                              double max_p_value, uint32_t *rep_out_dev /* [rows] */, uint64_t *n_clusters_out,
+                              uint64_t *n_edges_out);
+int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out,
+                            uint64_t *edge_capacity_out);
 /* Scalar helpers (same arithmetic as the bulk calls). */
 double mg_distance(uint32_t numer, uint32_t denom, int kmer_size);
 double mg_p_value(uint64_t x, uint64_t len_ref, uint64_t len_qry, double kmer_space,

@@ -32,7 +32,7 @@ EXPORTS = [
     "mg_finish_tri_host", "mg_finish_rect_host", "mg_distance", "mg_p_value",
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host",
-    "mg_cluster_tri_host", "mg_cluster_tri_dev",
+    "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
@@ -358,6 +358,9 @@ def load_library():
     lib.mg_compare_rect_results_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
     lib.mg_cluster_tri_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_tri_greedy_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_tri_greedy_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_greedy_stats.argtypes = [vp, vp, vp, vp, vp]
     lib.mg_compare_rect_topk_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_dscreen_create.argtypes = [vp, C.POINTER(MgParams), vp, i32, C.POINTER(vp)]
     lib.mg_dscreen_add_host.argtypes = [vp, vp, u64]
@@ -985,6 +988,27 @@ class MashGpu:
         nc, ne = C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.mg_cluster_tri_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, label_ptr, C.byref(nc), C.byref(ne)))
         return int(nc.value), int(ne.value)
+
+    def cluster_tri_greedy_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0):
+        """greedy representative clusters of the pairs compare_tri_results returns for the whole table, found on the device: (rep
+        u32[rows] = the row itself for a representative, else the smallest representative it has an edge to; clusters, edges)
+        (mg_cluster_tri_greedy_host)"""
+        rep = np.zeros(table.rows, dtype=np.uint32)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_greedy_host(self.ctx, table.handle, k, kmer_space, max_d, max_p, rep.ctypes.data, C.byref(nc), C.byref(ne)))
+        return rep, int(nc.value), int(ne.value)
+
+    def cluster_tri_greedy_dev(self, table, k, kmer_space, rep_ptr, max_d=-1.0, max_p=-1.0):
+        """cluster_tri_greedy_host with rep left on the device at rep_ptr (u32[rows]): (clusters, edges)"""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_greedy_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, rep_ptr, C.byref(nc), C.byref(ne)))
+        return int(nc.value), int(ne.value)
+
+    def cluster_greedy_stats(self):
+        """what this context's last cluster_tri_greedy_* call needed: {rounds, batches, regrows, edge_capacity} (mg_cluster_greedy_stats)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._check(self.lib.mg_cluster_greedy_stats(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("rounds", "batches", "regrows", "edge_capacity"), (int(x.value) for x in v)))
 
     def finish_tri_dev(self, table, counts_ptr, row_begin, row_end, k, kmer_space, max_d, max_p, out_ptr):
         self._check(self.lib.mg_finish_tri_dev(self.ctx, table.handle, counts_ptr, row_begin, row_end, k, kmer_space,

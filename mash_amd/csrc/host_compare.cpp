@@ -2324,8 +2324,12 @@ static int cluster_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, double kme
     return finish();
 }
 
+static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_d, double max_p, uint32_t *rep_out,
+                              bool rep_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out);
+
 static int cluster_entry(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                         uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out, const char *who)
+                         uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out, const char *who,
+                         bool greedy = false)
 {
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -2333,7 +2337,8 @@ static int cluster_entry(mg_ctx *ctx, const mg_table *t, int kmer_size, double k
     if (!t->lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
     if (!((max_distance >= 0.0 && max_distance < 1.0) || (max_p_value >= 0.0 && max_p_value < 1.0)))
         return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
-    return cluster_tri(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out, label_on_device, n_clusters_out, n_edges_out);
+    return (greedy ? cluster_greedy_tri : cluster_tri)(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out, label_on_device,
+                                                       n_clusters_out, n_edges_out);
 }
 
 int mg_cluster_tri_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
@@ -2346,6 +2351,181 @@ int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kme
                        uint32_t *label_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
 {
     return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out_dev, true, n_clusters_out, n_edges_out, "mg_cluster_tri_dev");
+}
+
+
+/* ------------------------------------------------- greedy representative clusters of the thresholded triangle (cluster_greedy.hip) */
+
+// The edge list of one call: grown on demand, the pairs of every block appended behind those of the blocks before it
+struct GreedyEdges {
+    mg_ctx *ctx;
+    DevBuf<uint2> buf;
+    DevBuf<unsigned long long> ctl;                           // [0] cursor, [1] pass A's count of the block, [2] overflow flag (its low word)
+    uint64_t cap = 0, used = 0, n_edges = 0, regrows = 0;
+    explicit GreedyEdges(mg_ctx *c) : ctx(c), buf(c), ctl(c) {}
+    int init(uint64_t want)
+    {
+        cap = std::max<uint64_t>(want, 1);
+        if (buf.alloc(cap) != hipSuccess || ctl.alloc(3) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(cap * sizeof(uint2)) + " bytes)");
+        }
+        HIP_TRY(ctx, hipMemsetAsync(ctl, 0, 24, ctx->stream));
+        return MG_OK;
+    }
+    // cluster_survivors' sibling: pass A over f's counts, its marked pairs appended; waits for the block's figures and, if the
+    // list was too short for them, regrows it (the pairs of earlier blocks copied over) and appends the block again -- pass A's
+    // ballots are still there
+    int append(mg::FinishArgs f, const ClusterBufs &b, uint32_t n)
+    {
+        f.masks = b.masks;
+        f.seg_count = b.seg_count;
+        f.seg_off = b.seg_off;
+        f.denom_seen = b.seen;
+        unsigned long long h[3] = {0, 0, 0};
+        HIP_TRY(ctx, mg::launch_finish_mark(f, ctl + 1, ctx->stream));
+        for (int attempt = 0;; attempt++) {
+            HIP_TRY(ctx, mg::launch_greedy_append(f, n, buf, cap, ctl, reinterpret_cast<uint32_t *>(ctl + 2), ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(h, ctl, 24, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (h[0] <= cap && !h[2]) break;
+            if (attempt) return fail(ctx, MG_ERR_HIP, "cluster: the edge list overflowed after it was regrown");
+            const uint64_t want = std::max<uint64_t>(h[0], 2 * cap);
+            DevBuf<uint2> bigger(ctx);
+            if (bigger.alloc(want) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(want * sizeof(uint2)) + " bytes for " +
+                                                   std::to_string(h[0]) + " edges so far)");
+            }
+            if (used) HIP_TRY(ctx, hipMemcpyAsync(bigger, buf, used * sizeof(uint2), hipMemcpyDeviceToDevice, ctx->stream));
+            const unsigned long long back[3] = {used, h[1], 0};
+            HIP_TRY(ctx, hipMemcpyAsync(ctl, back, 24, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the old list goes back to the pool behind the copy)
+            std::swap(buf.p, bigger.p);
+            cap = want;
+            regrows++;
+        }
+        used = h[0];
+        n_edges += h[1];
+        return MG_OK;
+    }
+};
+
+// The whole triangle of t: cluster_tri's two routes with GreedyEdges::append in cluster_survivors' place, then the rounds in
+// batches (one wait per batch: the rows each of its rounds left open), then the assignment
+static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_d, double max_p, uint32_t *rep_out,
+                              bool rep_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    *n_clusters_out = 0;
+    *n_edges_out = 0;
+    ctx->greedy_rounds = ctx->greedy_batches = ctx->greedy_regrows = ctx->greedy_edge_cap = 0;
+    OutRange R;
+    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
+    if (rc != MG_OK || R.empty()) return rc;
+    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
+    const uint32_t n = (uint32_t)t->n;
+    uint64_t edge_cap = 1ull << 23;                           // 64 MB; the list doubles, or grows to what a block needs, when it is short
+    if (const char *o = ctx_opt(ctx, "MASHGPU_GREEDY_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
+    GreedyEdges E(ctx);
+    DevBuf<uint32_t> state(ctx), rep(ctx), left(ctx);
+    DevBuf<unsigned long long> d_n(ctx);
+    constexpr uint32_t kBatchMax = 256;
+    // finish: the fixpoint over the edges appended so far, the assignment, the copy
+    auto finish = [&]() -> int {
+        if (state.alloc(n) != hipSuccess || left.alloc(kBatchMax) != hipSuccess || d_n.alloc(1) != hipSuccess || (!rep_on_device && rep.alloc(n) != hipSuccess))
+            return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+        uint32_t *d_rep = rep_on_device ? rep_out : rep.p;
+        HIP_TRY(ctx, hipMemsetAsync(state, 0, (size_t)n * 4, ctx->stream));
+        std::vector<uint32_t> h(kBatchMax);
+        uint64_t rounds = 0, batches = 0;
+        for (uint32_t batch = 8;; batch = std::min(batch * 2, kBatchMax)) {
+            HIP_TRY(ctx, mg::launch_greedy_rounds(E.buf, E.used, state, n, left, batch, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(h.data(), left, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            batches++;
+            uint32_t r = 0;
+            while (r < batch && h[r]) r++;
+            rounds += std::min(r + 1, batch);
+            if (r < batch) break;
+            if (rounds > n) return fail(ctx, MG_ERR_HIP, "cluster: the rounds did not reach their fixpoint");      // (at most n are ever needed)
+        }
+        unsigned long long reps = 0;
+        HIP_TRY(ctx, mg::launch_greedy_assign(E.buf, E.used, state, n, d_rep, d_n, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&reps, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (!rep_on_device) HIP_TRY(ctx, hipMemcpyAsync(rep_out, d_rep, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        *n_clusters_out = reps;
+        *n_edges_out = E.n_edges;
+        ctx->greedy_rounds = rounds;
+        ctx->greedy_batches = batches;
+        ctx->greedy_regrows = E.regrows;
+        ctx->greedy_edge_cap = E.cap;
+        return MG_OK;
+    };
+    if (!R.pairs) return finish();                            // (one row)
+    {   // ---- the inverted-index engine's candidates as one list (compare_results): one mark, one append
+        CandLists L(ctx);
+        ClusterBufs cb(ctx);
+        bool lists = false;
+        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return cb.alloc(K, R.s); });
+        if (rc != MG_OK) return rc;
+        if (lists) {
+            if (L.K) {
+                FinishTables fa(ctx);
+                if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
+                mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, true, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
+                f.list_rc = L.rc;
+                if ((rc = E.init(std::min<uint64_t>(edge_cap, L.K))) != MG_OK) return rc;
+                HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+                if ((rc = E.append(f, cb, n)) != MG_OK) return rc;
+            }
+            return finish();
+        }
+    }
+    // ---- the matrix in row blocks: a mark and an append per block, the list persistent across them
+    uint64_t block_pairs = 1ull << 30;
+    if (const char *o = ctx_opt(ctx, "MASHGPU_CLUSTER_BLOCK_PAIRS")) block_pairs = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
+    uint64_t largest = 0;
+    const std::vector<RowBlock> blocks = row_blocks(R, std::min<uint64_t>(block_pairs, 1ull << 30), &largest);
+    DevBuf<mg_counts> d_counts(ctx);
+    ClusterBufs cb(ctx);
+    if (d_counts.alloc(largest) != hipSuccess || !cb.alloc(largest, R.s)) return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+    if ((rc = E.init(std::min<uint64_t>(edge_cap, R.pairs))) != MG_OK) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+    FinishTables fa(ctx);
+    for (const RowBlock &b : blocks) {
+        if (!b.pairs) continue;                               // (row 0)
+        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, true, d_counts)) != MG_OK) return rc;
+        if (!fa.d_start.p && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;  // (once: behind the first compare)
+        if ((rc = E.append(finish_args(R.rows, R.cols, R.s, true, d_counts, b.pairs, b.r, fa, kmer_space, max_p), cb, n)) != MG_OK) return rc;
+    }
+    return finish();
+}
+
+int mg_cluster_tri_greedy_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                               uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, rep_out_host, false, n_clusters_out, n_edges_out,
+                         "mg_cluster_tri_greedy_host", true);
+}
+
+int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                              uint32_t *rep_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, rep_out_dev, true, n_clusters_out, n_edges_out,
+                         "mg_cluster_tri_greedy_dev", true);
+}
+
+int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out, uint64_t *edge_capacity_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (rounds_out) *rounds_out = ctx->greedy_rounds;
+    if (batches_out) *batches_out = ctx->greedy_batches;
+    if (regrows_out) *regrows_out = ctx->greedy_regrows;
+    if (edge_capacity_out) *edge_capacity_out = ctx->greedy_edge_cap;
+    return MG_OK;
 }
 
 

@@ -106,6 +106,8 @@ struct mg_ctx {
     // mg_ctx_set_option: tuning and test knobs of this context (name -> value); a knob that is not set here is looked
     // up in the environment under the same name
     std::map<std::string, std::string> options;
+    // mg_cluster_greedy_stats: what the last mg_cluster_tri_greedy_* call of this context needed
+    uint64_t greedy_rounds = 0, greedy_batches = 0, greedy_regrows = 0, greedy_edge_cap = 0;
     // the compare dispatch's prices, corrected from this context's own launches; the event pairs that time a phase
     SparseCosts costs;
     struct CostClock { hipEvent_t a = nullptr, b = nullptr; };

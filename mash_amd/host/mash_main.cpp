@@ -1630,6 +1630,9 @@ int cmd_triangle(int argc, const char **argv)
 // include/mashgpu.h: mg_cluster_tri_host).  One line per sketch in input order: cluster number (from 1, in order of the
 // clusters' first members), cluster size, name.  The clusters are found on the device and one label per sketch comes back;
 // MASH_AMD_HOST_FINISH=1 takes cmd_triangle's host edge route and a union-find here.
+// -R: greedy representative clusters of the same pairs instead (mg_cluster_tri_greedy_host): walking the sketches in input
+// order, a sketch opens a cluster iff no earlier representative is within the threshold, else it joins the first one that is.
+// Lines and numbering are the same (the label is the representative); the host route runs that walk here.
 int cmd_cluster(int argc, const char **argv)
 {
     Cmd c;
@@ -1637,6 +1640,7 @@ int cmd_cluster(int argc, const char **argv)
     c.add("help", Opt::Boolean, "h");
     c.add("list", Opt::Boolean, "l");
     c.add("comment", Opt::Boolean, "C");
+    c.add("representatives", Opt::Boolean, "R");
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "0.05", 0., 1.);
     c.use_sketch_options();
@@ -1648,10 +1652,14 @@ int cmd_cluster(int argc, const char **argv)
                 "numbered from 1 in order of their first member, which is the cluster's representative.\n"
                 "Options: -l -C and the sketch options of `mash sketch`.\n"
                 "  -d <num>  Maximum distance of an edge (0-1) [0.05]\n"
-                "  -v <num>  Maximum p-value of an edge (0-1) [1.0]\n\n";
+                "  -v <num>  Maximum p-value of an edge (0-1) [1.0]\n"
+                "  -R        Greedy representative clusters instead of single linkage: in input order, a sketch\n"
+                "            becomes a representative if no earlier representative has an edge to it, and joins the\n"
+                "            first representative that has one otherwise.  No two representatives share an edge and\n"
+                "            every member has an edge to its representative.\n\n";
         return 0;
     }
-    const bool comment = c.o("comment").active;
+    const bool comment = c.o("comment").active, greedy = c.o("representatives").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
     if (d_max >= 1.0 && p_max >= 1.0) {
         cerr << "ERROR: With -" << c.o("distance").id << " 1 and -" << c.o("pvalue").id << " 1 every pair is an edge; give a smaller maximum." << endl;
@@ -1676,15 +1684,18 @@ int cmd_cluster(int argc, const char **argv)
     vector<uint32_t> lab(n);
     if (!host_finish_wanted()) {
         uint64_t n_clusters = 0, n_edges = 0;
-        if (mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges) != MG_OK) {
+        const int rc = greedy ? mg_cluster_tri_greedy_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
+                              : mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges);
+        if (rc != MG_OK) {
             cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl;
             return 1;
         }
-        clk.lap("compare+mark+union+label+copy");
+        clk.lap(greedy ? "compare+mark+append+rounds+assign+copy" : "compare+mark+union+label+copy");
     } else {
         for (uint64_t i = 0; i < n; i++) lab[i] = (uint32_t)i;
         auto find = [&](uint32_t x) { while (lab[x] != x) { lab[x] = lab[lab[x]]; x = lab[x]; } return x; };
         vector<mg_edge> edges;
+        vector<vector<uint32_t>> smaller(greedy ? n : 0);      // -R: per sketch its neighbours with a smaller index
         for (uint64_t r0 = 1; r0 < n;) {
             uint64_t r1 = r0, npairs = 0;
             while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 31))) { npairs += r1; r1++; }
@@ -1694,13 +1705,24 @@ int cmd_cluster(int argc, const char **argv)
             for (const mg_edge &e : edges) {
                 mg_pair pr;
                 if (!finish_edge(e, lengths[e.row], lengths[e.col], set.p.kmer, kspace, p_max, pr)) continue;
+                if (greedy) {
+                    smaller[std::max(e.row, e.col)].push_back(std::min(e.row, e.col));
+                    continue;
+                }
                 const uint32_t a = find(e.row), b = find(e.col);
                 if (a != b) lab[std::max(a, b)] = std::min(a, b);
             }
             r0 = r1;
         }
-        for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
-        clk.lap("compare+filter+copy+union");
+        if (greedy) {
+            // the walk in input order: lab[j] == j says that j, decided before i, is a representative
+            for (uint64_t i = 0; i < n; i++)
+                for (const uint32_t j : smaller[i])
+                    if (lab[j] == j && (lab[i] == i || j < lab[i])) lab[i] = j;
+        } else {
+            for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
+        }
+        clk.lap(greedy ? "compare+filter+copy+walk" : "compare+filter+copy+union");
     }
     // label = the cluster's first member: numbers in order of first appearance are numbers by ascending label
     vector<uint32_t> number(n, 0), size(n, 0);
@@ -2257,7 +2279,7 @@ int main(int argc, const char **argv)
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
         "  dist      Estimate the distance of query sequences to references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n"
-        "  cluster   Group sequences into single-linkage clusters by distance.\n  info      Display information about sketch files.\n"
+        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance.\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"
