@@ -287,8 +287,9 @@ int mg_compare_rect_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry,
  * The filter is exact: the threshold is converted on the host (same libm as
  * mg_finish_*) into the smallest passing numer per denom and the device compares
  * integers.  out_host receives the survivors in reference order (row-major;
- * row = triangle row i / query index, col = j / reference index); *count_out is
- * their total number.  If it exceeds `capacity`, MG_ERR_NOMEM is returned, the
+ * row = triangle row i / query index, col = j / reference index: indices into the
+ * TABLES, so a call over rows [row_begin,row_end) / queries [q_begin,q_end) reports
+ * rows row_begin.. / q_begin.., not 0..); *count_out is their total number.  If it exceeds `capacity`, MG_ERR_NOMEM is returned, the
  * content of out_host is unspecified and the caller retries with *count_out
  * entries.  The p-value filter (:419-422) stays with the caller (mg_p_value). */
 typedef struct mg_edge { uint32_t row, col, numer, denom; } mg_edge;
@@ -306,7 +307,10 @@ int mg_compare_rect_filter_host(mg_ctx *ctx, const mg_table *ref, const mg_table
  * pair with numer >= 1 as {row, col, numer, denom}, in reference order; together with the rule and the
  * tables' nhash the caller has every {numer, denom} of the job -- 80 MB instead of 40 GB for 100 000
  * sketches (mg_expand_tri_sparse writes the dense form out of it).  capacity / *count_out / MG_ERR_NOMEM
- * as for the filter calls above. */
+ * as for the filter calls above (capacity 0 with out_host NULL asks for the count alone), and so are row and col:
+ * indices into the tables, strictly ascending by (row, col).  Rect: s = min of the two tables' sketch sizes and |X| =
+ * min(nhash, s) on BOTH sides, so the rule is {0, min(s, min(nhash_q, s) + min(nhash_r, s))} also where the tables
+ * differ in size; an empty range gives *count_out = 0 and writes nothing. */
 int mg_compare_tri_sparse_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end,
                                mg_edge *out_host, uint64_t capacity, uint64_t *count_out);
 int mg_compare_rect_sparse_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry,
@@ -335,9 +339,12 @@ int mg_finish_rect_host(const mg_counts *counts, const uint64_t *len_ref, uint64
 /* The same tail ON THE DEVICE (finish.hip): distances from a table the host builds with its libm
  * (one row per denominator that occurs), p-values by the exact double-double binomial tail of
  * pvalue.h -- both bit-identical to mg_finish_*_host -- and both filters before anything crosses
- * PCIe.  `t` / `ref`,`qry` supply Reference::length by index (the tables must carry lengths).
+ * PCIe.  `t` / `ref`,`qry` supply Reference::length by index (the tables must carry lengths:
+ * MG_ERR_INVALID from mg_finish_*_dev for one uploaded or wrapped without them).
  * max_distance < 0 or >= 1 and max_p_value < 0 or >= 1 disable the respective filter.
- *   mg_finish_*_dev          counts (device, layout of mg_compare_*_dev) -> mg_pair (device)
+ *   mg_finish_*_dev          counts (device, layout of mg_compare_*_dev for the same range) -> mg_pair (device):
+ *                            counts[0] / out_dev[0] belong to row row_begin / query q_begin; the range is clamped to
+ *                            the table as there, an empty one writes nothing
  *   mg_compare_*_pairs_host  compare + finish, every pair, 32 B per pair to the host
  *   mg_compare_*_results_host compare + both filters + ordered compaction: survivors only, in
  *                            reference order; capacity / *count_out / MG_ERR_NOMEM as for

@@ -580,9 +580,10 @@ class LocalComm:
         self._check(self.lib.mg_compare_tri_pairs_sharded_host(self.h, d, 0, n, k, kmer_space, max_d, max_p, out.ctypes.data))
         return out
 
-    def rect_pairs(self, dref, dqry, nref, nq, k, kmer_space, max_d=-1.0, max_p=-1.0):
-        out = np.zeros((nq, nref), dtype=PAIR_DTYPE)
-        self._check(self.lib.mg_compare_rect_pairs_sharded_host(self.h, dref, dqry, 0, nq, k, kmer_space, max_d, max_p, out.ctypes.data))
+    def rect_pairs(self, dref, dqry, nref, nq, k, kmer_space, max_d=-1.0, max_p=-1.0, q_begin=0, q_end=None):
+        q_end = nq if q_end is None else min(q_end, nq)
+        out = np.zeros((max(q_end - q_begin, 0), nref), dtype=PAIR_DTYPE)
+        self._check(self.lib.mg_compare_rect_pairs_sharded_host(self.h, dref, dqry, q_begin, q_end, k, kmer_space, max_d, max_p, out.ctypes.data))
         return out
 
     def _results(self, call, capacity):
@@ -601,9 +602,11 @@ class LocalComm:
         return self._results(lambda o, c, cnt: self.lib.mg_compare_tri_results_sharded_host(
             self.h, d, 0, n, k, kmer_space, max_d, max_p, o, c, cnt), capacity)
 
-    def rect_results(self, dref, dqry, nq, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=1 << 16):
+    def rect_results(self, dref, dqry, nq, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=1 << 16, q_begin=0, q_end=None):
+        """survivors of queries [q_begin, q_end) (q_end None: nq); `row` is the index into the query table"""
+        q_end = nq if q_end is None else q_end
         return self._results(lambda o, c, cnt: self.lib.mg_compare_rect_results_sharded_host(
-            self.h, dref, dqry, 0, nq, k, kmer_space, max_d, max_p, o, c, cnt), capacity)
+            self.h, dref, dqry, q_begin, q_end, k, kmer_space, max_d, max_p, o, c, cnt), capacity)
 
     def compare_rect_topk(self, dref, dqry, k, kmer_space, topk, max_d=-1.0, max_p=-1.0, q_begin=0, q_end=None, capacity=1 << 16):
         """the `topk` nearest references of every query over the devices (mg_compare_rect_topk_sharded_host); q_end None: every query"""
@@ -1013,6 +1016,12 @@ class MashGpu:
     def finish_tri_dev(self, table, counts_ptr, row_begin, row_end, k, kmer_space, max_d, max_p, out_ptr):
         self._check(self.lib.mg_finish_tri_dev(self.ctx, table.handle, counts_ptr, row_begin, row_end, k, kmer_space,
                                                max_d, max_p, out_ptr))
+
+    def finish_rect_dev(self, ref, qry, counts_ptr, q_begin, q_end, k, kmer_space, max_d, max_p, out_ptr):
+        """counts (device, layout of compare_rect_dev for the same range) -> mg_pair records (device): out[0] is query q_begin
+        against reference 0 (mg_finish_rect_dev)"""
+        self._check(self.lib.mg_finish_rect_dev(self.ctx, ref.handle, qry.handle, counts_ptr, q_begin, q_end, k, kmer_space,
+                                                max_d, max_p, out_ptr))
 
     # ---- finishing (host arithmetic) --------------------------------------------
     def finish_tri(self, counts, lengths, row_begin, row_end, k, kmer_space, max_d=-1.0, max_p=-1.0):

@@ -767,7 +767,8 @@ int SparseJobRun::row_side()
             Eq += c;
             if (Eq >= (1ull << 31)) return leave();
             if (c < s) { qshort_h.push_back((uint32_t)q); qshort_cnt_h.push_back((uint32_t)c); }
-            if (c == 0 && job) return leave();
+            // (an empty query is no reason to leave a list job: it has no candidate, and against a reference table without an
+            //  empty row -- open_index has left otherwise -- every pair of it is {0, |B|}: distance 1, p-value 1, numer 0)
             if (c && rows->last[row_begin + q] == MG_HASH_PAD) return leave();
         }
         qoff[nrows] = (uint32_t)Eq;
@@ -1858,6 +1859,7 @@ int mg_finish_tri_dev(mg_ctx *ctx, const mg_table *t, const mg_counts *counts_de
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !counts_dev || !out_dev) return fail(ctx, MG_ERR_INVALID, "mg_finish_tri_dev: NULL argument");
+    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_finish_tri_dev: the table carries no lengths");
     if (row_end > t->n) row_end = t->n;
     if (row_begin >= row_end) return MG_OK;
     return finish_pairs_dev(ctx, t, t, counts_dev, tri_pairs(row_begin, row_end), row_begin, true, kmer_size, kmer_space,
@@ -1871,6 +1873,8 @@ int mg_finish_rect_dev(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, co
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!ref || !qry || !counts_dev || !out_dev) return fail(ctx, MG_ERR_INVALID, "mg_finish_rect_dev: NULL argument");
+    if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
+        return fail(ctx, MG_ERR_INVALID, "mg_finish_rect_dev: the tables carry no lengths");
     if (q_end > qry->n) q_end = qry->n;
     if (q_begin >= q_end) return MG_OK;
     return finish_pairs_dev(ctx, qry, ref, counts_dev, (q_end - q_begin) * ref->n, q_begin, false, kmer_size, kmer_space,

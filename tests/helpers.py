@@ -89,3 +89,200 @@ def load_ref_sketch_vectors(name="ref_sketch_vectors.npz"):
             o += int(l)
         out.append((c, recs, z[f"hashes_{i}"], z[f"counts_{i}"]))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- rect jobs against the oracle
+
+COUNTS = np.dtype([("numer", "<u4"), ("denom", "<u4")])          # mg_counts
+PAD = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def rect_oracle(oracle, rt, rn, rl, qt, qn, ql, k, kspace):
+    """`mash dist` of the query table against the reference table by the oracle: (numer, denom, distance, p_value) as
+    [nq, nref] arrays.  Both tables are cut to s = min(s_ref, s_qry) columns (CommandDistance.cpp:313-315) with nhash
+    clamped to s, the queries are stacked under the references, and rows [nref, nref + nq) of that table's triangle
+    are computed: the first nref columns of such a row are the query against every reference."""
+    nref, nq = len(rn), len(qn)
+    s = min(rt.shape[1], qt.shape[1])
+    table = np.ascontiguousarray(np.concatenate([rt[:, :s], qt[:, :s]]), dtype=np.uint64)
+    nhash = np.minimum(np.concatenate([rn, qn]), s).astype(np.uint32)
+    lengths = np.concatenate([rl, ql]).astype(np.uint64)
+    flat = oracle.triangle(table, nhash, lengths, nref, nref + nq, k, kspace, stats=True)
+    i = np.arange(nq, dtype=np.int64)
+    idx = (nref * i + i * (i - 1) // 2)[:, None] + np.arange(nref, dtype=np.int64)[None, :]     # row nref + i holds nref + i pairs
+    return tuple(np.ascontiguousarray(a[idx]) for a in flat)
+
+
+def expand_rect(edges, rn, qn, s, q_begin, q_end, nref):
+    """The dense counts of queries [q_begin, q_end) out of mg_compare_rect_sparse_host's exceptions (include/mashgpu.h):
+    every pair is {0, min(s, |A| + |B|)} with |X| = min(nhash, s), except the pairs listed in `edges`
+    ({row = query index in the query table, col = reference index, numer, denom})."""
+    q_end = min(q_end, len(qn))
+    nrows = max(q_end - q_begin, 0)
+    out = np.zeros((nrows, nref), dtype=COUNTS)
+    if nrows == 0:
+        assert len(edges) == 0
+        return out
+    a = np.minimum(np.asarray(qn[q_begin:q_end], dtype=np.int64), s)
+    b = np.minimum(np.asarray(rn[:nref], dtype=np.int64), s)
+    out["denom"] = np.minimum(s, a[:, None] + b[None, :])
+    if len(edges):
+        row = edges["row"].astype(np.int64) - q_begin
+        assert row.min() >= 0 and row.max() < nrows and int(edges["col"].max()) < nref
+        out["numer"][row, edges["col"]] = edges["numer"]
+        out["denom"][row, edges["col"]] = edges["denom"]
+    return out
+
+
+def edges_of(numer, denom, q_begin=0):
+    """the exceptions of a dense [nq, nref] result: every pair with numer >= 1, query major, `row` offset by q_begin"""
+    q, r = np.nonzero(numer >= 1)
+    e = np.zeros(len(q), dtype=np.dtype([("row", "<u4"), ("col", "<u4"), ("numer", "<u4"), ("denom", "<u4")]))
+    e["row"], e["col"], e["numer"], e["denom"] = q + q_begin, r, numer[q, r], denom[q, r]
+    return e
+
+
+def shares_a_hash(rt, rn, qt, qn, s):
+    """bool [nq, nref]: the two sketches (each cut to its first min(nhash, s) hashes) have a hash in common"""
+    nref = len(rn)
+    cols = np.arange(min(rt.shape[1], s))[None, :]
+    refs = np.where(cols < np.minimum(rn, s)[:, None], rt[:, :cols.shape[1]], PAD)
+    out = np.zeros((len(qn), nref), dtype=bool)
+    for q in range(len(qn)):
+        mine = qt[q, : min(int(qn[q]), s)]
+        if len(mine):
+            out[q] = np.isin(refs, mine).any(axis=1)
+    return out
+
+
+def _pad_rows(table, nhash):
+    table = table.copy()
+    table[np.arange(table.shape[1])[None, :] >= nhash[:, None]] = PAD
+    return table
+
+
+def rect_case_clean():
+    """1 200 references without an empty, short or copied row (the list engine takes the table) and 87 queries: copies of
+    references, relatives, strangers, and the edges of the merge.  Returns a dict of the six arrays and what is where."""
+    from workloads import synth
+    nref, s = 1200, 256
+    table, nhash, _ = synth.clustered_sketches(1240, s, clusters=24, seed=21, pool=400, private=100)
+    rng = np.random.default_rng(8)
+    rl = rng.integers(10 ** 4, 10 ** 8, nref).astype(np.uint64)
+    rt, rn = table[:nref], nhash[:nref]
+    spare_t, spare_n = table[nref:], nhash[nref:]
+    originals = rng.choice(nref, 24, replace=False)
+    st, sn, _ = synth.random_sketches(16, s, seed=5)
+    rows, counts = [], []
+
+    def add(h, n=None):
+        row = np.full(s, PAD, dtype=np.uint64)
+        n = len(h) if n is None else n
+        row[:n] = h[:n]
+        rows.append(row)
+        counts.append(n)
+        return len(rows) - 1
+
+    for o in originals:
+        add(rt[o], int(rn[o]))
+    for i in range(40):
+        add(spare_t[i], int(spare_n[i]))
+    for i in range(16):
+        add(st[i], int(sn[i]))
+    where = {"copies": (0, originals), "relatives": 24, "strangers": 64}
+    where["empty"] = add(np.zeros(0, dtype=np.uint64))
+    where["last_of_7"] = add(rt[7, int(rn[7]) - 1: int(rn[7])])
+    where["above"] = add(np.uint64(0xFFFFFFFFFFFFFF00) - np.arange(s, 0, -1, dtype=np.uint64))
+    where["behind_11"] = add(np.concatenate([np.arange(1, s, dtype=np.uint64), rt[11, int(rn[11]) - 1: int(rn[11])]]))
+    where["short"] = add(spare_t[3], 90)
+    where["twice"] = (add(spare_t[5], int(spare_n[5])), add(spare_t[5], int(spare_n[5])))
+    qt, qn = np.stack(rows), np.array(counts, dtype=np.uint32)
+    ql = rng.integers(10 ** 4, 10 ** 8, len(qn)).astype(np.uint64)
+    return {"rt": np.ascontiguousarray(rt), "rn": rn.copy(), "rl": rl, "qt": qt, "qn": qn, "ql": ql, "where": where}
+
+
+def rect_case_ragged():
+    """the references of rect_case_clean with short, empty and copied rows (the list engine declines such a table) and the 40
+    spare rows as queries, every third one short and one empty"""
+    from workloads import synth
+    nref, s = 1200, 256
+    table, nhash, _ = synth.clustered_sketches(1240, s, clusters=24, seed=21, pool=400, private=100)
+    rng = np.random.default_rng(8)
+    rl = rng.integers(10 ** 4, 10 ** 8, nref).astype(np.uint64)
+    ql = rng.integers(10 ** 4, 10 ** 8, 40).astype(np.uint64)
+    rt, rn = table[:nref].copy(), nhash[:nref].copy()
+    qt, qn = table[nref:].copy(), nhash[nref:].copy()
+    for i in range(0, nref, 7):
+        rn[i] = rng.integers(0, 200)
+    rn[3] = rn[4] = 0
+    rn[9] = 1
+    rn[10] = s - 1
+    rt[21], rn[21] = rt[20], rn[20]
+    for i in range(0, 40, 3):
+        qn[i] = rng.integers(1, 150)
+    qn[1] = 0
+    return {"rt": _pad_rows(rt, rn), "rn": rn, "rl": rl, "qt": _pad_rows(qt, qn), "qn": qn, "ql": ql, "where": {}}
+
+
+def rect_case_species():
+    """600 rows of one species as references; 40 of them and 20 rows of another tree of descent as queries"""
+    from workloads import synth
+    rt, rn, rl = synth.species_sketches(600, 256, seed=9)
+    ot, on, ol = synth.species_sketches(20, 256, seed=10)
+    return {"rt": rt, "rn": rn, "rl": rl, "qt": np.concatenate([rt[100:140], ot]), "qn": np.concatenate([rn[100:140], on]),
+            "ql": np.concatenate([rl[100:140], ol]), "where": {"own": (0, 40), "strangers": (40, 60)}}
+
+
+def rect_case_sized(case, s_ref, s_qry):
+    """the same arrays with the reference table cut to s_ref columns and the query table to s_qry (nhash clamped)"""
+    out = dict(case)
+    out["rt"] = np.ascontiguousarray(case["rt"][:, :s_ref])
+    out["rn"] = np.minimum(case["rn"], s_ref).astype(np.uint32)
+    out["qt"] = np.ascontiguousarray(case["qt"][:, :s_qry])
+    out["qn"] = np.minimum(case["qn"], s_qry).astype(np.uint32)
+    return out
+
+
+def rect_case_oracle(oracle, case, k=21, kspace=4.0 ** 21):
+    return rect_oracle(oracle, case["rt"], case["rn"], case["rl"], case["qt"], case["qn"], case["ql"], k, kspace)
+
+
+def check_rect_case_conditions(name, case, numer, denom):
+    """What the rect tests rely on, asserted on the oracle's output alone (the counts in the comments: what this seed gives)."""
+    s = min(case["rt"].shape[1], case["qt"].shape[1])
+    nq, nref = numer.shape
+    w = case["where"]
+    if name == "clean":
+        assert (nq, nref) == (87, 1200)
+        assert case["rn"].min() == 256 and case["qn"][:80].min() == 256                   # no short row among the references
+        assert len(np.unique(case["rt"], axis=0)) == nref                                  # no copied row
+        hit = numer >= 1
+        assert 0.01 * numer.size < hit.sum() < 0.2 * numer.size                            # 3 382 of 104 400
+        behind = shares_a_hash(case["rt"], case["rn"], case["qt"], case["qn"], s) & ~hit
+        assert behind.sum() >= 1 and behind[w["behind_11"], 11]                            # 1: shares a hash, numer 0
+        q0, originals = w["copies"]
+        for i, o in enumerate(originals):                                                  # every copy finds its original
+            assert numer[q0 + i, o] == case["rn"][o] == denom[q0 + i, o]
+        assert not numer[w["strangers"]: w["strangers"] + 16].any() and not numer[w["empty"]].any() and not numer[w["above"]].any()
+        assert np.array_equal(denom[w["empty"]], np.minimum(case["rn"], s))                # |A| + 0
+        assert numer[w["last_of_7"], 7] == 1 and denom[w["last_of_7"], 7] == 256           # ... as the last union element
+        assert numer[w["relatives"]: w["relatives"] + 40].max() > 100
+        assert case["qn"][w["short"]] == 90 and numer[w["short"]].max() > 0
+        a, b = w["twice"]
+        assert np.array_equal(numer[a], numer[b]) and np.array_equal(denom[a], denom[b]) and numer[a].any()
+    elif name == "ragged":
+        assert (nq, nref) == (40, 1200)
+        hit = numer >= 1
+        assert len(np.unique(denom)) >= 100                                                # 255
+        assert ((numer == 0) & (denom == 0)).sum() >= 1                                    # 2: empty against empty
+        assert 0.01 * numer.size <= hit.sum() <= 0.2 * numer.size                          # 1 945 of 48 000
+        assert np.array_equal(case["rt"][21], case["rt"][20]) and case["rn"][9] == 1 and case["rn"][10] == 255
+    elif name == "species":
+        assert (nq, nref) == (60, 600)
+        (a, b), (c, d) = w["own"], w["strangers"]
+        own = np.delete(numer[a:b], np.arange(100, 140), axis=1)                           # (without the rows themselves)
+        assert 0.08 * 256 < np.percentile(own, 1) and np.percentile(own, 99) < 0.6 * 256   # 36 .. 106 of 256
+        assert all(numer[i, 100 + i] == 256 for i in range(40))
+        assert not numer[c:d].any()
+    else:
+        raise AssertionError(name)
