@@ -266,6 +266,9 @@ uint64_t mg_table_sketch_size(const mg_table *t);
  * Triangle (replaces compare(TriangleInput*), CommandTriangle.cpp:200-214):
  * rows [row_begin,row_end) of the lower triangle, output in reference order:
  * for i in rows, for j in [0,i): out[i*(i-1)/2 + j - row_begin*(row_begin-1)/2].
+ * Row 0 has no pairs (rows [0,1) are an empty job); row_end is clamped to the table's
+ * rows; an empty range (row_begin >= the clamped row_end) writes nothing, and the calls
+ * that report a count report 0 for it.
  *
  * Rect (replaces compare(CompareInput*), CommandDistance.cpp:306-334):
  * queries [q_begin,q_end) x all refs, query-major: out[(q-q_begin)*nref + r].
@@ -340,7 +343,8 @@ int mg_finish_rect_host(const mg_counts *counts, const uint64_t *len_ref, uint64
  * (one row per denominator that occurs), p-values by the exact double-double binomial tail of
  * pvalue.h -- both bit-identical to mg_finish_*_host -- and both filters before anything crosses
  * PCIe.  `t` / `ref`,`qry` supply Reference::length by index (the tables must carry lengths:
- * MG_ERR_INVALID from mg_finish_*_dev for one uploaded or wrapped without them).
+ * MG_ERR_INVALID from mg_finish_*_dev, mg_compare_*_pairs_host and mg_compare_*_results_host -- and from their
+ * sharded forms -- for one uploaded or wrapped without them).
  * max_distance < 0 or >= 1 and max_p_value < 0 or >= 1 disable the respective filter.
  *   mg_finish_*_dev          counts (device, layout of mg_compare_*_dev for the same range) -> mg_pair (device):
  *                            counts[0] / out_dev[0] belong to row row_begin / query q_begin; the range is clamped to

@@ -575,9 +575,11 @@ class LocalComm:
         self._check(self.lib.mg_compare_rect_sharded_host(self.h, dref, dqry, q_begin, q_end, out.ctypes.data))
         return out
 
-    def tri_pairs(self, d, n, k, kmer_space, max_d=-1.0, max_p=-1.0):
-        out = np.zeros(tri_pairs(0, n), dtype=PAIR_DTYPE)
-        self._check(self.lib.mg_compare_tri_pairs_sharded_host(self.h, d, 0, n, k, kmer_space, max_d, max_p, out.ctypes.data))
+    def tri_pairs(self, d, n, k, kmer_space, max_d=-1.0, max_p=-1.0, row_begin=0, row_end=None):
+        """every pair of rows [row_begin, row_end) x earlier rows (row_end None: n), reference order"""
+        row_end = n if row_end is None else min(row_end, n)
+        out = np.zeros(tri_pairs(row_begin, max(row_end, row_begin)), dtype=PAIR_DTYPE)
+        self._check(self.lib.mg_compare_tri_pairs_sharded_host(self.h, d, row_begin, row_end, k, kmer_space, max_d, max_p, out.ctypes.data))
         return out
 
     def rect_pairs(self, dref, dqry, nref, nq, k, kmer_space, max_d=-1.0, max_p=-1.0, q_begin=0, q_end=None):
@@ -598,9 +600,11 @@ class LocalComm:
             capacity = n.value
         self._check(rc)
 
-    def tri_results(self, d, n, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=1 << 16):
+    def tri_results(self, d, n, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=1 << 16, row_begin=0, row_end=None):
+        """survivors of rows [row_begin, row_end) (row_end None: n); `row` and `col` are indices into the table"""
+        row_end = n if row_end is None else row_end
         return self._results(lambda o, c, cnt: self.lib.mg_compare_tri_results_sharded_host(
-            self.h, d, 0, n, k, kmer_space, max_d, max_p, o, c, cnt), capacity)
+            self.h, d, row_begin, row_end, k, kmer_space, max_d, max_p, o, c, cnt), capacity)
 
     def rect_results(self, dref, dqry, nq, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=1 << 16, q_begin=0, q_end=None):
         """survivors of queries [q_begin, q_end) (q_end None: nq); `row` is the index into the query table"""

@@ -252,6 +252,7 @@ int mg_dtable_upload(mg_comm *c, const uint64_t *hashes, const uint32_t *nhash, 
         mg_table *t = new mg_table;
         t->ctx = x; t->hashes = (const uint64_t *)ph; t->nhash = (const uint32_t *)pn; t->lengths = (const uint64_t *)pl;
         t->n = n; t->s = s; t->owns = true;
+        t->has_lengths = t0->has_lengths;
         d->t.push_back(t);
         bh.push_back(ph); bn.push_back(pn); bl.push_back(pl);
     }
@@ -330,7 +331,7 @@ int mg_table_broadcast(mg_comm *c, const mg_table *src, int root, uint64_t n, ui
 {
     if (!c || c->local || !out || root < 0 || root >= c->nranks) return comm_fail(c, MG_ERR_INVALID, "mg_table_broadcast: needs a rank communicator");
     mg_ctx *x = c->ctxs[0];
-    if (c->rank == root && (!src || src->n != n || src->s != s || !src->lengths))
+    if (c->rank == root && (!src || src->n != n || src->s != s || !src->lengths || !src->has_lengths))
         return comm_fail(c, MG_ERR_INVALID, "mg_table_broadcast: the root must pass the table (with lengths) and its true size");
     if (hipSetDevice(x->device) != hipSuccess) return comm_fail(c, MG_ERR_HIP, "hipSetDevice failed");
     mg_table *t = new mg_table;
@@ -441,6 +442,7 @@ static int ref_block(mg_comm *c, const mg_dtable *ref, size_t g, const mg_table 
     const int rc = mg_table_wrap_dev(c->ctxs[g], full->hashes + lo * full->s, full->nhash + lo, full->lengths ? full->lengths + lo : nullptr,
                                      hi - lo, full->s, &view);
     if (rc != MG_OK) return rc;
+    view->has_lengths = full->has_lengths;
     ref->views.push_back({g, lo, hi, view});
     *tab = view;
     return MG_OK;

@@ -1361,6 +1361,8 @@ static int run_compare(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, 
 {
     if (row_end > rows->n) row_end = rows->n;
     if (row_begin >= row_end) return MG_OK;
+    // rows [0, 1) of a triangle: row 0 has no pair, so there is nothing to write -- and nothing a forced engine could refuse
+    if (triangle && row_end <= 1) return MG_OK;
     if (rows->n > 0xFFFFFFFFull || cols->n > 0xFFFFFFFFull) return fail(ctx, MG_ERR_INVALID, "compare: table too large");
     const uint64_t s64 = std::min(rows->s, cols->s);       // CommandDistance.cpp:313-315
     if (s64 > 0xFFFFFFFFull) return fail(ctx, MG_ERR_INVALID, "compare: sketch size too large");
@@ -1932,7 +1934,7 @@ int mg_compare_tri_pairs_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !out_host) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_pairs_host: NULL argument");
-    if (!t->lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_pairs_host: the table carries no lengths");
+    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_pairs_host: the table carries no lengths");
     return compare_pairs_host(ctx, t, t, row_begin, row_end, true, kmer_size, kmer_space, max_distance, max_p_value, out_host);
 }
 
@@ -1942,7 +1944,8 @@ int mg_compare_rect_pairs_host(mg_ctx *ctx, const mg_table *ref, const mg_table 
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!ref || !qry || !out_host) return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_pairs_host: NULL argument");
-    if (!ref->lengths || !qry->lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_pairs_host: the tables carry no lengths");
+    if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
+        return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_pairs_host: the tables carry no lengths");
     return compare_pairs_host(ctx, qry, ref, q_begin, q_end, false, kmer_size, kmer_space, max_distance, max_p_value, out_host);
 }
 
@@ -2206,7 +2209,7 @@ int mg_compare_tri_results_host(mg_ctx *ctx, const mg_table *t, uint64_t row_beg
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !count_out || (!out_host && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_results_host: NULL argument");
-    if (!t->lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_results_host: the table carries no lengths");
+    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_results_host: the table carries no lengths");
     return compare_results(ctx, t, t, row_begin, row_end, true, kmer_size, kmer_space, max_distance, max_p_value, out_host, capacity, count_out);
 }
 
@@ -2218,7 +2221,8 @@ int mg_compare_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_tabl
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!ref || !qry || !count_out || (!out_host && capacity))
         return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_results_host: NULL argument");
-    if (!ref->lengths || !qry->lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_results_host: the tables carry no lengths");
+    if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
+        return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_results_host: the tables carry no lengths");
     return compare_results(ctx, qry, ref, q_begin, q_end, false, kmer_size, kmer_space, max_distance, max_p_value, out_host, capacity, count_out);
 }
 
@@ -2338,7 +2342,7 @@ static int cluster_entry(mg_ctx *ctx, const mg_table *t, int kmer_size, double k
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !n_clusters_out || !n_edges_out || (!label_out && t->n)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (!t->lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
+    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
     if (!((max_distance >= 0.0 && max_distance < 1.0) || (max_p_value >= 0.0 && max_p_value < 1.0)))
         return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
     return (greedy ? cluster_greedy_tri : cluster_tri)(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out, label_on_device,

@@ -377,6 +377,7 @@ const mg_table *table_prefix_view(const mg_table *t, uint64_t n)
     v->hashes = t->hashes;
     v->nhash = t->nhash;
     v->lengths = t->lengths;
+    v->has_lengths = t->has_lengths;
     v->n = n;
     v->s = t->s;
     v->owns = false;

@@ -286,3 +286,246 @@ def check_rect_case_conditions(name, case, numer, denom):
         assert not numer[c:d].any()
     else:
         raise AssertionError(name)
+
+
+# ---------------------------------------------------------------------------------------------- finished records against the oracle
+
+def _set_kernel(monkeypatch, kernel):
+    """tests/test_gpu_parity.py's conventions; "default": the dispatch's own choice"""
+    for v in ("MASHGPU_COMPARE_KERNEL", "MASHGPU_COMPARE_WINDOWS", "MASHGPU_COMPARE_WIN_TARGET", "MASHGPU_RESULTS_MATRIX"):
+        monkeypatch.delenv(v, raising=False)
+    if kernel == "default":
+        return
+    if kernel == "plain":
+        monkeypatch.setenv("MASHGPU_COMPARE_KERNEL", "merged")
+        monkeypatch.setenv("MASHGPU_COMPARE_WINDOWS", "0")
+    elif kernel.startswith("windows"):
+        monkeypatch.setenv("MASHGPU_COMPARE_KERNEL", "merged")
+        monkeypatch.setenv("MASHGPU_COMPARE_WINDOWS", "1")
+        if kernel != "windows":
+            monkeypatch.setenv("MASHGPU_COMPARE_WIN_TARGET", kernel[len("windows"):])
+    else:
+        monkeypatch.setenv("MASHGPU_COMPARE_KERNEL", kernel)
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+
+
+def _oracle_pass(c, max_d, max_p):
+    """compareSketches' two filters (CommandDistance.cpp:409-422) on the oracle's distances and p-values"""
+    ok = np.ones(c["numer"].shape, dtype=bool)
+    if max_d >= 0:
+        ok &= c["dist"] <= max_d
+    if max_p >= 0:
+        ok &= c["pval"] <= max_p
+    return ok
+
+
+def _check_records_against_oracle(rec, c, lo, hi, max_d, max_p):
+    """finished records against the oracle's arrays c["numer"], c["denom"], c["dist"], c["pval"] cut to [lo:hi) along their first
+    axis -- queries [lo, hi) of a [nq, nref] rect result, or pairs [lo, hi) of a triangle's flat arrays: integers, pass and
+    distance equal, p-values at the oracle's own accuracy (where the distance filter rejected a pair only `pass` is meaningful)"""
+    assert np.array_equal(rec["numer"], c["numer"][lo:hi]) and np.array_equal(rec["denom"], c["denom"][lo:hi])
+    assert np.array_equal(rec["pass"] == 1, _oracle_pass(c, max_d, max_p)[lo:hi])
+    assert np.array_equal(rec["distance"], c["dist"][lo:hi])
+    seen = c["dist"][lo:hi] <= max_d if max_d >= 0 else np.ones(rec.shape, dtype=bool)
+    got, want = rec["p_value"][seen], c["pval"][lo:hi][seen]
+    big = want > 1e-290
+    assert np.all(np.abs(got[big] - want[big]) <= 1e-9 * want[big]) and np.all(got[~big] <= 1e-280)
+
+
+# ---------------------------------------------------------------------------------------------- triangle jobs against the oracle
+#
+# The judge is oracle.triangle(table, nhash, lengths, rb, re, k, kspace, stats=True): flat arrays in reference order (row rb
+# against rows 0 .. rb - 1, then row rb + 1, ...; row 0 has no pair).
+
+EDGE = np.dtype([("row", "<u4"), ("col", "<u4"), ("numer", "<u4"), ("denom", "<u4")])        # mg_edge
+
+
+def tri_base(row):
+    """the pairs of the triangle ahead of `row`"""
+    return row * (row - 1) // 2 if row > 0 else 0
+
+
+def tri_slice(flat, rb, re):
+    """the slice of a WHOLE triangle's flat array that rows [rb, re) occupy"""
+    return flat[tri_base(rb): tri_base(max(re, rb))]
+
+
+def tri_rows_cols(rb, re):
+    """(row, col) of every pair of rows [rb, re), reference order"""
+    r = np.arange(rb, max(re, rb), dtype=np.int64)
+    rows = np.repeat(r, r)
+    start = np.repeat(r * (r - 1) // 2 - tri_base(rb), r)               # where each pair's row begins in the range
+    return rows, np.arange(len(rows), dtype=np.int64) - start
+
+
+def edges_of_tri(numer, denom, rb, re):
+    """the exceptions of rows [rb, re): every pair with numer >= 1 as {row, col, numer, denom} with table indices, reference order;
+    numer and denom are the flat arrays OF THE RANGE (oracle.triangle over [rb, re), or tri_slice of the whole triangle)"""
+    rows, cols = tri_rows_cols(rb, re)
+    assert len(numer) == len(rows) == len(denom)
+    at = np.nonzero(numer >= 1)[0]
+    e = np.zeros(len(at), dtype=EDGE)
+    e["row"], e["col"], e["numer"], e["denom"] = rows[at], cols[at], numer[at], denom[at]
+    return e
+
+
+def expand_tri(edges, nhash, s, rb, re):
+    """The dense counts of rows [rb, re) out of mg_compare_tri_sparse_host's exceptions (include/mashgpu.h): every pair is
+    {0, min(s, |A| + |B|)} with |X| = min(nhash, s), except the pairs listed in `edges`.  The CPU judge of mg_expand_tri_sparse."""
+    re = min(re, len(nhash))
+    rows, cols = tri_rows_cols(rb, re)
+    out = np.zeros(len(rows), dtype=COUNTS)
+    if len(rows) == 0:
+        assert len(edges) == 0
+        return out
+    size = np.minimum(np.asarray(nhash, dtype=np.int64), s)
+    out["denom"] = np.minimum(s, size[rows] + size[cols])
+    if len(edges):
+        r, c = edges["row"].astype(np.int64), edges["col"].astype(np.int64)
+        assert r.min() >= rb and r.max() < re and np.all(c < r)
+        at = r * (r - 1) // 2 - tri_base(rb) + c
+        out["numer"][at] = edges["numer"]
+        out["denom"][at] = edges["denom"]
+    return out
+
+
+def clade_table(rng, sizes, s, keep=0.96, private=0.03, short_every=0, gap_rows=3, short_min=1 / 3):
+    """tests/test_gpu_parity.py's _clade_table (without its clumps): consecutive clades of the given sizes, near-copies of a pool
+    of 1.06 s values, `gap_rows` unrelated rows behind each, every short_every-th row of a clade cut to short_min s .. s - 1
+    hashes; returns (table, nhash, [(first, last + 1) of every clade])"""
+    rows, spans = [], []
+    for m in sizes:
+        pool = np.unique(rng.integers(1, 1 << 60, size=int(1.06 * s) + 8).astype(np.uint64))
+        spans.append((len(rows), len(rows) + m))
+        for i in range(m):
+            own = pool[rng.random(len(pool)) < keep]
+            priv = rng.integers(1, 1 << 60, size=max(1, int(private * s))).astype(np.uint64)
+            r = np.unique(np.concatenate([own, priv]))
+            k = s if not (short_every and i % short_every == 1) else int(rng.integers(int(short_min * s), s))
+            rows.append(r[:k])
+        for _ in range(gap_rows):
+            rows.append(np.unique(rng.integers(1, 1 << 60, size=s + 8).astype(np.uint64))[:s])
+    table = np.full((len(rows), s), PAD, dtype=np.uint64)
+    nhash = np.zeros(len(rows), dtype=np.uint32)
+    for i, r in enumerate(rows):
+        table[i, : len(r)] = r
+        nhash[i] = len(r)
+    return table, nhash, spans
+
+
+def _tri_case(table, nhash, lengths, where):
+    return {"table": np.ascontiguousarray(table), "nhash": np.ascontiguousarray(nhash, dtype=np.uint32),
+            "lengths": np.ascontiguousarray(lengths, dtype=np.uint64), "n": len(nhash), "s": table.shape[1], "where": where}
+
+
+def tri_case_families():
+    """3 200 rows of s = 64 in 16 interleaved families, every third row with 20 .. 97 % of its hashes replaced: the smallest table
+    on which a proper range of rows still has 4 * 10^6 pairs (the prefix view of host_compare.cpp engages).  No empty, short or
+    copied row: the list engine takes the table.  Row 3001 shares its last hash with row 11 -- behind the 64 smallest of their
+    union, so the pair counts nothing."""
+    from workloads import synth
+    n, s = 3200, 64
+    table, nhash, _ = synth.clustered_sketches(n, s, clusters=16, seed=61, pool=80, private=8, keep_p=0.9)
+    table, nhash = table.copy(), nhash.copy()
+    rng = np.random.default_rng(3)
+    for i in range(0, n, 3):
+        u = rng.uniform(0.2, 0.97)
+        m = rng.random(s) < u
+        row = table[i].copy()
+        row[m] = rng.integers(1, 1 << 60, int(m.sum())).astype(np.uint64)
+        table[i] = np.sort(row)
+    lengths = rng.integers(10 ** 4, 10 ** 8, n).astype(np.uint64)
+    table[3001] = np.concatenate([np.arange(1, s, dtype=np.uint64), table[11, s - 1:]])
+    return _tri_case(table, nhash, lengths, {"behind": (3001, 11)})
+
+
+def tri_case_families_ragged():
+    """tri_case_families with empty, short and copied rows: the list engine declines such a table, so list jobs take the blocked
+    matrix path"""
+    c = tri_case_families()
+    table, nhash = c["table"].copy(), c["nhash"].copy()
+    rng = np.random.default_rng(4)
+    for i in range(0, c["n"], 50):
+        nhash[i] = rng.integers(1, 64)
+    nhash[100] = nhash[2950] = 0
+    nhash[150], nhash[250] = 1, 63
+    table[2000], nhash[2000] = table[1999], nhash[1999]
+    table[3100], nhash[3100] = table[7], nhash[7]
+    where = {"empty": (100, 2950), "copies": ((2000, 1999), (3100, 7)), "one_hash": 150, "one_short": 250}
+    return _tri_case(_pad_rows(table, nhash), nhash, c["lengths"], where)
+
+
+def tri_case_head(case, n):
+    """the first n rows of a case as a case of its own"""
+    return _tri_case(case["table"][:n], case["nhash"][:n], case["lengths"][:n], {})
+
+
+def tri_case_clades():
+    """520 rows of s = 128: six consecutive clades of near-copies, every fifth row of a clade short (103 .. 127 hashes), three unrelated rows behind each"""
+    rng = np.random.default_rng(77)
+    table, nhash, spans = clade_table(rng, (70, 9, 200, 33, 150, 40), 128, keep=0.95, private=0.03, short_every=5, short_min=0.8)
+    lengths = rng.integers(10 ** 4, 10 ** 8, len(nhash)).astype(np.uint64)
+    return _tri_case(table, nhash, lengths, {"clades": spans})
+
+
+def tri_case_species():
+    """the rect suite's table: 600 rows of one species"""
+    from workloads import synth
+    table, nhash, lengths = synth.species_sketches(600, 256, seed=9)
+    return _tri_case(table, nhash, lengths, {})
+
+
+def tri_case_oracle(oracle, case, k=21, kspace=4.0 ** 21):
+    """the oracle's whole triangle of a case: (numer, denom, dist, pval), flat"""
+    return oracle.triangle(case["table"], case["nhash"], case["lengths"], 0, case["n"], k, kspace, stats=True)
+
+
+# What the GPU tests ask of a filter that is on: (max_d, max_p) and whether it may pass nothing
+TRI_FILTERS_FAMILIES = ((0.05, -1.0), (0.03, -1.0), (-1.0, 1e-30), (0.05, 1e-30), (0.0, 1.0))
+
+
+def check_tri_case_conditions(name, case, numer, denom, dist, pval):
+    """What the triangle tests rely on, asserted on the oracle's output alone (the counts in the comments: what these seeds give)."""
+    n, s, w = case["n"], case["s"], case["where"]
+    assert len(numer) == n * (n - 1) // 2
+    hit = numer >= 1
+    if name == "families":
+        assert case["table"].shape == (3200, 64) and case["nhash"].min() == 64               # no short row
+        assert len(np.unique(case["table"], axis=0)) == n                                     # no copied row
+        assert 0.01 * numer.size < hit.sum() < 0.2 * numer.size                               # 315 396 of 5 118 400 (6.2 %)
+        row, col = w["behind"]
+        assert case["table"][row, s - 1] == case["table"][col, s - 1]                         # shares a hash ...
+        assert numer[tri_base(row) + col] == 0 and denom[tri_base(row) + col] == s            # ... and counts nothing
+        c = {"numer": numer, "denom": denom, "dist": dist, "pval": pval}
+        for max_d, max_p in TRI_FILTERS_FAMILIES:
+            share = (_oracle_pass(c, max_d, max_p) & hit).sum() / hit.sum()
+            if (max_d, max_p) == (0.0, 1.0):
+                assert share == 0                                                             # nothing: no copy in the table
+            else:
+                assert 0.05 < share < 0.95, (max_d, max_p, share)                             # 78 %, 63 %, 89 %, 78 % of the hits
+    elif name == "families_ragged":
+        assert case["table"].shape == (3200, 64)
+        # (a denominator at s = 64 is one of 0 .. 64: "at least 100 distinct" cannot hold on this table; nearly all of the 65 must)
+        assert len(np.unique(denom)) >= 60                                                    # 62
+        a, b = w["empty"]
+        assert numer[tri_base(b) + a] == 0 and denom[tri_base(b) + a] == 0                    # empty against empty
+        assert ((numer == 0) & (denom == 0)).sum() >= 1                                       # 1
+        for row, col in w["copies"]:
+            assert numer[tri_base(row) + col] == denom[tri_base(row) + col] == case["nhash"][row] == case["nhash"][col]
+        assert case["nhash"][w["one_hash"]] == 1 and case["nhash"][w["one_short"]] == 63
+        assert 0.01 * numer.size < hit.sum() < 0.2 * numer.size                               # 314 855 (6.2 %)
+    elif name == "clades":
+        assert 500 <= n <= 540 and s == 128
+        rows, cols = tri_rows_cols(0, n)
+        for a, b in w["clades"]:
+            inside = (rows >= a) & (rows < b) & (cols >= a)
+            assert np.percentile(numer[inside], 1) > 0.5 * s, (a, b)                          # 92 .. 101 of 128
+        assert (case["nhash"] < s).sum() >= 50 and (numer == 0).any()                           # 101 short rows; 74 % of the pairs
+    elif name == "species":
+        assert (n, s) == (600, 256)
+        assert 0.08 * s < np.percentile(numer, 1) and np.percentile(numer, 99) < 0.6 * s      # 37 .. 102 of 256
+    else:
+        raise AssertionError(name)

@@ -12,6 +12,7 @@ import pytest
 
 from mash_amd import abi
 from tests import helpers
+from tests.helpers import _check_records_against_oracle, _oracle_pass, _same_bits, _set_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -35,24 +36,6 @@ def _ranges(nq):
     """the whole table, the first and the last query, ranges across the 16-row plain tiles and the <= 32-row window tiles, one the
     library clamps, two empty ones"""
     return [(0, nq), (0, 1), (nq - 1, nq), (15, 17), (31, 65), (5, nq + 1000), (nq, nq), (40, 40)]
-
-
-def _set_kernel(monkeypatch, kernel):
-    """tests/test_gpu_parity.py's conventions; "default": the dispatch's own choice"""
-    for v in ("MASHGPU_COMPARE_KERNEL", "MASHGPU_COMPARE_WINDOWS", "MASHGPU_COMPARE_WIN_TARGET", "MASHGPU_RESULTS_MATRIX"):
-        monkeypatch.delenv(v, raising=False)
-    if kernel == "default":
-        return
-    if kernel == "plain":
-        monkeypatch.setenv("MASHGPU_COMPARE_KERNEL", "merged")
-        monkeypatch.setenv("MASHGPU_COMPARE_WINDOWS", "0")
-    elif kernel.startswith("windows"):
-        monkeypatch.setenv("MASHGPU_COMPARE_KERNEL", "merged")
-        monkeypatch.setenv("MASHGPU_COMPARE_WINDOWS", "1")
-        if kernel != "windows":
-            monkeypatch.setenv("MASHGPU_COMPARE_WIN_TARGET", kernel[len("windows"):])
-    else:
-        monkeypatch.setenv("MASHGPU_COMPARE_KERNEL", kernel)
 
 
 @pytest.fixture(scope="module")
@@ -116,32 +99,6 @@ def host_fin(eng, cases):
 def _clamp(qb, qe, nq):
     hi = min(qe, nq)
     return qb, hi, max(hi - qb, 0)
-
-
-def _same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
-
-
-def _oracle_pass(c, max_d, max_p):
-    """compareSketches' two filters (CommandDistance.cpp:409-422) on the oracle's distances and p-values"""
-    ok = np.ones(c["numer"].shape, dtype=bool)
-    if max_d >= 0:
-        ok &= c["dist"] <= max_d
-    if max_p >= 0:
-        ok &= c["pval"] <= max_p
-    return ok
-
-
-def _check_records_against_oracle(rec, c, lo, hi, max_d, max_p):
-    """finished records [hi - lo, nref] of queries [lo, hi) against the oracle: integers, pass and distance equal, p-values at the
-    oracle's own accuracy (where the distance filter rejected a pair only `pass` is meaningful)"""
-    assert np.array_equal(rec["numer"], c["numer"][lo:hi]) and np.array_equal(rec["denom"], c["denom"][lo:hi])
-    assert np.array_equal(rec["pass"] == 1, _oracle_pass(c, max_d, max_p)[lo:hi])
-    assert np.array_equal(rec["distance"], c["dist"][lo:hi])
-    seen = c["dist"][lo:hi] <= max_d if max_d >= 0 else np.ones(rec.shape, dtype=bool)
-    got, want = rec["p_value"][seen], c["pval"][lo:hi][seen]
-    big = want > 1e-290
-    assert np.all(np.abs(got[big] - want[big]) <= 1e-9 * want[big]) and np.all(got[~big] <= 1e-280)
 
 
 def _check_records_against_host(rec, host, max_d):
