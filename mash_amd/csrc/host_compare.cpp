@@ -1534,6 +1534,45 @@ static std::vector<RowBlock> row_blocks(const OutRange &R, uint64_t max_pairs, u
     return v;
 }
 
+// How a caller has its matrix cut: row blocks of at most `pairs` pairs -- or of what the option `knob` says (the tests' way to many
+// blocks): below `pairs`, or up to `ceiling` where a caller sets one -- and the caller's name in the allocation error
+struct Blocks { uint64_t pairs; const char *knob, *who; uint64_t ceiling = 0; };
+
+// what a caller's allocation callback answers when the device has no room: its driver words the error
+static const int kAllocFailed = -1001;
+
+// The matrix of R, row block by row block, through `counts` (the caller's: its owner decides where a block's memory comes from, and
+// the caller decides how long it lives): the counts of the largest block and -- alloc(largest pairs, most rows of a block, blocks) --
+// whatever else the caller needs per block are allocated once, then every block is compared and handed to block(b, counts).
+// alloc returns MG_OK, kAllocFailed, or an error it has worded itself: it may also queue what has to precede the first compare.
+// Every block has pairs: row 0 of a triangle goes with row 1.
+template <class Alloc, class Block>
+static int matrix_blocks(mg_ctx *ctx, const OutRange &R, const Blocks &how, DevBuf<mg_counts> &counts, Alloc alloc, Block block)
+{
+    if (!R.pairs) return MG_OK;
+    uint64_t max_pairs = how.pairs, largest = 0, most_rows = 0;
+    if (const char *o = ctx_opt(ctx, how.knob))
+        max_pairs = std::min(std::max<uint64_t>(1, strtoull(o, nullptr, 10)), std::max(how.pairs, how.ceiling));
+    const std::vector<RowBlock> blocks = row_blocks(R, max_pairs, &largest);
+    for (const RowBlock &b : blocks) most_rows = std::max(most_rows, b.r2 - b.r);
+    int rc = counts.alloc(largest) == hipSuccess ? alloc(largest, most_rows, (uint64_t)blocks.size()) : kAllocFailed;
+    if (rc != MG_OK) return rc == kAllocFailed ? fail(ctx, MG_ERR_NOMEM, std::string(how.who) + ": device allocation failed") : rc;
+    for (const RowBlock &b : blocks) {
+        rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, R.triangle, counts);
+        if (rc == MG_OK) rc = block(b, counts.p);
+        if (rc != MG_OK) return rc;
+    }
+    return MG_OK;
+}
+
+// A caller's buffer of `capacity` records while blocks fill it: `total` counts on past the capacity (the caller is told the true
+// count), nothing is written past it
+struct Room {
+    uint64_t capacity, total = 0;
+    uint64_t left() const { return total <= capacity ? capacity - total : 0; }
+    template <class T> T *at(T *out) const { return out + std::min(total, capacity); }
+};
+
 // host-output variants: bounded device staging, processed in row blocks
 static int compare_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re,
                         bool triangle, mg_counts *out_host)
@@ -1541,17 +1580,15 @@ static int compare_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols,
     OutRange R;
     int rc = out_range(ctx, rows, cols, rb, re, triangle, &R, 0xFFFFFFFFull);
     if (rc != MG_OK || R.empty()) return rc;
-    uint64_t largest = 0;
-    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 27, &largest);          // 1 GiB of {numer,denom}
     DevBuf<mg_counts> d_out(ctx);
-    if (d_out.alloc(largest) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
-    for (const RowBlock &b : blocks) {
-        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_out)) != MG_OK) return rc;
-        if (b.pairs && (hipMemcpyAsync(out_host + b.before, d_out, b.pairs * sizeof(mg_counts), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                        hipStreamSynchronize(ctx->stream) != hipSuccess))
+    return matrix_blocks(ctx, R, {1ull << 27, "MASHGPU_OUT_BLOCK_PAIRS", "compare"}, d_out,    // 1 GiB of {numer,denom}
+                         [](uint64_t, uint64_t, uint64_t) { return MG_OK; },
+                         [&](const RowBlock &b, const mg_counts *counts) -> int {
+        if (hipMemcpyAsync(out_host + b.before, counts, b.pairs * sizeof(mg_counts), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
             return fail(ctx, MG_ERR_HIP, "compare: D2H copy failed");
-    }
-    return MG_OK;
+        return MG_OK;
+    });
 }
 
 int mg_compare_tri_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, mg_counts *out_host)
@@ -1690,22 +1727,19 @@ static int compare_filter(mg_ctx *ctx, const mg_table *rows, const mg_table *col
     // row blocks of up to 2^30 pairs (8 GiB of counts): large launches keep the
     // tail of the compare kernel short; survivors leave in windows of 2^26 edges
     const uint64_t window = 1ull << 26;
-    uint64_t largest = 0;
-    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 30, &largest);
-    const uint64_t nseg_max = mg::filter_segments(largest);
     DevBuf<mg_counts> d_counts;
     DevBuf<uint4> d_edges;
     DevBuf<uint32_t> d_min, d_segc;
     DevBuf<unsigned long long> d_sego, d_n;
-    if (d_min.alloc(min_numer.size()) != hipSuccess || d_n.alloc(1) != hipSuccess || d_counts.alloc(largest) != hipSuccess ||
-        d_edges.alloc(std::min(largest, window)) != hipSuccess || d_segc.alloc(nseg_max) != hipSuccess || d_sego.alloc(nseg_max) != hipSuccess ||
-        hipMemcpyAsync(d_min, min_numer.data(), min_numer.size() * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return fail(ctx, MG_ERR_NOMEM, "compare filter: device allocation failed");
-    uint64_t total = 0;
-    for (const RowBlock &b : blocks) {
-        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_counts)) != MG_OK) return rc;
+    Room room{capacity};
+    rc = matrix_blocks(ctx, R, {1ull << 30, "MASHGPU_OUT_BLOCK_PAIRS", "compare filter"}, d_counts, [&](uint64_t largest, uint64_t, uint64_t) {
+        const uint64_t nseg_max = mg::filter_segments(largest);
+        return d_min.alloc(min_numer.size()) == hipSuccess && d_n.alloc(1) == hipSuccess && d_edges.alloc(std::min(largest, window)) == hipSuccess &&
+               d_segc.alloc(nseg_max) == hipSuccess && d_sego.alloc(nseg_max) == hipSuccess &&
+               hipMemcpyAsync(d_min, min_numer.data(), min_numer.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? MG_OK : kAllocFailed;
+    }, [&](const RowBlock &b, const mg_counts *counts) -> int {
         mg::FilterArgs f;
-        f.counts = reinterpret_cast<const uint2 *>(d_counts.p);
+        f.counts = reinterpret_cast<const uint2 *>(counts);
         f.min_numer = d_min;
         f.seg_count = d_segc;
         f.seg_off = d_sego;
@@ -1722,19 +1756,21 @@ static int compare_filter(mg_ctx *ctx, const mg_table *rows, const mg_table *col
             hipStreamSynchronize(ctx->stream) != hipSuccess)
             return fail(ctx, MG_ERR_HIP, "compare filter: kernel failed");
         // survivors already rank in reference order; skip the copy once `capacity` is exceeded
-        for (uint64_t lo = 0; lo < n_blk && total + n_blk <= capacity; lo += window) {
+        for (uint64_t lo = 0; lo < n_blk && n_blk <= room.left(); lo += window) {
             f.win_lo = lo;
             f.win_n = std::min<uint64_t>(window, n_blk - lo);
             if (mg::launch_filter_write(f, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(out_host + total + lo, d_edges, f.win_n * sizeof(mg_edge), hipMemcpyDeviceToHost,
+                hipMemcpyAsync(room.at(out_host) + lo, d_edges, f.win_n * sizeof(mg_edge), hipMemcpyDeviceToHost,
                                ctx->stream) != hipSuccess ||
                 hipStreamSynchronize(ctx->stream) != hipSuccess)
                 return fail(ctx, MG_ERR_HIP, "compare filter: compaction failed");
         }
-        total += n_blk;
-    }
-    *count_out = total;
-    if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare filter: more passing pairs than `capacity` (see *count_out)");
+        room.total += n_blk;
+        return MG_OK;
+    });
+    if (rc != MG_OK) return rc;
+    *count_out = room.total;
+    if (room.total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare filter: more passing pairs than `capacity` (see *count_out)");
     return MG_OK;
 }
 
@@ -1764,6 +1800,15 @@ int mg_compare_rect_filter_host(mg_ctx *ctx, const mg_table *ref, const mg_table
 
 static_assert(sizeof(mg_pair) == sizeof(mg::FinishPair) && sizeof(mg_result) == sizeof(mg::FinishEdge), "ABI structs");
 
+// What a finish is given: k and the k-mer space of the distance and p-value formulas, and the two thresholds.  A threshold
+// is on when it lies in [0, 1): one of 1 or more lets every pair through, a negative one means none was asked for.
+struct Cut {
+    int k;
+    double kspace, max_d, max_p;
+    bool d_on() const { return max_d >= 0.0 && max_d < 1.0; }
+    bool filtered() const { return d_on() || (max_p >= 0.0 && max_p < 1.0); }
+};
+
 // What the device finish needs besides the counts: the distance table (host libm, one row per
 // denominator flagged in `seen`, row s always) and the integer form of the distance filter.
 struct FinishTables {
@@ -1773,8 +1818,9 @@ struct FinishTables {
     explicit FinishTables(mg_ctx *c) : d_start(c), d_min(c), d_lut(c) {}
 };
 
-static int build_finish_tables(mg_ctx *ctx, uint32_t s, int k, double max_d, const std::vector<uint32_t> &seen, FinishTables &ft)
+static int build_finish_tables(mg_ctx *ctx, uint32_t s, const Cut &cut, const std::vector<uint32_t> &seen, FinishTables &ft)
 {
+    const int k = cut.k;
     const uint64_t budget = 1ull << 26;                       // doubles (512 MiB): every denominator up to s = 11 583
     std::vector<uint32_t> start((size_t)s + 1, 0xFFFFFFFFu);
     std::vector<double> lut;
@@ -1791,9 +1837,9 @@ static int build_finish_tables(mg_ctx *ctx, uint32_t s, int k, double max_d, con
     HIP_TRY(ctx, ft.d_lut.alloc(lut.size()));
     HIP_TRY(ctx, hipMemcpyAsync(ft.d_start, start.data(), start.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ft.d_lut, lut.data(), lut.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (max_d >= 0 && max_d < 1.0) {
+    if (cut.d_on()) {
         std::vector<uint32_t> mn;
-        build_min_numer(s, k, max_d, mn);
+        build_min_numer(s, k, cut.max_d, mn);
         HIP_TRY(ctx, ft.d_min.alloc(mn.size()));
         HIP_TRY(ctx, hipMemcpyAsync(ft.d_min, mn.data(), mn.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -1804,7 +1850,7 @@ static int build_finish_tables(mg_ctx *ctx, uint32_t s, int k, double max_d, con
 // The FinishArgs fields every device finish fills: `pairs` counts from row first_row on, the tables' lengths, the distance
 // table and filters of `ft`
 static mg::FinishArgs finish_args(const mg_table *rows, const mg_table *cols, uint32_t s, bool triangle, const void *counts, uint64_t pairs,
-                                  uint64_t first_row, const FinishTables &ft, double kmer_space, double max_p)
+                                  uint64_t first_row, const FinishTables &ft, const Cut &cut)
 {
     mg::FinishArgs a{};
     a.counts = reinterpret_cast<const uint2 *>(counts);
@@ -1816,8 +1862,8 @@ static mg::FinishArgs finish_args(const mg_table *rows, const mg_table *cols, ui
     a.min_numer = ft.d_min;
     a.lut_start = ft.d_start;
     a.lut = ft.d_lut;
-    a.kmer_space = kmer_space;
-    a.max_p = max_p;
+    a.kmer_space = cut.kspace;
+    a.max_p = cut.max_p;
     a.s = s;
     a.triangle = triangle ? 1 : 0;
     return a;
@@ -1825,12 +1871,11 @@ static mg::FinishArgs finish_args(const mg_table *rows, const mg_table *cols, ui
 
 // counts (device) of `pairs` pairs starting at row `first_row` -> mg_pair (device)
 static int finish_pairs_dev(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, const mg_counts *counts_dev, uint64_t pairs,
-                            uint64_t first_row, bool triangle, int kmer_size, double kmer_space, double max_d, double max_p,
-                            mg_pair *out_dev, bool *complete_out)
+                            uint64_t first_row, bool triangle, const Cut &cut, mg_pair *out_dev, bool *complete_out)
 {
     if (pairs == 0) return MG_OK;
     if (!rows->lengths || !cols->lengths) return fail(ctx, MG_ERR_INVALID, "finish: the tables carry no lengths");
-    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "finish: bad k-mer size");
+    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "finish: bad k-mer size");
     const uint64_t s64 = std::min(rows->s, cols->s);
     if (s64 > 0xFFFFFFFEull) return fail(ctx, MG_ERR_INVALID, "finish: sketch size too large");
     const uint32_t s = (uint32_t)s64;
@@ -1843,9 +1888,9 @@ static int finish_pairs_dev(mg_ctx *ctx, const mg_table *rows, const mg_table *c
     HIP_TRY(ctx, hipMemcpyAsync(seen.data(), d_seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     FinishTables ft(ctx);
-    int rc = build_finish_tables(ctx, s, kmer_size, max_d, seen, ft);
+    int rc = build_finish_tables(ctx, s, cut, seen, ft);
     if (rc != MG_OK) return rc;
-    mg::FinishArgs a = finish_args(rows, cols, s, triangle, counts_dev, pairs, first_row, ft, kmer_space, max_p);
+    mg::FinishArgs a = finish_args(rows, cols, s, triangle, counts_dev, pairs, first_row, ft, cut);
     a.pairs_out = reinterpret_cast<mg::FinishPair *>(out_dev);
     HIP_TRY(ctx, mg::launch_finish_pairs(a, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the tables are released on return
@@ -1864,8 +1909,8 @@ int mg_finish_tri_dev(mg_ctx *ctx, const mg_table *t, const mg_counts *counts_de
     if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_finish_tri_dev: the table carries no lengths");
     if (row_end > t->n) row_end = t->n;
     if (row_begin >= row_end) return MG_OK;
-    return finish_pairs_dev(ctx, t, t, counts_dev, tri_pairs(row_begin, row_end), row_begin, true, kmer_size, kmer_space,
-                            max_distance, max_p_value, out_dev, nullptr);
+    return finish_pairs_dev(ctx, t, t, counts_dev, tri_pairs(row_begin, row_end), row_begin, true,
+                            Cut{kmer_size, kmer_space, max_distance, max_p_value}, out_dev, nullptr);
 }
 
 int mg_finish_rect_dev(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const mg_counts *counts_dev, uint64_t q_begin,
@@ -1879,35 +1924,32 @@ int mg_finish_rect_dev(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, co
         return fail(ctx, MG_ERR_INVALID, "mg_finish_rect_dev: the tables carry no lengths");
     if (q_end > qry->n) q_end = qry->n;
     if (q_begin >= q_end) return MG_OK;
-    return finish_pairs_dev(ctx, qry, ref, counts_dev, (q_end - q_begin) * ref->n, q_begin, false, kmer_size, kmer_space,
-                            max_distance, max_p_value, out_dev, nullptr);
+    return finish_pairs_dev(ctx, qry, ref, counts_dev, (q_end - q_begin) * ref->n, q_begin, false,
+                            Cut{kmer_size, kmer_space, max_distance, max_p_value}, out_dev, nullptr);
 }
 
 
 // compare + finish on the device, full PairOutput records to the host (32 B per pair), in row blocks
-static int compare_pairs_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle,
-                              int kmer_size, double kmer_space, double max_d, double max_p, mg_pair *out_host)
+static int compare_pairs_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle, const Cut &cut,
+                              mg_pair *out_host)
 {
     OutRange R;
     int rc = out_range(ctx, rows, cols, rb, re, triangle, &R);
     if (rc != MG_OK || !R.pairs) return rc;
-    uint64_t largest = 0;
-    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 26, &largest);         // 2 GiB of records, 512 MiB of counts
     DevBuf<mg_counts> d_counts(ctx);
     DevBuf<mg_pair> d_pairs(ctx);
-    if (d_counts.alloc(largest) != hipSuccess || d_pairs.alloc(largest) != hipSuccess)
-        return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
     std::vector<uint64_t> len_rows, len_cols;                // host copies, only if a block must be patched
-    for (const RowBlock &b : blocks) {
-        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_counts)) != MG_OK) return rc;
+    return matrix_blocks(ctx, R, {1ull << 26, "MASHGPU_OUT_BLOCK_PAIRS", "compare"}, d_counts,   // 2 GiB of records, 512 MiB of counts
+                         [&](uint64_t largest, uint64_t, uint64_t) { return d_pairs.alloc(largest) == hipSuccess ? MG_OK : kAllocFailed; },
+                         [&](const RowBlock &b, const mg_counts *counts) -> int {
         bool complete = true;
-        rc = finish_pairs_dev(ctx, R.rows, R.cols, d_counts, b.pairs, b.r, triangle, kmer_size, kmer_space, max_d, max_p, d_pairs, &complete);
-        if (rc != MG_OK) return rc;
+        const int rcf = finish_pairs_dev(ctx, R.rows, R.cols, counts, b.pairs, b.r, triangle, cut, d_pairs, &complete);
+        if (rcf != MG_OK) return rcf;
         mg_pair *out = out_host + b.before;
         if (hipMemcpyAsync(out, d_pairs, b.pairs * sizeof(mg_pair), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess)
             return fail(ctx, MG_ERR_HIP, "compare: D2H copy failed");
-        if (complete) continue;
+        if (complete) return MG_OK;
         // a denominator beyond the device table's budget left NaN distances: those pairs are finished here
         if (len_rows.empty()) {
             len_rows.resize(R.rows->n);
@@ -1921,11 +1963,11 @@ static int compare_pairs_host(mg_ctx *ctx, const mg_table *rows, const mg_table 
             for (uint64_t j = 0; j < ncol; j++, out++) {
                 if (out->distance == out->distance) continue;
                 const mg_counts c{out->numer, out->denom};
-                finish_one(c, len_rows[i], len_cols[j], kmer_size, kmer_space, max_d, max_p, out);
+                finish_one(c, len_rows[i], len_cols[j], cut.k, cut.kspace, cut.max_d, cut.max_p, out);
             }
         }
-    }
-    return MG_OK;
+        return MG_OK;
+    });
 }
 
 int mg_compare_tri_pairs_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, int kmer_size,
@@ -1935,7 +1977,7 @@ int mg_compare_tri_pairs_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !out_host) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_pairs_host: NULL argument");
     if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_pairs_host: the table carries no lengths");
-    return compare_pairs_host(ctx, t, t, row_begin, row_end, true, kmer_size, kmer_space, max_distance, max_p_value, out_host);
+    return compare_pairs_host(ctx, t, t, row_begin, row_end, true, Cut{kmer_size, kmer_space, max_distance, max_p_value}, out_host);
 }
 
 int mg_compare_rect_pairs_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin, uint64_t q_end,
@@ -1946,7 +1988,7 @@ int mg_compare_rect_pairs_host(mg_ctx *ctx, const mg_table *ref, const mg_table 
     if (!ref || !qry || !out_host) return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_pairs_host: NULL argument");
     if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
         return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_pairs_host: the tables carry no lengths");
-    return compare_pairs_host(ctx, qry, ref, q_begin, q_end, false, kmer_size, kmer_space, max_distance, max_p_value, out_host);
+    return compare_pairs_host(ctx, qry, ref, q_begin, q_end, false, Cut{kmer_size, kmer_space, max_distance, max_p_value}, out_host);
 }
 
 
@@ -1979,6 +2021,7 @@ struct CandLists {
     DevBuf<unsigned char> temp;
     size_t tb = 0;
     explicit CandLists(mg_ctx *c) : rc(c), cnt(c), byrow(c), base(c), temp(c) {}
+    void release() { rc.free(); cnt.free(); byrow.free(); base.free(); temp.free(); }
 };
 
 // The inverted-index engine's job over R as lists (job_lists) instead of a matrix.  *ok false: no lists -- the engine is forced
@@ -2002,27 +2045,93 @@ static int cand_lists(mg_ctx *ctx, const OutRange &R, CandLists &L, bool *ok, Ex
     if (!handled || L.K >= (1ull << 32) || L.rc.alloc(L.K) != hipSuccess || L.cnt.alloc(L.K) != hipSuccess || L.byrow.alloc(nrows) != hipSuccess ||
         L.base.alloc(nrows) != hipSuccess || !extra(L.K, L.tb) || L.temp.alloc(std::max<size_t>(L.tb, 16)) != hipSuccess) {
         (void)hipGetLastError();
+        L.release();                                          // (the fallback needs the memory: whoever gave extra() its buffers frees those)
         return MG_OK;
     }
     *ok = true;
     return job_lists(ctx, job, nrows, R.triangle ? 0u : (uint32_t)R.rb, R.s, L.byrow, L.base, L.temp, L.tb, L.rc, L.cnt);
 }
 
-static const uint64_t kResultsWindow = 1ull << 25;          // survivors leave the device in windows of 2^25 records
-
-// What finish_survivors needs on the device for up to `pairs` entries: pass A's ballots and segments, the survivors' count and
-// denominators, one window of records
-struct SurvivorBufs {
-    DevBuf<unsigned long long> masks, seg_off, n;
+// Pass A of a finish (finish_mark_kernel) over up to `pairs` entries: its ballots and segments, the denominators it flags
+struct PassABufs {
+    DevBuf<unsigned long long> masks, seg_off;
     DevBuf<uint32_t> seg_count, seen;
-    DevBuf<mg::FinishEdge> edges;
-    explicit SurvivorBufs(mg_ctx *owner) : masks(owner), seg_off(owner), n(owner), seg_count(owner), seen(owner), edges(owner) {}
+    explicit PassABufs(mg_ctx *owner) : masks(owner), seg_off(owner), seg_count(owner), seen(owner) {}
     bool alloc(uint64_t pairs, uint32_t s)
     {
         return masks.alloc(mg::finish_mask_words(pairs)) == hipSuccess && seg_count.alloc(mg::finish_segments(pairs)) == hipSuccess &&
-               seg_off.alloc(mg::finish_segments(pairs)) == hipSuccess && n.alloc(1) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess &&
-               edges.alloc(std::min(pairs, kResultsWindow)) == hipSuccess;
+               seg_off.alloc(mg::finish_segments(pairs)) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess;
     }
+    void release() { masks.free(); seg_off.free(); seg_count.free(); seen.free(); }
+    void bind(mg::FinishArgs &f) const
+    {
+        f.masks = masks;
+        f.seg_count = seg_count;
+        f.seg_off = seg_off;
+        f.denom_seen = seen;
+    }
+};
+
+// What a thresholded call keeps on the device for as long as it runs, whichever route serves it: the candidate lists, the finish
+// tables of pass A, the counts of a matrix block (their owner is the caller's choice)
+struct CutBufs {
+    CandLists L;
+    FinishTables fa;
+    DevBuf<mg_counts> counts;
+    CutBufs(mg_ctx *ctx, mg_ctx *counts_owner) : L(ctx), fa(ctx), counts(counts_owner) {}
+};
+
+// The counts of R for a consumer that thresholds them (survivors, unions, edges, the nearest k), by one of two routes:
+//  * lists, if asked for and the index engine gives them (cand_lists): a filter is on, so only pairs that share a hash can pass
+//    (numer = 0 means distance 1 and p-value 1), and those are the engine's candidates -- no matrix is filled, no 8 B per pair read
+//    back.  use() is called once, f over the list (f.list_rc) and L the lists, b the whole range -- or not at all: no candidates.
+//  * the matrix in row blocks (matrix_blocks) otherwise: use() is called per block, L == nullptr.
+// f carries pass A's tables (no extra denominator row), built once: behind the first compare, for building waits.
+// alloc(pairs, rows, blocks, lists) allocates the consumer's buffers for the list or the largest block and answers as matrix_blocks'
+// callback does; on the lists route anything but MG_OK only means no lists.  Lists that fall through leave nothing behind on the
+// device -- the fallback is there for the device that is short of memory --: give_back() frees what alloc(.., true) took.
+template <class Alloc, class GiveBack, class Use>
+static int cut_counts(mg_ctx *ctx, const OutRange &R, const Cut &cut, bool try_lists, const Blocks &how, CutBufs &B, Alloc alloc, GiveBack give_back,
+                      Use use)
+{
+    if (!R.pairs) return MG_OK;
+    int rc = MG_OK;
+    if (try_lists) {
+        bool lists = false;
+        rc = cand_lists(ctx, R, B.L, &lists, [&](uint64_t K, size_t &) { return alloc(K, R.re - R.rb, (uint64_t)1, true) == MG_OK; });
+        if (rc != MG_OK || (lists && B.L.K == 0)) return rc;
+        if (lists) {
+            if ((rc = build_finish_tables(ctx, R.s, cut, {}, B.fa)) != MG_OK) return rc;
+            mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, R.triangle, B.L.cnt, B.L.K, R.rb, B.fa, cut);
+            f.list_rc = B.L.rc;
+            return use(f, RowBlock{R.rb, R.re, B.L.K, 0}, &B.L);
+        }
+        give_back();                                          // (cand_lists has released B.L)
+    }
+    return matrix_blocks(ctx, R, how, B.counts, [&](uint64_t pairs, uint64_t rows, uint64_t blocks) { return alloc(pairs, rows, blocks, false); },
+                         [&](const RowBlock &b, const mg_counts *counts) -> int {
+        if (!B.fa.d_start.p && (rc = build_finish_tables(ctx, R.s, cut, {}, B.fa)) != MG_OK) return rc;
+        return use(finish_args(R.rows, R.cols, R.s, R.triangle, counts, b.pairs, b.r, B.fa, cut), b, nullptr);
+    });
+}
+
+// a denominator beyond the distance table's budget left NaN distances (FinishTables::complete): those are computed here
+static void patch_nan_distances(mg_result *r, uint64_t n, int k)
+{
+    for (uint64_t i = 0; i < n; i++)
+        if (r[i].distance != r[i].distance) r[i].distance = mg::mash_distance(r[i].numer, r[i].denom, k);
+}
+
+static const uint64_t kResultsWindow = 1ull << 25;          // survivors leave the device in windows of 2^25 records
+
+// What finish_survivors needs on the device for up to `pairs` entries: pass A's, the survivors' count, one window of records
+struct SurvivorBufs {
+    PassABufs a;
+    DevBuf<unsigned long long> n;
+    DevBuf<mg::FinishEdge> edges;
+    explicit SurvivorBufs(mg_ctx *owner) : a(owner), n(owner), edges(owner) {}
+    bool alloc(uint64_t pairs, uint32_t s) { return a.alloc(pairs, s) && n.alloc(1) == hipSuccess && edges.alloc(std::min(pairs, kResultsWindow)) == hipSuccess; }
+    void release() { a.release(); n.free(); edges.free(); }
 };
 
 // The two finish passes over f's counts -- one matrix block, or the candidate list (f.list_rc).  Pass A needs the distance filter
@@ -2030,25 +2139,21 @@ struct SurvivorBufs {
 // denominators; only then are the distance rows of exactly those known, so the tables are built a second time for pass B, which
 // writes the survivors in reference order.
 // *n_out: the survivors, always; they are written to out_host only when they fit `room`.
-static int finish_survivors(mg_ctx *ctx, mg::FinishArgs f, const SurvivorBufs &b, int kmer_size, double max_d, uint64_t room,
-                            mg_result *out_host, uint64_t *n_out)
+static int finish_survivors(mg_ctx *ctx, mg::FinishArgs f, const SurvivorBufs &b, const Cut &cut, uint64_t room, mg_result *out_host, uint64_t *n_out)
 {
-    f.masks = b.masks;
-    f.seg_count = b.seg_count;
-    f.seg_off = b.seg_off;
-    f.denom_seen = b.seen;
+    b.a.bind(f);
     f.edges = b.edges;
     std::vector<uint32_t> seen((size_t)f.s + 1);
     unsigned long long n = 0;
-    HIP_TRY(ctx, hipMemsetAsync(b.seen, 0, seen.size() * 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.a.seen, 0, seen.size() * 4, ctx->stream));
     HIP_TRY(ctx, mg::launch_finish_mark(f, b.n, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&n, b.n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(seen.data(), b.seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(seen.data(), b.a.seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = n;
     if (n == 0 || n > room) return MG_OK;
     FinishTables fb(ctx);
-    const int rc = build_finish_tables(ctx, f.s, kmer_size, max_d, seen, fb);
+    const int rc = build_finish_tables(ctx, f.s, cut, seen, fb);
     if (rc != MG_OK) return rc;
     f.lut_start = fb.d_start;
     f.lut = fb.d_lut;
@@ -2060,64 +2165,34 @@ static int finish_survivors(mg_ctx *ctx, mg::FinishArgs f, const SurvivorBufs &b
         HIP_TRY(ctx, hipMemcpyAsync(out_host + lo, b.edges, f.win_n * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    if (!fb.complete)                                         // a denominator beyond the table's budget left NaN distances
-        for (uint64_t i = 0; i < n; i++) {
-            mg_result &e = out_host[i];
-            if (e.distance != e.distance) e.distance = mg::mash_distance(e.numer, e.denom, kmer_size);
-        }
+    if (!fb.complete) patch_nan_distances(out_host, n, cut.k);
     return MG_OK;
 }
 
 // compare + both filters + compaction on the device: survivors only, as full records, in reference order
-static int compare_results(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle,
-                           int kmer_size, double kmer_space, double max_d, double max_p, mg_result *out_host, uint64_t capacity,
-                           uint64_t *count_out)
+static int compare_results(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle, const Cut &cut,
+                           mg_result *out_host, uint64_t capacity, uint64_t *count_out)
 {
     *count_out = 0;
     OutRange R;
     int rc = out_range(ctx, rows, cols, rb, re, triangle, &R);
     if (rc != MG_OK || R.empty()) return rc;
-    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
-    if (!R.pairs) return MG_OK;
-    // ---- a filter is on: only pairs that share a hash can pass (numer = 0 means distance 1 and p-value 1), and
-    // those are the inverted-index engine's candidates -- no matrix is filled, no 8 B per pair read back by
-    // the filter pass: discover + merge, the candidates put into reference order, the same two finish passes
-    // over that list.
-    if ((max_d >= 0.0 && max_d < 1.0) || (max_p >= 0.0 && max_p < 1.0)) {
-        CandLists L(ctx);
-        SurvivorBufs sb(ctx);
-        bool lists = false;
-        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return sb.alloc(K, R.s); });
-        if (rc != MG_OK || (lists && L.K == 0)) return rc;
-        if (lists) {
-            FinishTables fa(ctx);
-            if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
-            mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, triangle, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
-            f.list_rc = L.rc;
-            rc = finish_survivors(ctx, f, sb, kmer_size, max_d, capacity, out_host, count_out);
-            if (rc != MG_OK) return rc;
-            if (*count_out > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
-            return MG_OK;
-        }
-    }
-    uint64_t largest = 0;
-    const std::vector<RowBlock> blocks = row_blocks(R, 1ull << 30, &largest);
-    DevBuf<mg_counts> d_counts;
-    SurvivorBufs sb(nullptr);
-    if (d_counts.alloc(largest) != hipSuccess || !sb.alloc(largest, R.s)) return fail(ctx, MG_ERR_NOMEM, "compare: device allocation failed");
-    FinishTables fa(ctx);
-    uint64_t total = 0;
-    for (const RowBlock &b : blocks) {
-        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, triangle, d_counts)) != MG_OK) return rc;
-        if (&b == &blocks.front() && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;  // (once: behind the first compare)
+    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    CutBufs bufs(ctx, nullptr);
+    SurvivorBufs of_list(ctx), of_block(nullptr);             // (a block's buffers, 8 GiB and more, stay out of the context's cache)
+    Room room{capacity};
+    rc = cut_counts(ctx, R, cut, cut.filtered(), {1ull << 30, "MASHGPU_OUT_BLOCK_PAIRS", "compare"}, bufs,
+                    [&](uint64_t pairs, uint64_t, uint64_t, bool lists) { return (lists ? of_list : of_block).alloc(pairs, R.s) ? MG_OK : kAllocFailed; },
+                    [&] { of_list.release(); },
+                    [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
         uint64_t n = 0;
-        rc = finish_survivors(ctx, finish_args(R.rows, R.cols, R.s, triangle, d_counts, b.pairs, b.r, fa, kmer_space, max_p), sb, kmer_size, max_d,
-                              total <= capacity ? capacity - total : 0, out_host + total, &n);
-        if (rc != MG_OK) return rc;
-        total += n;
-    }
-    *count_out = total;
-    if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
+        const int rcf = finish_survivors(ctx, f, L ? of_list : of_block, cut, room.left(), room.at(out_host), &n);
+        room.total += n;
+        return rcf;
+    });
+    if (rc != MG_OK) return rc;
+    *count_out = room.total;
+    if (room.total > capacity) return fail(ctx, MG_ERR_NOMEM, "compare: more passing pairs than `capacity` (see *count_out)");
     return MG_OK;
 }
 
@@ -2210,7 +2285,7 @@ int mg_compare_tri_results_host(mg_ctx *ctx, const mg_table *t, uint64_t row_beg
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !count_out || (!out_host && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_results_host: NULL argument");
     if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_results_host: the table carries no lengths");
-    return compare_results(ctx, t, t, row_begin, row_end, true, kmer_size, kmer_space, max_distance, max_p_value, out_host, capacity, count_out);
+    return compare_results(ctx, t, t, row_begin, row_end, true, Cut{kmer_size, kmer_space, max_distance, max_p_value}, out_host, capacity, count_out);
 }
 
 int mg_compare_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin, uint64_t q_end,
@@ -2223,142 +2298,88 @@ int mg_compare_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_tabl
         return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_results_host: NULL argument");
     if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
         return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_results_host: the tables carry no lengths");
-    return compare_results(ctx, qry, ref, q_begin, q_end, false, kmer_size, kmer_space, max_distance, max_p_value, out_host, capacity, count_out);
+    return compare_results(ctx, qry, ref, q_begin, q_end, false, Cut{kmer_size, kmer_space, max_distance, max_p_value}, out_host, capacity, count_out);
 }
 
 
 /* ------------------------------------------------- single-linkage clusters of the thresholded triangle (cluster.hip) */
 
-// What one mark + union needs on the device for up to `pairs` entries: pass A's ballots and segments, the denominators it flags
-struct ClusterBufs {
-    DevBuf<unsigned long long> masks, seg_off;
-    DevBuf<uint32_t> seg_count, seen;
-    explicit ClusterBufs(mg_ctx *owner) : masks(owner), seg_off(owner), seg_count(owner), seen(owner) {}
-    bool alloc(uint64_t pairs, uint32_t s)
-    {
-        return masks.alloc(mg::finish_mask_words(pairs)) == hipSuccess && seg_count.alloc(mg::finish_segments(pairs)) == hipSuccess &&
-               seg_off.alloc(mg::finish_segments(pairs)) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess;
-    }
-};
-
-// finish_survivors' sibling: pass A over f's counts -- one matrix block, or the candidate list (f.list_rc) -- and the union of
-// every pair it marks.  No pass B, no distance table, no record, no wait: pass A's count goes to *n_dev (device).
-static int cluster_survivors(mg_ctx *ctx, mg::FinishArgs f, const ClusterBufs &b, uint32_t *parent, uint32_t n, unsigned long long *n_dev)
-{
-    f.masks = b.masks;
-    f.seg_count = b.seg_count;
-    f.seg_off = b.seg_off;
-    f.denom_seen = b.seen;
-    HIP_TRY(ctx, mg::launch_finish_mark(f, n_dev, ctx->stream));
-    HIP_TRY(ctx, mg::launch_cluster_union(f, parent, n, ctx->stream));
-    return MG_OK;
-}
-
-// The whole triangle of t: compare_results' two routes, with cluster_survivors in finish_survivors' place, then one label launch
-static int cluster_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_d, double max_p, uint32_t *label_out,
-                       bool label_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+// The whole triangle of t: pass A over its thresholded counts (cut_counts) -- the candidate list, or block after block of the matrix --
+// and the union of every pair it marks into `parent`, which lives across the blocks; then one label launch.  No pass B, no distance
+// table, no record, and no wait before finish's: pass A's counts stay on the device until then.
+static int cluster_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out,
+                       uint64_t *n_edges_out)
 {
     *n_clusters_out = 0;
     *n_edges_out = 0;
     OutRange R;
     int rc = out_range(ctx, t, t, 0, t->n, true, &R);
     if (rc != MG_OK || R.empty()) return rc;
-    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
     if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
     const uint32_t n = (uint32_t)t->n;
     DevBuf<uint32_t> parent(ctx), label(ctx);
-    DevBuf<unsigned long long> d_n(ctx);                      // [0]: the clusters, [1 + b]: pass A's count of block b
+    DevBuf<unsigned long long> d_n(ctx);                      // [0]: the clusters, [1 + b]: pass A's count of block b (the list: block 0)
     HIP_TRY(ctx, parent.alloc(n));
     if (!label_on_device) HIP_TRY(ctx, label.alloc(n));
     uint32_t *d_label = label_on_device ? label_out : label.p;
     HIP_TRY(ctx, mg::launch_cluster_init(parent, n, ctx->stream));
+    CutBufs bufs(ctx, ctx);
+    PassABufs pa(ctx);
     uint64_t nblocks = 0;
-    // finish: the labels, the roots' number and pass A's counts, behind every union queued so far
-    auto finish = [&]() -> int {
-        std::vector<unsigned long long> h(1 + nblocks);
-        HIP_TRY(ctx, mg::launch_cluster_label(parent, n, d_label, d_n, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_n, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (!label_on_device) HIP_TRY(ctx, hipMemcpyAsync(label_out, d_label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        *n_clusters_out = h[0];
-        for (uint64_t b = 0; b < nblocks; b++) *n_edges_out += h[1 + b];
+    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
+                    [&](uint64_t pairs, uint64_t, uint64_t blocks, bool lists) -> int {
+        if (!pa.alloc(pairs, R.s) || d_n.alloc(1 + blocks) != hipSuccess) return kAllocFailed;
+        if (lists) return MG_OK;                              // (the flags are cleared once the list's tables stand: below)
+        HIP_TRY(ctx, hipMemsetAsync(d_n, 0, (1 + blocks) * 8, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
         return MG_OK;
-    };
-    if (!R.pairs) {                                           // (one row)
-        HIP_TRY(ctx, d_n.alloc(1));
-        return finish();
-    }
-    {   // ---- the inverted-index engine's candidates as one list (compare_results): one mark, one union
-        CandLists L(ctx);
-        ClusterBufs cb(ctx);
-        bool lists = false;
-        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return cb.alloc(K, R.s); });
-        if (rc != MG_OK) return rc;
-        if (lists) {
-            HIP_TRY(ctx, d_n.alloc(2));
-            if (L.K) {
-                FinishTables fa(ctx);
-                if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
-                mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, true, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
-                f.list_rc = L.rc;
-                HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-                if ((rc = cluster_survivors(ctx, f, cb, parent, n, d_n + 1)) != MG_OK) return rc;
-                nblocks = 1;
-                return finish();                              // (fa and the lists are released behind finish's wait)
-            }
-            return finish();
-        }
-    }
-    // ---- the matrix in row blocks: a mark and a union per block, `parent` persistent across them
-    uint64_t block_pairs = 1ull << 30;
-    if (const char *o = ctx_opt(ctx, "MASHGPU_CLUSTER_BLOCK_PAIRS")) block_pairs = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
-    uint64_t largest = 0;
-    const std::vector<RowBlock> blocks = row_blocks(R, std::min<uint64_t>(block_pairs, 1ull << 30), &largest);
-    DevBuf<mg_counts> d_counts(ctx);
-    ClusterBufs cb(ctx);
-    if (d_counts.alloc(largest) != hipSuccess || !cb.alloc(largest, R.s) || d_n.alloc(1 + blocks.size()) != hipSuccess)
-        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
-    HIP_TRY(ctx, hipMemsetAsync(d_n, 0, (1 + blocks.size()) * 8, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-    FinishTables fa(ctx);
-    for (const RowBlock &b : blocks) {
-        nblocks++;
-        if (!b.pairs) continue;                               // (row 0)
-        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, true, d_counts)) != MG_OK) return rc;
-        if (!fa.d_start.p && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;  // (once: behind the first compare)
-        rc = cluster_survivors(ctx, finish_args(R.rows, R.cols, R.s, true, d_counts, b.pairs, b.r, fa, kmer_space, max_p), cb, parent, n, d_n + nblocks);
-        if (rc != MG_OK) return rc;
-    }
-    return finish();
+    },
+                    [&] { pa.release(); },
+                    [&](mg::FinishArgs f, const RowBlock &, const CandLists *L) -> int {
+        if (L) HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+        pa.bind(f);
+        HIP_TRY(ctx, mg::launch_finish_mark(f, d_n + ++nblocks, ctx->stream));
+        HIP_TRY(ctx, mg::launch_cluster_union(f, parent, n, ctx->stream));
+        return MG_OK;
+    });
+    if (rc != MG_OK) return rc;
+    if (!nblocks) HIP_TRY(ctx, d_n.alloc(1));                 // (one row, or no candidates)
+    // the labels, the roots' number and pass A's counts, behind every union queued so far
+    std::vector<unsigned long long> h(1 + nblocks);
+    HIP_TRY(ctx, mg::launch_cluster_label(parent, n, d_label, d_n, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_n, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!label_on_device) HIP_TRY(ctx, hipMemcpyAsync(label_out, d_label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (bufs and pa are released behind this wait)
+    *n_clusters_out = h[0];
+    for (uint64_t b = 0; b < nblocks; b++) *n_edges_out += h[1 + b];
+    return MG_OK;
 }
 
-static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_d, double max_p, uint32_t *rep_out,
-                              bool rep_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out);
+static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
+                              uint64_t *n_edges_out);
 
-static int cluster_entry(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                         uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out, const char *who,
-                         bool greedy = false)
+static int cluster_entry(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out,
+                         uint64_t *n_edges_out, const char *who, bool greedy = false)
 {
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !n_clusters_out || !n_edges_out || (!label_out && t->n)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
     if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
-    if (!((max_distance >= 0.0 && max_distance < 1.0) || (max_p_value >= 0.0 && max_p_value < 1.0)))
-        return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
-    return (greedy ? cluster_greedy_tri : cluster_tri)(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out, label_on_device,
-                                                       n_clusters_out, n_edges_out);
+    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
+    return (greedy ? cluster_greedy_tri : cluster_tri)(ctx, t, cut, label_out, label_on_device, n_clusters_out, n_edges_out);
 }
 
 int mg_cluster_tri_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
                         uint32_t *label_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
 {
-    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out_host, false, n_clusters_out, n_edges_out, "mg_cluster_tri_host");
+    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_host, false, n_clusters_out, n_edges_out, "mg_cluster_tri_host");
 }
 
 int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
                        uint32_t *label_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
 {
-    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, label_out_dev, true, n_clusters_out, n_edges_out, "mg_cluster_tri_dev");
+    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_dev, true, n_clusters_out, n_edges_out, "mg_cluster_tri_dev");
 }
 
 
@@ -2381,15 +2402,12 @@ struct GreedyEdges {
         HIP_TRY(ctx, hipMemsetAsync(ctl, 0, 24, ctx->stream));
         return MG_OK;
     }
-    // cluster_survivors' sibling: pass A over f's counts, its marked pairs appended; waits for the block's figures and, if the
+    // Pass A over f's counts, its marked pairs appended; waits for the block's figures and, if the
     // list was too short for them, regrows it (the pairs of earlier blocks copied over) and appends the block again -- pass A's
     // ballots are still there
-    int append(mg::FinishArgs f, const ClusterBufs &b, uint32_t n)
+    int append(mg::FinishArgs f, const PassABufs &b, uint32_t n)
     {
-        f.masks = b.masks;
-        f.seg_count = b.seg_count;
-        f.seg_off = b.seg_off;
-        f.denom_seen = b.seen;
+        b.bind(f);
         unsigned long long h[3] = {0, 0, 0};
         HIP_TRY(ctx, mg::launch_finish_mark(f, ctl + 1, ctx->stream));
         for (int attempt = 0;; attempt++) {
@@ -2419,10 +2437,10 @@ struct GreedyEdges {
     }
 };
 
-// The whole triangle of t: cluster_tri's two routes with GreedyEdges::append in cluster_survivors' place, then the rounds in
-// batches (one wait per batch: the rows each of its rounds left open), then the assignment
-static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_d, double max_p, uint32_t *rep_out,
-                              bool rep_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+// The whole triangle of t: cluster_tri's way to the thresholded counts (cut_counts) with GreedyEdges::append as their consumer -- one
+// wait per block --, then the rounds in batches (one wait per batch: the rows each of its rounds left open), then the assignment
+static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
+                              uint64_t *n_edges_out)
 {
     *n_clusters_out = 0;
     *n_edges_out = 0;
@@ -2430,7 +2448,7 @@ static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, dou
     OutRange R;
     int rc = out_range(ctx, t, t, 0, t->n, true, &R);
     if (rc != MG_OK || R.empty()) return rc;
-    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
     if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
     const uint32_t n = (uint32_t)t->n;
     uint64_t edge_cap = 1ull << 23;                           // 64 MB; the list doubles, or grows to what a block needs, when it is short
@@ -2471,57 +2489,39 @@ static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, int kmer_size, dou
         ctx->greedy_edge_cap = E.cap;
         return MG_OK;
     };
-    if (!R.pairs) return finish();                            // (one row)
-    {   // ---- the inverted-index engine's candidates as one list (compare_results): one mark, one append
-        CandLists L(ctx);
-        ClusterBufs cb(ctx);
-        bool lists = false;
-        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return cb.alloc(K, R.s); });
-        if (rc != MG_OK) return rc;
-        if (lists) {
-            if (L.K) {
-                FinishTables fa(ctx);
-                if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
-                mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, true, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
-                f.list_rc = L.rc;
-                if ((rc = E.init(std::min<uint64_t>(edge_cap, L.K))) != MG_OK) return rc;
-                HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-                if ((rc = E.append(f, cb, n)) != MG_OK) return rc;
-            }
-            return finish();
-        }
-    }
-    // ---- the matrix in row blocks: a mark and an append per block, the list persistent across them
-    uint64_t block_pairs = 1ull << 30;
-    if (const char *o = ctx_opt(ctx, "MASHGPU_CLUSTER_BLOCK_PAIRS")) block_pairs = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
-    uint64_t largest = 0;
-    const std::vector<RowBlock> blocks = row_blocks(R, std::min<uint64_t>(block_pairs, 1ull << 30), &largest);
-    DevBuf<mg_counts> d_counts(ctx);
-    ClusterBufs cb(ctx);
-    if (d_counts.alloc(largest) != hipSuccess || !cb.alloc(largest, R.s)) return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
-    if ((rc = E.init(std::min<uint64_t>(edge_cap, R.pairs))) != MG_OK) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(cb.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-    FinishTables fa(ctx);
-    for (const RowBlock &b : blocks) {
-        if (!b.pairs) continue;                               // (row 0)
-        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, true, d_counts)) != MG_OK) return rc;
-        if (!fa.d_start.p && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;  // (once: behind the first compare)
-        if ((rc = E.append(finish_args(R.rows, R.cols, R.s, true, d_counts, b.pairs, b.r, fa, kmer_space, max_p), cb, n)) != MG_OK) return rc;
-    }
-    return finish();
+    CutBufs bufs(ctx, ctx);
+    PassABufs pa(ctx);
+    // the list starts no longer than the pairs its route can bring: the candidates, or the whole triangle
+    auto begin = [&](uint64_t most_edges) -> int {
+        const int rci = E.init(std::min<uint64_t>(edge_cap, most_edges));
+        if (rci != MG_OK) return rci;
+        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+        return MG_OK;
+    };
+    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
+                    [&](uint64_t pairs, uint64_t, uint64_t, bool lists) -> int {
+        if (!pa.alloc(pairs, R.s)) return kAllocFailed;
+        return lists ? MG_OK : begin(R.pairs);                // (the list route begins once its tables stand: below)
+    },
+                    [&] { pa.release(); },
+                    [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
+        const int rcb = L ? begin(L->K) : MG_OK;
+        return rcb != MG_OK ? rcb : E.append(f, pa, n);
+    });
+    return rc != MG_OK ? rc : finish();
 }
 
 int mg_cluster_tri_greedy_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
                                uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
 {
-    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, rep_out_host, false, n_clusters_out, n_edges_out,
+    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_host, false, n_clusters_out, n_edges_out,
                          "mg_cluster_tri_greedy_host", true);
 }
 
 int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
                               uint32_t *rep_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
 {
-    return cluster_entry(ctx, t, kmer_size, kmer_space, max_distance, max_p_value, rep_out_dev, true, n_clusters_out, n_edges_out,
+    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_dev, true, n_clusters_out, n_edges_out,
                          "mg_cluster_tri_greedy_dev", true);
 }
 
@@ -2544,18 +2544,18 @@ static_assert(MG_TOPK_MAX == mg::TOPK_MAX, "MG_TOPK_MAX");
 // What one selection needs on the device: pass A's ballots when a filter is on (eligibility), the rows' lists as indices into
 // the counts, their lengths and offsets, the denominators they carry, the records.
 struct TopkBufs {
-    DevBuf<uint32_t> sel, row_n, seen, seg_count;
-    DevBuf<unsigned long long> row_off, total, masks, seg_off;
+    PassABufs a;                                              // (without a filter: its denominator flags alone)
+    DevBuf<uint32_t> sel, row_n;
+    DevBuf<unsigned long long> row_off, total;
     DevBuf<mg::FinishEdge> edges;
-    explicit TopkBufs(mg_ctx *c) : sel(c), row_n(c), seen(c), seg_count(c), row_off(c), total(c), masks(c), seg_off(c), edges(c) {}
+    explicit TopkBufs(mg_ctx *c) : a(c), sel(c), row_n(c), row_off(c), total(c), edges(c) {}
     bool alloc(uint64_t nrows, uint32_t k, uint32_t s, uint64_t pairs, bool filtered)
     {
-        if (filtered && (masks.alloc(mg::finish_mask_words(pairs)) != hipSuccess || seg_count.alloc(mg::finish_segments(pairs)) != hipSuccess ||
-                         seg_off.alloc(mg::finish_segments(pairs)) != hipSuccess))
-            return false;
-        return sel.alloc(nrows * k) == hipSuccess && row_n.alloc(nrows) == hipSuccess && row_off.alloc(nrows) == hipSuccess &&
-               total.alloc(2) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess && edges.alloc(nrows * k) == hipSuccess;
+        return (filtered ? a.alloc(pairs, s) : a.seen.alloc((uint64_t)s + 1) == hipSuccess) && sel.alloc(nrows * k) == hipSuccess &&
+               row_n.alloc(nrows) == hipSuccess && row_off.alloc(nrows) == hipSuccess && total.alloc(2) == hipSuccess &&
+               edges.alloc(nrows * k) == hipSuccess;
     }
+    void release() { a.release(); sel.free(); row_n.free(); row_off.free(); total.free(); edges.free(); }
 };
 
 // One selection over f's counts -- a block of the matrix (seg_base == nullptr) or the candidate lists (f.list_rc, seg_base / seg_cnt):
@@ -2563,20 +2563,18 @@ struct TopkBufs {
 // finish_survivors), the rows' best k, and only then -- the denominators of the selected are known -- the distance table and the
 // records.  *n_out: the records of these rows, always; they are written to out_host only when they fit `room`.
 static int topk_select_finish(mg_ctx *ctx, mg::FinishArgs f, const TopkBufs &b, const uint32_t *seg_base, const uint32_t *seg_cnt, uint32_t nrows,
-                              uint32_t k, bool filtered, int kmer_size, double max_d, uint64_t room, mg_result *out_host, uint64_t *n_out)
+                              uint32_t k, const Cut &cut, uint64_t room, mg_result *out_host, uint64_t *n_out)
 {
     *n_out = 0;
     if (!nrows || !f.pairs) return MG_OK;
+    const bool filtered = cut.filtered();
     if (filtered) {
-        f.masks = b.masks;
-        f.seg_count = b.seg_count;
-        f.seg_off = b.seg_off;
-        f.denom_seen = b.seen;
+        b.a.bind(f);
         HIP_TRY(ctx, mg::launch_finish_mark(f, b.total + 1, ctx->stream));
     }
     mg::TopkArgs a{};
     a.counts = f.counts;
-    a.masks = filtered ? b.masks.p : nullptr;
+    a.masks = filtered ? b.a.masks.p : nullptr;
     a.seg_base = seg_base;
     a.seg_cnt = seg_cnt;
     a.ncols = (uint32_t)f.ncols;
@@ -2584,87 +2582,66 @@ static int topk_select_finish(mg_ctx *ctx, mg::FinishArgs f, const TopkBufs &b, 
     a.k = k;
     a.sel = b.sel;
     a.row_n = b.row_n;
-    a.denom_seen = b.seen;
+    a.denom_seen = b.a.seen;
     a.s = f.s;
     std::vector<uint32_t> seen((size_t)f.s + 1);
     unsigned long long n = 0;
-    HIP_TRY(ctx, hipMemsetAsync(b.seen, 0, seen.size() * 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.a.seen, 0, seen.size() * 4, ctx->stream));
     HIP_TRY(ctx, mg::launch_topk_select(a, ctx->stream));
     HIP_TRY(ctx, mg::launch_topk_scan(b.row_n, b.row_off, nrows, b.total, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&n, b.total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(seen.data(), b.seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(seen.data(), b.a.seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = n;
     if (n == 0 || n > room) return MG_OK;
     FinishTables fb(ctx);
-    const int rc = build_finish_tables(ctx, f.s, kmer_size, max_d, seen, fb);
+    const int rc = build_finish_tables(ctx, f.s, cut, seen, fb);
     if (rc != MG_OK) return rc;
     f.lut_start = fb.d_start;
     f.lut = fb.d_lut;
     HIP_TRY(ctx, mg::launch_topk_finish(f, a, b.row_off, b.edges, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_host, b.edges, n * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (!fb.complete)                                         // a denominator beyond the table's budget left NaN distances
-        for (uint64_t i = 0; i < n; i++) {
-            mg_result &e = out_host[i];
-            if (e.distance != e.distance) e.distance = mg::mash_distance(e.numer, e.denom, kmer_size);
-        }
+    if (!fb.complete) patch_nan_distances(out_host, n, cut.k);
     return MG_OK;
 }
 
 // queries [rb, re): few enough that rows * k records fit the device buffers
-static int topk_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, int kmer_size, double kmer_space,
-                      double max_d, double max_p, uint32_t k, uint64_t room, mg_result *out_host, uint64_t *n_out)
+static int topk_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, const Cut &cut, uint32_t k, uint64_t capacity,
+                      mg_result *out_host, uint64_t *n_out)
 {
     *n_out = 0;
     OutRange R;
     int rc = out_range(ctx, rows, cols, rb, re, false, &R);
     if (rc != MG_OK || !R.pairs) return rc;
-    const bool filtered = (max_d >= 0.0 && max_d < 1.0) || (max_p >= 0.0 && max_p < 1.0);
-    const uint32_t nrows = (uint32_t)(R.re - R.rb);
+    // A row's positions and a block's indices are 32-bit, and the streaming loop steps past the row's end by up to one chunk.  A block
+    // of the matrix is larger than that only as one row of that many references -- and tables of 2^31 rows and more have no lists
+    // (SparseJobRun::open_index) --, so this is said before anything is allocated.
+    const uint64_t most = 0xFFFFFFFFull - mg::TOPK_CHUNK;
+    if (R.cols->n > most) return fail(ctx, MG_ERR_UNSUPPORTED, "top-k: more than 2^32 - 1025 references");
+    // Lists only with a filter on, a row's candidates in column order.  With the filters off a row is completed by its numer = 0
+    // pairs in index order, and a candidate can itself have numer = 0 (a hash shared behind the first s union elements): it ties with
+    // the pairs that are no candidates and has to fall into index order among them, which only the full row gives -- those jobs take
+    // the matrix: row blocks of counts (never of records), a workgroup per row streams its nref x 8 B once.  512 MiB of counts a
+    // block; the option may also raise that, to the 2^31 pairs the lists' 32-bit indices into a block allow.
+    const bool filtered = cut.filtered();
     TopkBufs tb(ctx);
-    // ---- a filter is on: only pairs that share a hash can pass, and those are the inverted-index engine's candidates, a row's in
-    // column order (compare_results).  With the filters off a row is completed by its numer = 0 pairs in index order, and a
-    // candidate can itself have numer = 0 (a hash shared behind the first s union elements): it ties with the pairs that are
-    // no candidates and has to fall into index order among them, which only the full row gives -- those jobs take the matrix route.
-    if (filtered) {
-        CandLists L(ctx);
-        bool lists = false;
-        rc = cand_lists(ctx, R, L, &lists, [&](uint64_t K, size_t &) { return K <= 0xFFFFFFFFull - mg::TOPK_CHUNK && tb.alloc(nrows, k, R.s, K, true); });
-        if (rc != MG_OK || (lists && L.K == 0)) return rc;
-        if (lists) {
-            FinishTables fa(ctx);
-            if ((rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
-            mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, false, L.cnt, L.K, R.rb, fa, kmer_space, max_p);
-            f.list_rc = L.rc;
-            return topk_select_finish(ctx, f, tb, L.base, L.byrow, nrows, k, true, kmer_size, max_d, room, out_host, n_out);
-        }
-    }
-    // ---- the matrix in row blocks of counts (never as records): a workgroup per row streams its nref x 8 B once
-    uint64_t block_pairs = 1ull << 26;                       // 512 MiB of counts
-    if (const char *o = ctx_opt(ctx, "MASHGPU_TOPK_BLOCK_PAIRS")) block_pairs = std::max<uint64_t>(1, strtoull(o, nullptr, 10));
-    block_pairs = std::min<uint64_t>(block_pairs, 1ull << 31);              // (the lists hold 32-bit indices into a block)
-    uint64_t largest = 0, most_rows = 0;
-    const std::vector<RowBlock> blocks = row_blocks(R, block_pairs, &largest);
-    // (a row's positions and a block's indices are 32-bit, and the streaming loop steps past the row's end by up to one chunk)
-    if (largest > 0xFFFFFFFFull - mg::TOPK_CHUNK) return fail(ctx, MG_ERR_UNSUPPORTED, "top-k: more than 2^32 - 1025 references");
-    for (const RowBlock &b : blocks) most_rows = std::max(most_rows, b.r2 - b.r);
-    DevBuf<mg_counts> d_counts(ctx);
-    if (d_counts.alloc(largest) != hipSuccess || !tb.alloc(most_rows, k, R.s, largest, filtered))
-        return fail(ctx, MG_ERR_NOMEM, "top-k: device allocation failed");
-    FinishTables fa(ctx);
-    uint64_t total = 0;
-    for (const RowBlock &b : blocks) {
-        if ((rc = run_compare(ctx, R.rows, R.cols, b.r, b.r2, false, d_counts)) != MG_OK) return rc;
-        if (&b == &blocks.front() && (rc = build_finish_tables(ctx, R.s, kmer_size, max_d, {}, fa)) != MG_OK) return rc;
+    CutBufs bufs(ctx, ctx);
+    Room room{capacity};
+    rc = cut_counts(ctx, R, cut, filtered, {1ull << 26, "MASHGPU_TOPK_BLOCK_PAIRS", "top-k", 1ull << 31}, bufs,
+                    [&](uint64_t pairs, uint64_t nrows, uint64_t, bool lists) {        // (more candidates than a 32-bit index reaches: no lists)
+        return (!lists || pairs <= most) && tb.alloc(nrows, k, R.s, pairs, filtered) ? MG_OK : kAllocFailed;
+    },
+                    [&] { tb.release(); },
+                    [&](const mg::FinishArgs &f, const RowBlock &b, const CandLists *L) -> int {
         uint64_t n = 0;
-        rc = topk_select_finish(ctx, finish_args(R.rows, R.cols, R.s, false, d_counts, b.pairs, b.r, fa, kmer_space, max_p), tb, nullptr, nullptr,
-                                (uint32_t)(b.r2 - b.r), k, filtered, kmer_size, max_d, total <= room ? room - total : 0, out_host + std::min(total, room), &n);
-        if (rc != MG_OK) return rc;
-        total += n;
-    }
-    *n_out = total;
-    return MG_OK;
+        const int rcf = topk_select_finish(ctx, f, tb, L ? L->base.p : nullptr, L ? L->byrow.p : nullptr, (uint32_t)(b.r2 - b.r), k, cut, room.left(),
+                                           room.at(out_host), &n);
+        room.total += n;
+        return rcf;
+    });
+    *n_out = room.total;
+    return rc;
 }
 
 int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin, uint64_t q_end, int kmer_size,
@@ -2684,15 +2661,15 @@ int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *
     if (q_begin >= q_end || ref->n == 0) return MG_OK;
     k = (uint32_t)std::min<uint64_t>(k, ref->n);
     const uint64_t step = std::max<uint64_t>(1, (1ull << 24) / k);          // at most 2^24 records (512 MiB) on the device at a time
-    uint64_t total = 0;
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    Room room{capacity};
     for (uint64_t q0 = q_begin; q0 < q_end; q0 += step) {
         uint64_t n = 0;
-        const int rc = topk_range(ctx, qry, ref, q0, std::min(q_end, q0 + step), kmer_size, kmer_space, max_distance, max_p_value, k,
-                                  total <= capacity ? capacity - total : 0, out_host + std::min(total, capacity), &n);
+        const int rc = topk_range(ctx, qry, ref, q0, std::min(q_end, q0 + step), cut, k, room.left(), room.at(out_host), &n);
         if (rc != MG_OK) return rc;
-        total += n;
+        room.total += n;
     }
-    *count_out = total;
-    if (total > capacity) return fail(ctx, MG_ERR_NOMEM, "top-k: more records than `capacity` (see *count_out)");
+    *count_out = room.total;
+    if (room.total > capacity) return fail(ctx, MG_ERR_NOMEM, "top-k: more records than `capacity` (see *count_out)");
     return MG_OK;
 }

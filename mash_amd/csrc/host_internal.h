@@ -251,10 +251,11 @@ struct DevBuf {
     explicit DevBuf(mg_ctx *ctx) : owner(ctx) {}
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) { if (owner) ctx_free(owner, p); else hipFree(p); } }
+    ~DevBuf() { free(); }
+    void free() { if (p) { if (owner) ctx_free(owner, p); else hipFree(p); p = nullptr; } }
     hipError_t alloc(uint64_t count)
     {
-        if (p) { if (owner) ctx_free(owner, p); else hipFree(p); p = nullptr; }     // (a second alloc: the first block goes back)
+        free();                                                 // (a second alloc: the first block goes back)
         const size_t bytes = std::max<uint64_t>(count, 1) * sizeof(T);
         return owner ? ctx_malloc(owner, reinterpret_cast<void **>(&p), bytes) : hipMalloc(&p, bytes);
     }
