@@ -20,7 +20,8 @@
 //   lay_out         offsets, short rows, the sort's bits, the tiles' plan, every buffer, the uploads;
 //   build_by_tiles  index_build.hip in three stages with the candidate groups laid out in between: the second wait
 //                   (an event behind the bucket sorts);  build_by_sort: rounds 3-4's way, for what the tiles refuse;
-//   dense_groups    universes, layout and encoding of the groups of near-identical rows: the third wait.
+//   check_build     the statistics;  dense_groups: universes, choice and encoding of the groups of near-identical rows: the third wait.
+// A phase that fails settles it there (no_memory, lost, unusable): every phase may assume what the phases before it made.
 #include "host_internal.h"
 #include "index_build.h"
 #ifdef IX_PHASE_CLOCKS
@@ -47,6 +48,51 @@ uint64_t longest_label_run(const uint32_t *lab_sorted, uint64_t n)
     }
     return longest;
 }
+
+// Sub-blocks of one block of memory, each at its type's alignment.  Without a block (nullptr) it hands out nullptr and only
+// counts: the block's size comes from the same list of takes that later carves it.
+struct Carve {
+    unsigned char *base = nullptr;
+    size_t at = 0;
+    template <class T> T *take(size_t count)
+    {
+        const size_t from = (at + alignof(T) - 1) & ~(alignof(T) - 1);
+        at = from + count * sizeof(T);
+        return base ? reinterpret_cast<T *>(base + from) : nullptr;
+    }
+};
+
+// The dense groups' leaders (compare_dense.hip): {key, val} entries appended to `lists` lists of `cap` entries each -- by the
+// tiles' bucket sorts (index_build.h, IxLeaders) or by a search of the finished index (dense_find_leaders) -- then made
+// one list (keyj, valj).  tot: {leaders kept, what the fullest list asked for}, the host's after the next wait.
+struct LeaderLists {
+    DevBuf<unsigned long long> key, keyj;
+    DevBuf<uint32_t> val, valj, cnt_sub, off_sub, nlead;
+    uint32_t lists = mg::dense_sublists(), cap = 0, tot[2] = {0, 0};
+    explicit LeaderLists(mg_ctx *c) : key(c), keyj(c), val(c), valj(c), cnt_sub(c), off_sub(c), nlead(c) {}
+
+    // `room` entries per list (the counters come with the first).  The four lists go back to the pool BEFORE any is taken
+    // again: the pool's peak is one set of lists.  cap follows only if all four stand.
+    hipError_t alloc(uint32_t room)
+    {
+        key.free(); val.free(); keyj.free(); valj.free();
+        const uint64_t all = (uint64_t)lists * room;
+        if (!(nlead.p && cnt_sub.p && off_sub.p) && (nlead.alloc(2) != hipSuccess || cnt_sub.alloc(lists) != hipSuccess || off_sub.alloc(lists) != hipSuccess))
+            return hipErrorOutOfMemory;
+        if (key.alloc(all) != hipSuccess || val.alloc(all) != hipSuccess || keyj.alloc(all) != hipSuccess || valj.alloc(all) != hipSuccess) return hipErrorOutOfMemory;
+        cap = room;
+        return hipSuccess;
+    }
+    // the counters zeroed (before anything appends); the totals on their way back; the lists made one and the totals with them
+    hipError_t reset(hipStream_t st) { const hipError_t e = hipMemsetAsync(cnt_sub, 0, lists * 4, st); return e != hipSuccess ? e : hipMemsetAsync(nlead, 0, 8, st); }
+    hipError_t join(hipStream_t st)
+    {
+        const hipError_t e = mg::dense_join_leaders(key, val, cap, keyj, valj, cnt_sub, off_sub, nlead, st);
+        return e != hipSuccess ? e : hipMemcpyAsync(tot, nlead, 8, hipMemcpyDeviceToHost, st);
+    }
+    mg::IxLeaders view(const uint32_t *lead_rows) const { return mg::IxLeaders{lead_rows, key, val, cnt_sub, cap, lists}; }
+    bool overflowed() const { return tot[1] > cap; }        // a list was asked for more than its room: the joined list is short
+};
 
 struct SparseIndexBuild {
     // ---- what is built, from what
@@ -97,10 +143,9 @@ struct SparseIndexBuild {
     std::vector<mg::DenseGroup> cand_groups;
     std::vector<uint32_t> grp_of_h;
     DevBuf<mg::DenseGroup> d_groups;
-    DevBuf<uint32_t> d_grp_of, d_lead_rows, d_val, d_valj, d_cnt_sub, d_off_sub, d_nlead;
-    DevBuf<unsigned long long> d_key, d_keyj;
-    uint32_t lead_lists = 0, lead_tot[2] = {0, 0}, lead_cap = 0;
-    bool lead_ready = false, lead_done = false, cand_prepared = false;
+    DevBuf<uint32_t> d_grp_of, d_lead_rows;
+    LeaderLists lead;
+    bool lead_ready = false, cand_prepared = false;
     mg::IxPlan plan;
     size_t temp_bytes = 0;
     DevBuf<unsigned char> temp;
@@ -109,29 +154,20 @@ struct SparseIndexBuild {
     struct Stat { unsigned long long shared; uint32_t max_group, groups, bad, tie_overflow; uint32_t ixf[4]; } h_stat = {0, 0, 0, 0, 0, {0, 0, 0, 0}};
     DevBuf<Stat> d_stat;
     DevBuf<unsigned char> d_slots;
-    bool want_order = true, ok = false;
-    size_t nshort = 0;
+    bool want_order = true;
     std::vector<uint32_t> short_cnt;
-    hipError_t e = hipSuccess;
 
     // ---- build
     bool built = false;
+    uint64_t dn_xrows = 0, dn_words = 0;                    // choose_groups: rows and mask words of the groups kept
 
     SparseIndexBuild(mg_ctx *c, const mg_table *tab, uint32_t sketch_size, bool clustered_variant, mg_table::Sparse *index, uint32_t split_row)
-        : ctx(c), t(tab), s(sketch_size), clustered(clustered_variant), split(split_row), sp(index), n(tab->n), dc_cls(c), d_link(c), dc_last(c), d_dig(c),
-          d_dig_sorted(c), k_a(c), k_b(c), d_cnt(c), d_rows_sorted(c), d_flags(c), d_nflag(c), r_a(c), r_b(c), l_a(c), l_b(c), d_inv(c),
-          d_lab(c), d_tmp_dup(c), d_tmp_cl(c), d_lb(c), d_groups(c), d_grp_of(c), d_lead_rows(c), d_val(c), d_valj(c), d_cnt_sub(c),
-          d_off_sub(c), d_nlead(c), d_key(c), d_keyj(c), temp(c), gs_of(c), key64_a(c), key64_b(c), d_stat(c), d_slots(c)
-    {
-    }
+        : ctx(c), t(tab), s(sketch_size), clustered(clustered_variant), split(split_row), sp(index), n(tab->n), dc_cls(c), d_link(c), dc_last(c), d_dig(c), d_dig_sorted(c),
+          k_a(c), k_b(c), d_cnt(c), d_rows_sorted(c), d_flags(c), d_nflag(c), r_a(c), r_b(c), l_a(c), l_b(c), d_inv(c), d_lab(c), d_tmp_dup(c), d_tmp_cl(c), d_lb(c),
+          d_groups(c), d_grp_of(c), d_lead_rows(c), lead(c), temp(c), gs_of(c), key64_a(c), key64_b(c), d_stat(c), d_slots(c)
+    {}
 
-    int unusable(const char *why)
-    {
-        sp->usable = false;
-        sp->why = why;
-        stop = true;
-        return MG_OK;
-    }
+    int unusable(const char *why) { sp->usable = false; sp->why = why; stop = true; return MG_OK; }
 
     // the device's counts in the index's order: only if somebody asks (copy suspects, no clustering to be had)
     hipError_t counts_to_device()
@@ -157,15 +193,57 @@ struct SparseIndexBuild {
                 if (*q) { ctx_free(ctx, *q); *q = nullptr; }
     }
 
+    // how a phase ends that found no room for the index, or one of whose launches, copies or waits failed
+    int no_memory() { (void)hipGetLastError(); drop(); return unusable("no device memory for the index"); }
+    int lost(hipError_t e) { drop(); return fail(ctx, MG_ERR_HIP, std::string("compare (index build): ") + hipGetErrorString(e)); }
+
+    void drop_dense()                                       // the dense groups' retained buffers back to the pool: the table goes without
+    {
+        for (void **q : {(void **)&sp->dgroups, (void **)&sp->grp_of, (void **)&sp->gdata, (void **)&sp->ext, (void **)&sp->ulist, (void **)&sp->upos})
+            if (*q) { ctx_free(ctx, *q); *q = nullptr; }
+        sp->dgroups_host.clear();
+    }
+
+    struct TileScratch {                                    // index_build.hip's scratch besides the window offsets (IxPlan's sizes)
+        DevBuf<unsigned char> tcnt, start, big, pk, tc;
+        explicit TileScratch(mg_ctx *c) : tcnt(c), start(c), big(c), pk(c), tc(c) {}
+    };
+
+    // the ONE call of index_build.hip: its stages by bit mask (index_build.h), the leaders' lists once the candidates are laid out
+    hipError_t tiles(const TileScratch &w, int stages)
+    {
+        const mg::IxLeaders lv = lead.view(d_lead_rows);
+        return mg::index_build(plan, H, sp->off, d_lb, w.tcnt, w.start, w.big, w.pk, w.tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
+                               sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf, lead_ready ? &lv : nullptr,
+                               ctx->stream, stages);
+    }
+    // The bucket sorts: values, rows, groups, statistics, leaders are final behind them.  The leaders' lists are made one; their
+    // totals come back with the statistics -- the host's after the caller's wait.
+    hipError_t sort_buckets(const TileScratch &w)
+    {
+        hipError_t e = tiles(w, 2);
+        if (e == hipSuccess && lead_ready) e = lead.join(ctx->stream);
+        return e != hipSuccess ? e : hipMemcpyAsync(&h_stat, d_stat, sizeof(Stat), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    // visiting order of the rows (by the run of their first shared value, larger rows first inside a run)
+    hipError_t row_order()
+    {
+        return mg::launch_sparse_row_order(sp->off, sp->code_img, sp->gend, sp->rep, (uint32_t)n, sp->rs, temp, temp_bytes, key64_a, key64_b, sp->order, ctx->stream);
+    }
+
     int scan_rows();
     int order_rows();
     int find_copies();
     int lay_out();
     void prepare_candidates();
-    void finish_build();
+    hipError_t tile_passes();
     int build_by_tiles();
     int build_by_sort();
     int check_build();
+    bool search_leaders();
+    bool sort_universes(std::vector<uint32_t> &us, std::vector<uint32_t> &ue);
+    bool choose_groups(const std::vector<uint32_t> &us, const std::vector<uint32_t> &ue);
+    int encode_groups();
     int dense_groups();
     int run();
 };
@@ -233,13 +311,20 @@ int SparseIndexBuild::scan_rows()
         }
         // the read-backs: into one pinned block if there is one -- queued all at once, one wait, then handed to the vectors
         // that outlive this call -- else straight into the vectors, one blocking copy after the other
-        const size_t pin_bytes = 8 * n + 4 * n + 4 * n + 4 * n + 8 + n + n + 64;
-        unsigned char *pin = static_cast<unsigned char *>(ctx_pinned(ctx, pin_bytes));
-        unsigned long long *p_last = pin ? reinterpret_cast<unsigned long long *>(pin) : nullptr;
-        uint32_t *p_nh = pin ? reinterpret_cast<uint32_t *>(pin + 8 * n) : nullptr, *p_inv = pin ? p_nh + n : nullptr, *p_lab = pin ? p_inv + n : nullptr;
-        uint32_t *p_nflag = pin ? p_lab + n : &nflag;
-        uint8_t *p_cls = pin ? pin + 20 * n + 8 : nullptr, *p_link = pin ? p_cls + n : nullptr;
-        if (!pin) {
+        unsigned long long *p_last = nullptr;
+        uint32_t *p_nh = nullptr, *p_inv = nullptr, *p_lab = nullptr, *p_nflag = nullptr;
+        uint8_t *p_cls = nullptr, *p_link = nullptr;
+        auto carve = [&](unsigned char *block) {             // the block's sub-blocks; returns the bytes it takes (and some slack)
+            Carve c{block};
+            p_last = c.take<unsigned long long>(n); p_nh = c.take<uint32_t>(n); p_inv = c.take<uint32_t>(n); p_lab = c.take<uint32_t>(n);
+            p_nflag = c.take<uint32_t>(2); p_cls = c.take<uint8_t>(n); p_link = c.take<uint8_t>(n);
+            return c.at + 64;
+        };
+        unsigned char *pin = static_cast<unsigned char *>(ctx_pinned(ctx, carve(nullptr)));      // (the dry pass left every pointer nullptr)
+        if (pin) {
+            carve(pin);
+        } else {
+            p_nflag = &nflag;
             if (cluster_q) { inv_v.resize(n); lab_v.resize(n); p_inv = inv_v.data(); p_lab = lab_v.data(); }
             p_nh = hc_nh.data(); p_cls = hc_cls.data(); p_last = reinterpret_cast<unsigned long long *>(hc_last.data()); p_link = link.data();
         }
@@ -464,10 +549,6 @@ int SparseIndexBuild::lay_out()
     // largest hashes (by bit length); b is chosen for 2^13 of them at most, and never above the even-spread rule (sort_bits.h).
     sort_begin_bit = mg::sparse_sort_begin_bit(E, end_bit, ctx_opt(ctx, "MASHGPU_SPARSE_SORT_BITS"), ctx_opt(ctx, "MASHGPU_SPARSE_SORT_ALL_BITS") != nullptr);
     if (sort_begin_bit > 0 && !ctx_opt(ctx, "MASHGPU_SPARSE_SORT_BITS")) sort_begin_bit = mg::sort_begin_bit_from_density(dens, end_bit, sort_begin_bit);
-    // room for the dense groups' leaders (prepare_candidates): one list entry each, a quarter of the entries in all
-    lead_lists = mg::dense_sublists();
-    lead_cap = std::max<uint32_t>(E / 4u / lead_lists + 64u, 256u);
-    if (const char *ev = ctx_opt(ctx, "MASHGPU_DENSE_LEAD_CAP")) lead_cap = std::max<uint32_t>((uint32_t)atoi(ev), 1u);      // (test knob: lists that overflow)
     const bool tiles_hopeless = ix_tiles && !ix_verify && lab_sorted && !ctx_opt(ctx, "MASHGPU_SPARSE_INDEX") &&
                                 longest_label_run(lab_sorted, n) > kTilesLongestRun;
     if (ix_tiles && !tiles_hopeless) plan = mg::index_plan((uint32_t)n, E, s, sp->rs, t->s, maxv, dens0, ix_verify);
@@ -479,37 +560,32 @@ int SparseIndexBuild::lay_out()
     temp_bytes = std::max(std::max(mg::sparse_order_temp_bytes((uint32_t)n), mg::sparse_order_slice_temp_bytes((uint32_t)n)),
                           mg::sparse_offsets_temp_bytes((uint32_t)n));
     want_order = !ctx_opt(ctx, "MASHGPU_SPARSE_NO_ORDER");
-    ok = temp.alloc(std::max<size_t>(temp_bytes, 16)) == hipSuccess && gs_of.alloc(E) == hipSuccess && d_stat.alloc(1) == hipSuccess &&
+    bool ok = temp.alloc(std::max<size_t>(temp_bytes, 16)) == hipSuccess && gs_of.alloc(E) == hipSuccess && d_stat.alloc(1) == hipSuccess &&
               d_slots.alloc(std::max(mg::sparse_stat_scratch_bytes(), mg::index_stat_scratch_bytes())) == hipSuccess &&
               (!want_order || (key64_a.alloc(n) == hipSuccess && key64_b.alloc(n) == hipSuccess));
     // retained buffers
     ok = ok && take(&sp->off, n + 1) && take(&sp->keys_sorted, E) && take(&sp->gend, E) && take(&sp->sorted_rows, E) &&
          take(&sp->code_img, (size_t)n * sp->rs + 64) && take(&sp->pos_img, (size_t)n * sp->rs) && take(&sp->counters, 4) &&
          (!want_order || take(&sp->order, n));
-    nshort = sp->short_rows_host.size();
+    const size_t nshort = sp->short_rows_host.size();
     short_cnt.assign(nshort, 0);
     for (size_t k = 0; k < nshort; k++) short_cnt[k] = cnt_true[sp->short_rows_host[k]];
     if (ok && nshort) ok = take(&sp->short_rows, nshort) && take(&sp->short_cnt, nshort);
     if (ok && sp->copies)
         ok = take(&sp->rep, n) && take(&sp->cls_of, n) && take(&sp->cls_off, cls_off.size()) && take(&sp->cls_rows, cls_rows.size()) &&
              take(&sp->cls_first, cls_first.size());
-    e = hipSuccess;
-    if (ok && sp->copies) {
-        e = hipMemcpyAsync(sp->rep, rep.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(sp->cls_of, cls_of.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(sp->cls_off, cls_off.data(), cls_off.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(sp->cls_rows, cls_rows.data(), cls_rows.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(sp->cls_first, cls_first.data(), cls_first.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (ok && e == hipSuccess) {
-        // the rows' offsets: made on the device from its counts (sp_offsets_kernel) unless copies stay out of the index
-        // (its temporary: the ordering's, not in use before the index stands)
-        if (rep.empty()) e = mg::launch_sparse_offsets(d_cnt, cnt_stale ? sp->inv : nullptr, (uint32_t)n, temp, sp->off, ctx->stream);
-        else e = hipMemcpyAsync(sp->off, sp->off_host.data(), (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && nshort) e = hipMemcpyAsync(sp->short_rows, sp->short_rows_host.data(), nshort * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && nshort) e = hipMemcpyAsync(sp->short_cnt, short_cnt.data(), nshort * 4, hipMemcpyHostToDevice, ctx->stream);
-    }
-    return MG_OK;
+    if (!ok) return no_memory();
+    hipError_t e = hipSuccess;
+    auto upload = [&](uint32_t *dst, const std::vector<uint32_t> &v) {      // (an empty vector queues nothing)
+        if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(dst, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    };
+    if (sp->copies) { upload(sp->rep, rep); upload(sp->cls_of, cls_of); upload(sp->cls_off, cls_off); upload(sp->cls_rows, cls_rows); upload(sp->cls_first, cls_first); }
+    // the rows' offsets: made on the device from its counts (sp_offsets_kernel) unless copies stay out of the index
+    // (its temporary: the ordering's, not in use before the index stands)
+    if (!rep.empty()) upload(sp->off, sp->off_host);
+    else if (e == hipSuccess) e = mg::launch_sparse_offsets(d_cnt, cnt_stale ? sp->inv : nullptr, (uint32_t)n, temp, sp->off, ctx->stream);
+    upload(sp->short_rows, sp->short_rows_host); upload(sp->short_cnt, short_cnt);
+    return e == hipSuccess ? MG_OK : lost(e);
 }
 
 // ---- candidates for dense groups (compare_dense.hip): runs of at least 8 consecutive rows linked to their predecessors.
@@ -536,15 +612,14 @@ void SparseIndexBuild::prepare_candidates()
     grp_of_h.assign(n, 0xFFFFFFFFu);
     for (uint32_t g = 0; g < ng; g++)
         for (uint32_t r = cand_groups[g].g0; r < cand_groups[g].g1; r++) grp_of_h[r] = g;
-    // the device's copies -- every row's group, and per row {group, its first row, one past its last, 0}: what K4
-    // gathers -- are made there from the groups (dn_group_rows_kernel)
-    const uint64_t room = (uint64_t)lead_lists * lead_cap;
-    if (d_groups.alloc(ng) == hipSuccess && d_grp_of.alloc(n) == hipSuccess && d_lead_rows.alloc(4 * n) == hipSuccess && d_nlead.alloc(2) == hipSuccess && d_cnt_sub.alloc(lead_lists) == hipSuccess &&
-        d_off_sub.alloc(lead_lists) == hipSuccess && d_key.alloc(room) == hipSuccess && d_val.alloc(room) == hipSuccess && d_keyj.alloc(room) == hipSuccess &&
-        d_valj.alloc(room) == hipSuccess &&
+    // room for the leaders: one list entry each, a quarter of the entries in all, evenly.  The device's copies -- every row's
+    // group, and per row {group, its first row, one past its last, 0}: what K4 gathers -- are made there from the groups
+    // (dn_group_rows_kernel)
+    uint32_t room = std::max<uint32_t>(E / 4u / lead.lists + 64u, 256u);
+    if (const char *ev = ctx_opt(ctx, "MASHGPU_DENSE_LEAD_CAP")) room = std::max<uint32_t>((uint32_t)atoi(ev), 1u);      // (test knob: lists that overflow)
+    if (d_groups.alloc(ng) == hipSuccess && d_grp_of.alloc(n) == hipSuccess && d_lead_rows.alloc(4 * n) == hipSuccess && lead.alloc(room) == hipSuccess &&
         hipMemcpyAsync(d_groups, cand_groups.data(), ng * sizeof(mg::DenseGroup), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-        mg::launch_dense_group_rows(d_groups, ng, (uint32_t)n, d_grp_of, d_lead_rows, ctx->stream) == hipSuccess &&
-        hipMemsetAsync(d_cnt_sub, 0, lead_lists * 4, ctx->stream) == hipSuccess && hipMemsetAsync(d_nlead, 0, 8, ctx->stream) == hipSuccess) {
+        mg::launch_dense_group_rows(d_groups, ng, (uint32_t)n, d_grp_of, d_lead_rows, ctx->stream) == hipSuccess && lead.reset(ctx->stream) == hipSuccess) {
         lead_ready = true;
     } else {
         (void)hipGetLastError();
@@ -552,213 +627,155 @@ void SparseIndexBuild::prepare_candidates()
     }
 }
 
-// visiting order of the rows (by the run of their first shared value, larger rows first inside a run), the statistics, one wait
-void SparseIndexBuild::finish_build()
+// index_build.hip in three stages with the candidate groups laid out in between; `built` says whether the index stands
+hipError_t SparseIndexBuild::tile_passes()
 {
-    if (e == hipSuccess && want_order)
-        e = mg::launch_sparse_row_order(sp->off, sp->code_img, sp->gend, sp->rep, (uint32_t)n, sp->rs, temp, temp_bytes, key64_a, key64_b,
-                                        sp->order, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_stat, d_stat, sizeof(Stat), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    TileScratch w(ctx);
+    if (!((lb_made || d_lb.alloc(plan.lb_bytes) == hipSuccess) && w.tcnt.alloc(plan.cnt_bytes) == hipSuccess && w.start.alloc(plan.start_bytes) == hipSuccess &&
+          w.big.alloc(plan.big_bytes) == hipSuccess && w.pk.alloc(plan.pk_bytes) == hipSuccess && w.tc.alloc(plan.tc_bytes) == hipSuccess)) {
+        (void)hipGetLastError();                            // (no memory for the tiles' scratch: the sort)
+        return hipSuccess;
+    }
+    hipError_t e = hipMemsetAsync(d_stat, 0, sizeof(Stat), ctx->stream);
+    // the partition (K0 - K3) goes first: the host lays out the candidates for dense groups while it runs
+    if (e == hipSuccess) e = tiles(w, lb_made ? 1 | 8 : 1);
+    // (test knob: what a ticket served out of lane order would leave behind -- the sorts' order check has to refuse the table)
+    DevBuf<uint32_t> d_swapped(ctx);
+    if (e == hipSuccess && ctx_opt(ctx, "MASHGPU_IX_DEBUG_SWAP") && d_swapped.alloc(1) == hipSuccess) {
+        e = hipMemsetAsync(d_swapped, 0, 4, ctx->stream);
+        if (e == hipSuccess) e = mg::index_debug_swap(plan, w.pk, w.start, d_swapped, ctx->stream);
+    }
+    if (e == hipSuccess) prepare_candidates();
+    // What the host wants of the bucket sorts is copied back and marked with an event; the images (K5) and the rows'
+    // visiting order are queued behind, and the host waits for the EVENT -- it lays out the dense groups while the images
+    // are still being written.
+    if (e == hipSuccess && ctx->aside_at_sort) ctx->aside_at_sort();      // (a job's fill that waits for the sorts: host_compare.cpp, prefill)
+    if (e == hipSuccess) e = sort_buckets(w);
+    hipEvent_t ev_stats = nullptr;
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_stats, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(ev_stats, ctx->stream);
+    if (e == hipSuccess) e = tiles(w, 4);
+    if (e == hipSuccess && want_order) e = row_order();
+    // (after a failure the whole stream: host memory is the target of copies that may be queued)
+    const hipError_t ew = e == hipSuccess ? hipEventSynchronize(ev_stats) : hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = ew;
+    if (ev_stats) (void)hipEventDestroy(ev_stats);
+    built = e == hipSuccess && !h_stat.ixf[mg::IXF_DEGENERATE];
+    // (not with buckets beyond the LDS: their second split reuses the partition's array, which the sorts would read again)
+    if (built && lead_ready && lead.overflowed() && h_stat.ixf[mg::IXF_NBIG] == 0) {
+        // A list of leaders filled beyond its room (the lists are filled by bucket: a table whose near-copies crowd a few
+        // buckets).  The leaders are found a second time with the room the fullest list asked for: the bucket sorts
+        // again -- the same index into the same arrays, the statistics counted anew (the table used to
+        // lose its dense groups here).
+        e = hipStreamSynchronize(ctx->stream);
+        const uint32_t want_cap = lead.tot[1];
+        if (e == hipSuccess && lead.alloc(want_cap) == hipSuccess) {
+            e = lead.reset(ctx->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(d_stat.p, 0, offsetof(Stat, bad), ctx->stream);      // shared, max_group, groups
+            if (e == hipSuccess) e = sort_buckets(w);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            built = e == hipSuccess && !h_stat.ixf[mg::IXF_DEGENERATE];
+            if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+                fprintf(stderr, "compare dense: a list of leaders asked for %u entries: found again with that room (%u leaders)\n", want_cap, lead.tot[0]);
+        } else {
+            (void)hipGetLastError();                    // (no room: the table goes without dense groups, as before)
+        }
+    }
+    if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+        fprintf(stderr, "compare sparse: index by tiles: shift %u, %u buckets (%u per window, %u windows), fullest %u, %u beyond the LDS (%u values streamed)%s\n",
+                plan.g.shift, plan.g.Bp, plan.g.BW, plan.g.NW, h_stat.ixf[mg::IXF_MAXBUCKET], h_stat.ixf[mg::IXF_NBIG], h_stat.ixf[mg::IXF_NSTREAMED],
+                h_stat.ixf[mg::IXF_DEGENERATE] ? " -- clumped values: sorted instead" : "");
+    return e;
 }
 
 int SparseIndexBuild::build_by_tiles()
 {
-    if (ok && e == hipSuccess && plan.ok) {
-        DevBuf<unsigned char> d_tcnt(ctx), d_start(ctx), d_big(ctx), d_pk(ctx), d_tc(ctx);
-        if ((lb_made || d_lb.alloc(plan.lb_bytes) == hipSuccess) && d_tcnt.alloc(plan.cnt_bytes) == hipSuccess && d_start.alloc(plan.start_bytes) == hipSuccess &&
-            d_big.alloc(plan.big_bytes) == hipSuccess && d_pk.alloc(plan.pk_bytes) == hipSuccess && d_tc.alloc(plan.tc_bytes) == hipSuccess) {
-            e = hipMemsetAsync(d_stat, 0, sizeof(Stat), ctx->stream);
-            // the partition (K0 - K3) goes first: the host lays out the candidates for dense groups while it runs
-            if (e == hipSuccess)
-                e = mg::index_build(plan, H, sp->off, d_lb, d_tcnt, d_start, d_big, d_pk, d_tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
-                                    sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf, nullptr, ctx->stream,
-                                    lb_made ? 1 | 8 : 1);
-            // (test knob: what a ticket served out of lane order would leave behind -- the sorts' order check has to refuse the table)
-            DevBuf<uint32_t> d_swapped(ctx);
-            if (e == hipSuccess && ctx_opt(ctx, "MASHGPU_IX_DEBUG_SWAP") && d_swapped.alloc(1) == hipSuccess) {
-                e = hipMemsetAsync(d_swapped, 0, 4, ctx->stream);
-                if (e == hipSuccess) e = mg::index_debug_swap(plan, d_pk, d_start, d_swapped, ctx->stream);
-            }
-            prepare_candidates();
-            mg::IxLeaders lead;
-            if (lead_ready) {
-                lead.grp_of = d_lead_rows;
-                lead.key = d_key;
-                lead.val = d_val;
-                lead.cnt = d_cnt_sub;
-                lead.cap_sub = lead_cap;
-                lead.nsub = lead_lists;
-            }
-            // values, rows, groups, statistics, leaders: final behind the bucket sorts.  What the host wants of them is copied
-            // back and marked with an event; the images (K5) and the rows' visiting order are queued behind, and the host waits
-            // for the EVENT -- it lays out the dense groups while the images are still being written.
-            if (e == hipSuccess && ctx->aside_at_sort) ctx->aside_at_sort();      // (a job's fill that waits for the sorts: host_compare.cpp, prefill)
-            if (e == hipSuccess)
-                e = mg::index_build(plan, H, sp->off, d_lb, d_tcnt, d_start, d_big, d_pk, d_tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
-                                    sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf,
-                                    lead_ready ? &lead : nullptr, ctx->stream, 2);
-            if (e == hipSuccess && lead_ready) {             // the leaders' lists made one; their count comes back with the statistics
-                e = mg::dense_join_leaders(d_key, d_val, lead_cap, d_keyj, d_valj, d_cnt_sub, d_off_sub, d_nlead, ctx->stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(lead_tot, d_nlead, 8, hipMemcpyDeviceToHost, ctx->stream);
-            }
-            hipEvent_t ev_stats = nullptr;
-            if (e == hipSuccess) e = hipMemcpyAsync(&h_stat, d_stat, sizeof(Stat), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_stats, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventRecord(ev_stats, ctx->stream);
-            if (e == hipSuccess)
-                e = mg::index_build(plan, H, sp->off, d_lb, d_tcnt, d_start, d_big, d_pk, d_tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
-                                    sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf,
-                                    lead_ready ? &lead : nullptr, ctx->stream, 4);
-            if (e == hipSuccess && want_order)
-                e = mg::launch_sparse_row_order(sp->off, sp->code_img, sp->gend, sp->rep, (uint32_t)n, sp->rs, temp, temp_bytes, key64_a, key64_b,
-                                                sp->order, ctx->stream);
-            if (ev_stats) {
-                const hipError_t ew = e == hipSuccess ? hipEventSynchronize(ev_stats) : hipStreamSynchronize(ctx->stream);
-                if (e == hipSuccess) e = ew;
-                (void)hipEventDestroy(ev_stats);
-            } else {
-                (void)hipStreamSynchronize(ctx->stream);    // (host memory is the target of copies that may be queued)
-            }
-            built = e == hipSuccess && !h_stat.ixf[mg::IXF_DEGENERATE];
-            // (not with buckets beyond the LDS: their second split reuses the partition's array, which the sorts would read again)
-            if (built && lead_ready && lead_tot[1] > lead_cap && h_stat.ixf[mg::IXF_NBIG] == 0) {
-                // A list of leaders filled beyond its room (the lists are filled by bucket: a table whose near-copies crowd a few
-                // buckets).  The leaders are found a second time with the room the fullest list asked for: the bucket sorts
-                // again -- the same index into the same arrays, the statistics counted anew (the table used to
-                // lose its dense groups here).
-                e = hipStreamSynchronize(ctx->stream);
-                const uint32_t want_cap = lead_tot[1];
-                for (void **q : {(void **)&d_key.p, (void **)&d_val.p, (void **)&d_keyj.p, (void **)&d_valj.p})
-                    if (*q) { ctx_free(ctx, *q); *q = nullptr; }
-                const uint64_t room = (uint64_t)lead_lists * want_cap;
-                if (e == hipSuccess && d_key.alloc(room) == hipSuccess && d_val.alloc(room) == hipSuccess && d_keyj.alloc(room) == hipSuccess &&
-                    d_valj.alloc(room) == hipSuccess) {
-                    lead_cap = want_cap;
-                    lead.key = d_key;
-                    lead.val = d_val;
-                    lead.cap_sub = lead_cap;
-                    e = hipMemsetAsync(d_cnt_sub, 0, lead_lists * 4, ctx->stream);
-                    if (e == hipSuccess) e = hipMemsetAsync(d_nlead, 0, 8, ctx->stream);
-                    if (e == hipSuccess) e = hipMemsetAsync(d_stat.p, 0, offsetof(Stat, bad), ctx->stream);      // shared, max_group, groups
-                    if (e == hipSuccess)
-                        e = mg::index_build(plan, H, sp->off, d_lb, d_tcnt, d_start, d_big, d_pk, d_tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of,
-                                            sp->code_img, sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf, &lead,
-                                            ctx->stream, 2);
-                    if (e == hipSuccess) e = mg::dense_join_leaders(d_key, d_val, lead_cap, d_keyj, d_valj, d_cnt_sub, d_off_sub, d_nlead, ctx->stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(lead_tot, d_nlead, 8, hipMemcpyDeviceToHost, ctx->stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(&h_stat, d_stat, sizeof(Stat), hipMemcpyDeviceToHost, ctx->stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                    built = e == hipSuccess && !h_stat.ixf[mg::IXF_DEGENERATE];
-                    if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
-                        fprintf(stderr, "compare dense: a list of leaders asked for %u entries: found again with that room (%u leaders)\n", want_cap, lead_tot[0]);
-                } else {
-                    (void)hipGetLastError();                // (no room: the table goes without dense groups, as before)
-                }
-            }
-            lead_done = built && lead_ready;
-            if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
-                fprintf(stderr, "compare sparse: index by tiles: shift %u, %u buckets (%u per window, %u windows), fullest %u, %u beyond the LDS (%u values streamed)%s\n",
-                        plan.g.shift, plan.g.Bp, plan.g.BW, plan.g.NW, h_stat.ixf[mg::IXF_MAXBUCKET], h_stat.ixf[mg::IXF_NBIG], h_stat.ixf[mg::IXF_NSTREAMED],
-                        h_stat.ixf[mg::IXF_DEGENERATE] ? " -- clumped values: sorted instead" : "");
-        } else {
-            (void)hipGetLastError();
-        }
-    } else if (ix_tiles && ctx_opt(ctx, "MASHGPU_SPARSE_DBG")) {
-        fprintf(stderr, "compare sparse: index by tiles refused: %s\n", plan.why);
-    }
+    hipError_t e = hipSuccess;
+    if (plan.ok) e = tile_passes();
+    else if (ix_tiles && ctx_opt(ctx, "MASHGPU_SPARSE_DBG")) fprintf(stderr, "compare sparse: index by tiles refused: %s\n", plan.why);
+    if (e != hipSuccess) return lost(e);
     sp->by_tiles = built;
     prepare_candidates();                                   // (no tiles: the candidates are still to be laid out)
 #ifdef IX_PHASE_CLOCKS
     if (built && ctx_opt(ctx, "MASHGPU_IX_CLOCKS")) mg::index_dump_clocks();
 #endif
-    if (ix_verify && !built && ok && e == hipSuccess && !ctx_opt(ctx, "MASHGPU_SPARSE_INDEX_MAY_REFUSE"))
+    if (ix_verify && !built && !ctx_opt(ctx, "MASHGPU_SPARSE_INDEX_MAY_REFUSE"))
         return fail(ctx, MG_ERR_INVALID, std::string("index verify: the tile build refused this table (") + (plan.ok ? "bucket flags" : plan.why) + ")");
     return MG_OK;
 }
 
 int SparseIndexBuild::build_by_sort()
 {
-    if (ok && e == hipSuccess && (!built || ix_verify)) {
-        // ---- the general way: every entry through a radix sort on the values' leading bits (compare_sparse.hip)
-        const size_t sort_bytes = mg::sparse_sort_temp_bytes(E, end_bit, sort_begin_bit);
-        DevBuf<unsigned char> temp_sort(ctx), d_ties(ctx);
-        DevBuf<uint64_t> keys_a(ctx), v_keys(ctx);
-        DevBuf<uint32_t> idx_a(ctx), idx_sorted(ctx), v_rows(ctx), v_gend(ctx), v_gs(ctx), v_code(ctx), v_pos(ctx);
-        DevBuf<unsigned long long> d_diff(ctx);
-        bool ok2 = temp_sort.alloc(std::max<size_t>(sort_bytes, 16)) == hipSuccess && keys_a.alloc(E) == hipSuccess && idx_a.alloc(E) == hipSuccess &&
-                   idx_sorted.alloc(E) == hipSuccess && d_ties.alloc(mg::sparse_tie_scratch_bytes()) == hipSuccess;
-        if (ok2 && built)                                   // (verify: the second build goes into arrays of its own)
-            ok2 = v_keys.alloc(E) == hipSuccess && v_rows.alloc(E) == hipSuccess && v_gend.alloc(E) == hipSuccess && v_gs.alloc(E) == hipSuccess &&
-                  v_code.alloc((size_t)n * sp->rs + 64) == hipSuccess && v_pos.alloc((size_t)n * sp->rs) == hipSuccess && d_diff.alloc(16) == hipSuccess;
-        if (!ok2) {
-            (void)hipGetLastError();
-            ok = false;
-        } else {
-            const Stat tiles_stat = h_stat;
-            uint64_t *o_keys = built ? v_keys.p : sp->keys_sorted;
-            uint32_t *o_rows = built ? v_rows.p : sp->sorted_rows, *o_gend = built ? v_gend.p : sp->gend, *o_gs = built ? v_gs.p : gs_of.p,
-                     *o_code = built ? v_code.p : sp->code_img, *o_pos = built ? v_pos.p : sp->pos_img;
-            // (the sort looks at the values' leading bits only and repairs the few ties; a table that defeats that is sorted again, on every bit)
-            for (uint32_t begin_bit = sort_begin_bit;; begin_bit = 0) {
-                if (e == hipSuccess) e = hipMemsetAsync(d_stat, 0, sizeof(Stat), ctx->stream);
-                if (e == hipSuccess)
-                    e = mg::sparse_build_index(H, t->s, sp->off, (uint32_t)n, E, sp->rs, end_bit, temp_sort, sort_bytes, keys_a, idx_a, o_keys, idx_sorted,
-                                               /*head=*/idx_a, o_gs, o_rows, o_gend, o_code, o_pos, d_slots, begin_bit, d_ties, &d_stat.p->shared,
-                                               &d_stat.p->max_group, &d_stat.p->groups, &d_stat.p->bad, &d_stat.p->tie_overflow, ctx->stream);
-                if (built) {
-                    if (e == hipSuccess) e = hipMemcpyAsync(&h_stat, d_stat, sizeof(Stat), hipMemcpyDeviceToHost, ctx->stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                } else {
-                    finish_build();
-                }
-                // (also when the order came out wrong behind a sort on the leading bits -- never seen since the repair kernels
-                //  exist, but the remedy is the same and silent downgrades to the tile engine are worse)
-                if (e != hipSuccess || (!h_stat.tie_overflow && !h_stat.bad) || begin_bit == 0) break;
-                if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
-                    fprintf(stderr, "compare sparse: sort on bits [%u, %u) %s: every bit again\n", begin_bit, end_bit,
-                            h_stat.bad ? "left values out of order" : "left ties the repair could not take");
-            }
-            if (built && e == hipSuccess) {
-                // every array of the two builds, word by word
-                unsigned long long diff[16];
-                for (int k = 0; k < 8; k++) { diff[2 * k] = 0; diff[2 * k + 1] = ~0ull; }
-                e = hipMemcpyAsync(d_diff, diff, sizeof diff, hipMemcpyHostToDevice, ctx->stream);
-                const uint64_t img = (uint64_t)n * sp->rs;
-                if (e == hipSuccess) e = mg::index_verify_words((const uint32_t *)sp->keys_sorted, (const uint32_t *)v_keys.p, nullptr, 0, 2ull * E, d_diff.p + 0, ctx->stream);
-                if (e == hipSuccess) e = mg::index_verify_words(sp->sorted_rows, v_rows, nullptr, 0, E, d_diff.p + 2, ctx->stream);
-                if (e == hipSuccess) e = mg::index_verify_words(gs_of, v_gs, nullptr, 0, E, d_diff.p + 4, ctx->stream);
-                if (e == hipSuccess) e = mg::index_verify_words(sp->gend, v_gend, v_gs, 1, E, d_diff.p + 6, ctx->stream);
-                if (e == hipSuccess) e = mg::index_verify_words(sp->code_img, v_code, nullptr, 0, img, d_diff.p + 8, ctx->stream);
-                if (e == hipSuccess) e = mg::index_verify_words(sp->pos_img, v_pos, v_code, 2, img, d_diff.p + 10, ctx->stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(diff, d_diff, sizeof diff, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e == hipSuccess) {
-                    static const char *names[6] = {"values (32-bit words)", "rows", "group starts", "group ends", "code image", "position image"};
-                    std::string msg;
-                    for (int k = 0; k < 6; k++)
-                        if (diff[2 * k]) msg += std::string(msg.empty() ? "" : "; ") + names[k] + ": " + std::to_string(diff[2 * k]) + " differ, first at " + std::to_string(diff[2 * k + 1]);
-                    if (h_stat.shared != tiles_stat.shared || h_stat.max_group != tiles_stat.max_group || h_stat.groups != tiles_stat.groups)
-                        msg += std::string(msg.empty() ? "" : "; ") + "statistics: shared " + std::to_string(tiles_stat.shared) + " / " + std::to_string(h_stat.shared) +
-                               ", largest group " + std::to_string(tiles_stat.max_group) + " / " + std::to_string(h_stat.max_group) + ", groups " +
-                               std::to_string(tiles_stat.groups) + " / " + std::to_string(h_stat.groups);
-                    if (!msg.empty()) {
-                        char geom[160];
-                        snprintf(geom, sizeof geom, " [n %llu, E %u, shift %u, %u buckets, %u per window, %u windows]", (unsigned long long)n, E, plan.g.shift, plan.g.Bp, plan.g.BW, plan.g.NW);
-                        sp->usable = false;
-                        return fail(ctx, MG_ERR_INVALID, "index verify: tiles / sort -- " + msg + geom);
-                    }
-                }
-            }
-        }
+    if (built && !ix_verify) return MG_OK;
+    // ---- the general way: every entry through a radix sort on the values' leading bits (compare_sparse.hip)
+    const size_t sort_bytes = mg::sparse_sort_temp_bytes(E, end_bit, sort_begin_bit);
+    DevBuf<unsigned char> temp_sort(ctx), d_ties(ctx);
+    DevBuf<uint64_t> keys_a(ctx), v_keys(ctx);
+    DevBuf<uint32_t> idx_a(ctx), idx_sorted(ctx), v_rows(ctx), v_gend(ctx), v_gs(ctx), v_code(ctx), v_pos(ctx);
+    DevBuf<unsigned long long> d_diff(ctx);
+    bool ok = temp_sort.alloc(std::max<size_t>(sort_bytes, 16)) == hipSuccess && keys_a.alloc(E) == hipSuccess && idx_a.alloc(E) == hipSuccess &&
+              idx_sorted.alloc(E) == hipSuccess && d_ties.alloc(mg::sparse_tie_scratch_bytes()) == hipSuccess;
+    if (ok && built)                                        // (verify: the second build goes into arrays of its own)
+        ok = v_keys.alloc(E) == hipSuccess && v_rows.alloc(E) == hipSuccess && v_gend.alloc(E) == hipSuccess && v_gs.alloc(E) == hipSuccess &&
+             v_code.alloc((size_t)n * sp->rs + 64) == hipSuccess && v_pos.alloc((size_t)n * sp->rs) == hipSuccess && d_diff.alloc(16) == hipSuccess;
+    if (!ok) return no_memory();
+    const Stat tiles_stat = h_stat;
+    uint64_t *o_keys = built ? v_keys.p : sp->keys_sorted;
+    uint32_t *o_rows = built ? v_rows.p : sp->sorted_rows, *o_gend = built ? v_gend.p : sp->gend, *o_gs = built ? v_gs.p : gs_of.p,
+             *o_code = built ? v_code.p : sp->code_img, *o_pos = built ? v_pos.p : sp->pos_img;
+    hipError_t e = hipSuccess;
+    // (the sort looks at the values' leading bits only and repairs the few ties; a table that defeats that is sorted again, on every bit)
+    for (uint32_t begin_bit = sort_begin_bit;; begin_bit = 0) {
+        e = hipMemsetAsync(d_stat, 0, sizeof(Stat), ctx->stream);
+        if (e == hipSuccess)
+            e = mg::sparse_build_index(H, t->s, sp->off, (uint32_t)n, E, sp->rs, end_bit, temp_sort, sort_bytes, keys_a, idx_a, o_keys, idx_sorted,
+                                       /*head=*/idx_a, o_gs, o_rows, o_gend, o_code, o_pos, d_slots, begin_bit, d_ties, &d_stat.p->shared,
+                                       &d_stat.p->max_group, &d_stat.p->groups, &d_stat.p->bad, &d_stat.p->tie_overflow, ctx->stream);
+        // (verify: the order is the tiles'), the statistics, one wait
+        if (e == hipSuccess && !built && want_order) e = row_order();
+        if (e == hipSuccess) e = hipMemcpyAsync(&h_stat, d_stat, sizeof(Stat), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return lost(e);
+        // (also when the order came out wrong behind a sort on the leading bits -- never seen since the repair kernels
+        //  exist, but the remedy is the same and silent downgrades to the tile engine are worse)
+        if ((!h_stat.tie_overflow && !h_stat.bad) || begin_bit == 0) break;
+        if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+            fprintf(stderr, "compare sparse: sort on bits [%u, %u) %s: every bit again\n", begin_bit, end_bit,
+                    h_stat.bad ? "left values out of order" : "left ties the repair could not take");
+    }
+    if (!built) return MG_OK;
+    // every array of the two builds, word by word
+    unsigned long long diff[16];
+    for (int k = 0; k < 8; k++) { diff[2 * k] = 0; diff[2 * k + 1] = ~0ull; }
+    e = hipMemcpyAsync(d_diff, diff, sizeof diff, hipMemcpyHostToDevice, ctx->stream);
+    const uint64_t img = (uint64_t)n * sp->rs;
+    const struct { const char *name; const uint32_t *tiles, *sort, *ref; uint32_t mode; uint64_t words; } arrays[6] = {
+        {"values (32-bit words)", (const uint32_t *)sp->keys_sorted, (const uint32_t *)v_keys.p, nullptr, 0, 2ull * E}, {"rows", sp->sorted_rows, v_rows, nullptr, 0, E},
+        {"group starts", gs_of, v_gs, nullptr, 0, E}, {"group ends", sp->gend, v_gend, v_gs, 1, E}, {"code image", sp->code_img, v_code, nullptr, 0, img},
+        {"position image", sp->pos_img, v_pos, v_code, 2, img}};
+    for (int k = 0; k < 6 && e == hipSuccess; k++)
+        e = mg::index_verify_words(arrays[k].tiles, arrays[k].sort, arrays[k].ref, arrays[k].mode, arrays[k].words, d_diff.p + 2 * k, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(diff, d_diff, sizeof diff, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return lost(e);
+    std::string msg;
+    for (int k = 0; k < 6; k++)
+        if (diff[2 * k]) msg += std::string(msg.empty() ? "" : "; ") + arrays[k].name + ": " + std::to_string(diff[2 * k]) + " differ, first at " + std::to_string(diff[2 * k + 1]);
+    if (h_stat.shared != tiles_stat.shared || h_stat.max_group != tiles_stat.max_group || h_stat.groups != tiles_stat.groups)
+        msg += std::string(msg.empty() ? "" : "; ") + "statistics: shared " + std::to_string(tiles_stat.shared) + " / " + std::to_string(h_stat.shared) +
+               ", largest group " + std::to_string(tiles_stat.max_group) + " / " + std::to_string(h_stat.max_group) + ", groups " +
+               std::to_string(tiles_stat.groups) + " / " + std::to_string(h_stat.groups);
+    if (!msg.empty()) {
+        char geom[160];
+        snprintf(geom, sizeof geom, " [n %llu, E %u, shift %u, %u buckets, %u per window, %u windows]", (unsigned long long)n, E, plan.g.shift, plan.g.Bp, plan.g.BW, plan.g.NW);
+        sp->usable = false;
+        return fail(ctx, MG_ERR_INVALID, "index verify: tiles / sort -- " + msg + geom);
     }
     return MG_OK;
 }
 
 int SparseIndexBuild::check_build()
 {
-    if (!ok) { (void)hipGetLastError(); drop(); return unusable("no device memory for the index"); }
-    if (e != hipSuccess) { drop(); return fail(ctx, MG_ERR_HIP, std::string("compare (index build): ") + hipGetErrorString(e)); }
     if (h_stat.bad) { drop(); return unusable("sort order inside a value not by row"); }
     sp->G = h_stat.groups;
     sp->shared = h_stat.shared;
@@ -768,135 +785,116 @@ int SparseIndexBuild::check_build()
     return MG_OK;
 }
 
+// The leaders behind the SORT (the tiles find them themselves; searching needs every position's group start, which the sort
+// wrote): the finished index is searched, a second time with the room the first pass asked for if the lists filled unevenly.
+bool SparseIndexBuild::search_leaders()
+{
+    for (int attempt = 0;; attempt++) {
+        hipError_t e = mg::dense_find_leaders(sp->sorted_rows, gs_of, sp->gend, d_grp_of, d_groups, E, lead.key, lead.val, lead.cap, lead.keyj, lead.valj,
+                                              lead.cnt_sub, lead.off_sub, lead.nlead, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(lead.tot, lead.nlead, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return false;
+        if (!lead.overflowed() || attempt >= 1) return true;
+        if (lead.alloc(lead.tot[1]) != hipSuccess) return false;
+    }
+}
+
+// the leaders sorted by group and value: the universes' values (ulist) and leader positions (upos), retained, and where
+// every group's universe begins and ends in them (us, ue)
+bool SparseIndexBuild::sort_universes(std::vector<uint32_t> &us, std::vector<uint32_t> &ue)
+{
+    const uint32_t ng = (uint32_t)cand_groups.size(), nlead = lead.tot[0];
+    uint32_t gbits = 1;
+    while ((1u << gbits) < ng) gbits++;
+    const size_t tb = mg::dense_universe_temp_bytes(nlead);
+    DevBuf<uint32_t> d_us(ctx), d_ue(ctx);                  // (scratch: back to the pool behind the wait below)
+    DevBuf<unsigned long long> d_key2(ctx);
+    DevBuf<unsigned char> d_utmp(ctx);
+    bool ok = d_us.alloc(ng) == hipSuccess && d_ue.alloc(ng) == hipSuccess && d_key2.alloc(nlead) == hipSuccess && d_utmp.alloc(std::max<size_t>(tb, 16)) == hipSuccess;
+    if (!ok || !take(&sp->ulist, nlead) || !take(&sp->upos, nlead)) return false;
+    // (Measured and dropped: this sort -- two dozen small kernels that need the leaders only -- on a second stream beside
+    //  the images' kernel.  The large kernel holds every CU: a 4 us memset took 170 us there, and the sort ended when it
+    //  would have ended behind the images.)
+    hipError_t e = hipMemsetAsync(d_us, 0, ng * 4, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_ue, 0, ng * 4, ctx->stream);
+    if (e == hipSuccess) e = mg::dense_sort_universes(lead.keyj, lead.valj, nlead, d_utmp, tb, d_key2, sp->ulist, sp->upos, d_us, d_ue, gbits, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(us.data(), d_us, ng * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ue.data(), d_ue, ng * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess;
+}
+
+// the groups that stay (sp->dgroups_host, the rows' map in grp_of_h): a universe of at least 32 values (else the rows are not
+// near-copies and the pairs are cheap elsewhere) and at most as many words as a tile's rows fit the LDS with
+bool SparseIndexBuild::choose_groups(const std::vector<uint32_t> &us, const std::vector<uint32_t> &ue)
+{
+    const uint32_t kMaxWords = mg::dense_max_words();
+    std::fill(grp_of_h.begin(), grp_of_h.end(), 0xFFFFFFFFu);
+    for (uint32_t g = 0; g < (uint32_t)cand_groups.size(); g++) {
+        mg::DenseGroup G = cand_groups[g];
+        G.u = ue[g] > us[g] ? ue[g] - us[g] : 0u;
+        G.ustart = us[g];
+        G.W = (G.u >> 6) + 1u;
+        if (G.u < 32u || G.W > kMaxWords) continue;
+        G.xrow0 = (uint32_t)dn_xrows;
+        G.data_off = dn_words;
+        const uint64_t m = G.g1 - G.g0;
+        dn_xrows += m;
+        dn_words += ((m + 127) / 128) * mg::dense_block_words(G.W);
+        sp->dn_wmax = std::max(sp->dn_wmax, G.W);
+        for (uint32_t r = G.g0; r < G.g1; r++) grp_of_h[r] = (uint32_t)sp->dgroups_host.size();
+        sp->dgroups_host.push_back(G);
+    }
+    return !sp->dgroups_host.empty();
+}
+
+// the retained buffers, the uploads, and the encoding: masks, extras, and the index's runs clipped for the rows of the
+// groups -- discovery sees the partners outside only
+int SparseIndexBuild::encode_groups()
+{
+    sp->dn_xs = ((s + 7u) & ~7u) + 8u;
+    if (!take(&sp->dgroups, sp->dgroups_host.size()) || !take(&sp->grp_of, n) || !take(&sp->gdata, dn_words) || !take(&sp->ext, dn_xrows * sp->dn_xs)) {
+        (void)hipGetLastError();
+        sp->dgroups_host.clear();                          // (no room: nothing is kept, and dense_groups returns what was taken)
+        return MG_OK;
+    }
+    hipError_t e = hipMemcpyAsync(sp->dgroups, sp->dgroups_host.data(), sp->dgroups_host.size() * sizeof(mg::DenseGroup), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sp->grp_of, grp_of_h.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess)
+        e = mg::launch_dense_encode(sp->off, sp->code_img, sp->pos_img, sp->rs, sp->grp_of, sp->dgroups, sp->ulist, sp->upos, sp->gdata, sp->ext, sp->dn_xs,
+                                    (uint32_t)n, sp->dn_wmax, ctx->stream, ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS") ? atoi(ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS")) : -1);
+    // (no wait here: what the copies above read -- dgroups_host and the rows' group map -- lives in the index, what
+    //  comes next is queued on the same stream, and a fault shows at its wait)
+    sp->grp_of_host.swap(grp_of_h);
+    if (e != hipSuccess) {
+        // the runs may be half clipped: this index is not to be used
+        drop();
+        drop_dense();
+        sp->usable = false;
+        return fail(ctx, MG_ERR_HIP, std::string("compare (index build, dense groups): ") + hipGetErrorString(e));
+    }
+    sp->dn_lists = ctx_opt(ctx, "MASHGPU_DENSE_LISTS") != nullptr;          // (test knob: every word resolved from the lists)
+    return MG_OK;
+}
+
 int SparseIndexBuild::dense_groups()
 {
     // ---- dense groups: runs of at least 8 consecutive rows linked to their predecessors.  Their universes come from the
     // index just built (gs_of is still alive), groups without one (or with one too large for a tile's LDS) are dropped,
-    // the rest are encoded and the index's runs clipped for their rows.  Any failure here leaves the index as it is.
+    // the rest are encoded and the index's runs clipped for their rows.
     if (!cand_groups.empty()) {
         auto t_dense = std::chrono::steady_clock::now();
-        while (!cand_groups.empty()) {                       // (a block to leave with `break`)
-            const uint32_t ng = (uint32_t)cand_groups.size();
-            std::vector<uint32_t> &grp_of = grp_of_h;
-            DevBuf<uint32_t> d_us(ctx), d_ue(ctx);
-            DevBuf<unsigned long long> d_key2(ctx);
-            DevBuf<unsigned char> d_tmp(ctx);
-            if (d_us.alloc(ng) != hipSuccess || d_ue.alloc(ng) != hipSuccess) { (void)hipGetLastError(); break; }
-            // leaders: one list entry each, appended to one of a thousand lists (room for a quarter of the entries in all, evenly).
-            // The build by tiles has found them already; behind the sort the finished index is searched, a second time with
-            // the room the first pass asked for if the lists filled unevenly.
-            const uint32_t L = lead_lists;
-            uint32_t *tot = lead_tot, cap_sub = lead_cap;
-            hipError_t e2 = hipSuccess;
-            if (!lead_done) {
-                if (built || !lead_ready) break;             // (searching needs every position's group start: the sort wrote it)
-                for (int attempt = 0; e2 == hipSuccess; attempt++) {
-                    if (attempt > 0) {
-                        for (void **q : {(void **)&d_key.p, (void **)&d_val.p, (void **)&d_keyj.p, (void **)&d_valj.p})
-                            if (*q) { ctx_free(ctx, *q); *q = nullptr; }
-                        const uint64_t room = (uint64_t)L * cap_sub;
-                        if (d_key.alloc(room) != hipSuccess || d_val.alloc(room) != hipSuccess || d_keyj.alloc(room) != hipSuccess || d_valj.alloc(room) != hipSuccess) {
-                            (void)hipGetLastError();
-                            e2 = hipErrorOutOfMemory;
-                            break;
-                        }
-                    }
-                    e2 = mg::dense_find_leaders(sp->sorted_rows, gs_of, sp->gend, d_grp_of, d_groups, E, d_key, d_val, cap_sub, d_keyj, d_valj, d_cnt_sub, d_off_sub,
-                                                d_nlead, ctx->stream);
-                    if (e2 == hipSuccess) e2 = hipMemcpyAsync(tot, d_nlead, 8, hipMemcpyDeviceToHost, ctx->stream);
-                    if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-                    if (e2 != hipSuccess || tot[1] <= cap_sub || attempt >= 1) break;
-                    cap_sub = tot[1];
-                }
-            } else if (tot[1] > cap_sub && ctx_opt(ctx, "MASHGPU_SPARSE_DBG")) {
-                fprintf(stderr, "compare dense: a list of leaders asked for %u entries, room for %u: no dense groups for this table\n", tot[1], cap_sub);
-            }
-            const uint32_t nlead = tot[0];
-            if (e2 != hipSuccess || nlead == 0 || tot[1] > cap_sub) { (void)hipGetLastError(); break; }
-            uint32_t gbits = 1;
-            while ((1u << gbits) < ng) gbits++;
-            std::vector<uint32_t> us(ng, 0), ue(ng, 0);
-            void *ul = nullptr, *up = nullptr;
-            const size_t tb = mg::dense_universe_temp_bytes(nlead);
-            if (d_key2.alloc(nlead) != hipSuccess || d_tmp.alloc(std::max<size_t>(tb, 16)) != hipSuccess ||
-                ctx_malloc(ctx, &ul, (size_t)nlead * 4) != hipSuccess || ctx_malloc(ctx, &up, (size_t)nlead * 4) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx_free(ctx, ul);
-                break;
-            }
-            sp->ulist = static_cast<uint32_t *>(ul);
-            sp->upos = static_cast<uint32_t *>(up);
-            // (Measured and dropped: this sort -- two dozen small kernels that need the leaders only -- on a second stream beside
-            //  the images' kernel.  The large kernel holds every CU: a 4 us memset took 170 us there, and the sort ended when it
-            //  would have ended behind the images.)
-            e2 = hipMemsetAsync(d_us, 0, ng * 4, ctx->stream);
-            if (e2 == hipSuccess) e2 = hipMemsetAsync(d_ue, 0, ng * 4, ctx->stream);
-            if (e2 == hipSuccess)
-                e2 = mg::dense_sort_universes(d_keyj, d_valj, nlead, d_tmp, tb, d_key2, sp->ulist, sp->upos, d_us, d_ue, gbits, ctx->stream);
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(us.data(), d_us, ng * 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(ue.data(), d_ue, ng * 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-            if (e2 != hipSuccess) { (void)hipGetLastError(); break; }
-            // the groups that stay: a universe of at least 32 values (else the rows are not near-copies and the pairs are
-            // cheap elsewhere) and at most as many words as a tile's rows fit the LDS with
-            const uint32_t kMaxWords = mg::dense_max_words();
-            std::fill(grp_of.begin(), grp_of.end(), 0xFFFFFFFFu);
-            uint32_t xrows = 0, wmax = 0;
-            uint64_t words = 0;
-            for (uint32_t g = 0; g < ng; g++) {
-                mg::DenseGroup G = cand_groups[g];
-                G.u = ue[g] > us[g] ? ue[g] - us[g] : 0u;
-                G.ustart = us[g];
-                G.W = (G.u >> 6) + 1u;
-                if (G.u < 32u || G.W > kMaxWords) continue;
-                G.xrow0 = xrows;
-                G.data_off = words;
-                const uint64_t m = G.g1 - G.g0;
-                xrows += (uint32_t)m;
-                words += ((m + 127) / 128) * mg::dense_block_words(G.W);
-                wmax = std::max(wmax, G.W);
-                for (uint32_t r = G.g0; r < G.g1; r++) grp_of[r] = (uint32_t)sp->dgroups_host.size();
-                sp->dgroups_host.push_back(G);
-            }
-            if (sp->dgroups_host.empty()) break;
-            sp->dn_wmax = wmax;
-            sp->dn_xs = ((s + 7u) & ~7u) + 8u;
-            void *p1 = nullptr, *p2 = nullptr, *p3 = nullptr, *p4 = nullptr;
-            if (ctx_malloc(ctx, &p1, sp->dgroups_host.size() * sizeof(mg::DenseGroup)) != hipSuccess || ctx_malloc(ctx, &p2, n * 4) != hipSuccess ||
-                ctx_malloc(ctx, &p3, words * 8) != hipSuccess || ctx_malloc(ctx, &p4, (size_t)xrows * sp->dn_xs * 2) != hipSuccess) {
-                (void)hipGetLastError();
-                for (void *q : {p1, p2, p3, p4}) ctx_free(ctx, q);
-                sp->dgroups_host.clear();
-                break;
-            }
-            sp->dgroups = static_cast<mg::DenseGroup *>(p1);
-            sp->grp_of = static_cast<uint32_t *>(p2);
-            sp->gdata = static_cast<unsigned long long *>(p3);
-            sp->ext = static_cast<uint16_t *>(p4);
-            e2 = hipMemcpyAsync(sp->dgroups, sp->dgroups_host.data(), sp->dgroups_host.size() * sizeof(mg::DenseGroup), hipMemcpyHostToDevice, ctx->stream);
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(sp->grp_of, grp_of.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
-            // masks, extras, and the index's runs clipped for the rows of the groups: discovery sees the partners outside only
-            if (e2 == hipSuccess)
-                e2 = mg::launch_dense_encode(sp->off, sp->code_img, sp->pos_img, sp->rs, sp->grp_of, sp->dgroups, sp->ulist, sp->upos, sp->gdata,
-                                             sp->ext, sp->dn_xs, (uint32_t)n, wmax, ctx->stream,
-                                             ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS") ? atoi(ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS")) : -1);
-            // (no wait here: what the copies above read -- dgroups_host and the rows' group map -- lives in the index, what
-            //  comes next is queued on the same stream, and a fault shows at its wait)
-            sp->grp_of_host.swap(grp_of);
-            if (e2 != hipSuccess) {
-                // the runs may be half clipped: this index is not to be used
-                drop();
-                for (void **q : {(void **)&sp->dgroups, (void **)&sp->grp_of, (void **)&sp->gdata, (void **)&sp->ext, (void **)&sp->ulist,
-                                 (void **)&sp->upos})
-                    if (*q) { ctx_free(ctx, *q); *q = nullptr; }
-                sp->dgroups_host.clear();
-                sp->usable = false;
-                return fail(ctx, MG_ERR_HIP, std::string("compare (index build, dense groups): ") + hipGetErrorString(e2));
-            }
-            sp->dn_lists = ctx_opt(ctx, "MASHGPU_DENSE_LISTS") != nullptr;          // (test knob: every word resolved from the lists)
-            break;
-        }
-        if (sp->dgroups_host.empty() && sp->ulist) { ctx_free(ctx, sp->ulist); ctx_free(ctx, sp->upos); sp->ulist = sp->upos = nullptr; }
+        if (built && lead_ready && lead.overflowed() && ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+            fprintf(stderr, "compare dense: a list of leaders asked for %u entries, room for %u: no dense groups for this table\n", lead.tot[1], lead.cap);
+        std::vector<uint32_t> us(cand_groups.size(), 0), ue(cand_groups.size(), 0);
+        const int rc = [&] {                                // the steps in their order: one that says no ends it, the index stays as it is
+            if (!lead_ready || (!built && !search_leaders())) return (int)MG_OK;      // (the build by tiles has found the leaders itself)
+            if (lead.tot[0] == 0 || lead.overflowed()) return (int)MG_OK;
+            return sort_universes(us, ue) && choose_groups(us, ue) ? encode_groups() : (int)MG_OK;
+        }();
+        if (rc != MG_OK) return rc;
+        if (sp->dgroups_host.empty()) { (void)hipGetLastError(); drop_dense(); }      // (nothing kept: the universes go back)
         sp->build_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dense).count();
         if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG")) {
             uint64_t rows_in = 0;
