@@ -392,6 +392,28 @@ int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *
                               uint64_t q_end, int kmer_size, double kmer_space, double max_distance,
                               double max_p_value, uint32_t k, mg_result *out_host, uint64_t capacity,
                               uint64_t *count_out);
+/* The k nearest neighbours of every sketch of ONE table, chosen ON THE DEVICE (knn.hip, topk.hip) -- `mash triangle -N`.  The
+ * reference has no such option; the definition stands on the lines of `mash triangle -E` (CommandTriangle.cpp:159-198, which
+ * prints the unordered pair {i, j}, j < i, once).  For row i the neighbours are all j != i:
+ *   record   : the reference's record of the unordered pair -- numer, denom, distance and p-value of the `triangle -E` line of
+ *              (max(i, j), min(i, j)), doubles bit-equal to mg_compare_tri_pairs_host's -- as mg_result{row = i, col = j};
+ *   eligible : the pairs mg_compare_tri_pairs_host marks `pass` under the same max_distance / max_p_value conventions;
+ *   order    : mg_compare_rect_topk_host's on the exact fraction, equal fractions by ascending NEIGHBOUR index j -- one order
+ *              across both sides of the diagonal;
+ *   result   : for rows [row_begin, row_end), ascending, the first min(k, eligible) neighbours each; the neighbours come from
+ *              the whole table.
+ * capacity / *count_out / MG_ERR_NOMEM as for mg_compare_rect_topk_host; (row_end - row_begin) * min(k, n - 1) always suffices.
+ * k == 0: MG_ERR_INVALID; k > MG_TOPK_MAX: MG_ERR_UNSUPPORTED; k > n - 1 is clamped; n <= 1 or an empty range: MG_OK, 0 records.
+ * The table must carry lengths.
+ * With a filter on, every unordered pair is compared once: the thresholded candidate lists of the WHOLE triangle are built and
+ * mirrored on the device (both rows of a pair get its entry) whatever the row range -- a caller that walks the table in row
+ * ranges pays that per call.  With the filters off, or where the list engine declines or is switched off, rows [row_begin,
+ * row_end) are compared against the whole table as a rect job (each pair of the range's square twice) and a row's own column
+ * is masked out.  Limits: one device (no sharded form), host output only (no *_dev form), k <= MG_TOPK_MAX, tables of fewer
+ * than 2^31 rows. */
+int mg_compare_tri_topk_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, int kmer_size,
+                             double kmer_space, double max_distance, double max_p_value, uint32_t k, mg_result *out_host,
+                             uint64_t capacity, uint64_t *count_out);
 /* Single-linkage clusters of the thresholded all-vs-all, found ON THE DEVICE (cluster.hip) -- `mash cluster`.  The reference
  * has no such command (its user feeds the lines of `mash triangle -E` to a union-find of their own); the definition stands on
  * those lines:

@@ -31,7 +31,7 @@ EXPORTS = [
     "mg_compare_tri_filter_host", "mg_compare_rect_filter_host", "mg_compare_tri_sparse_host", "mg_compare_rect_sparse_host", "mg_expand_tri_sparse",
     "mg_finish_tri_host", "mg_finish_rect_host", "mg_distance", "mg_p_value",
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
-    "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host",
+    "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host", "mg_compare_tri_topk_host",
     "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
@@ -321,6 +321,7 @@ def load_library():
     lib.mg_compare_tri_results_host.argtypes = [vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
     lib.mg_compare_rect_results_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
     lib.mg_compare_rect_topk_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
+    lib.mg_compare_tri_topk_host.argtypes = [vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_comm_create_local.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
     lib.mg_comm_unique_id.argtypes = [vp, C.c_size_t]
     lib.mg_comm_create_rank.argtypes = [vp, vp, C.c_size_t, i32, i32, C.POINTER(vp)]
@@ -981,6 +982,16 @@ class MashGpu:
             capacity = max(q_end - q_begin, 0) * max(min(int(topk), ref.rows), 0)
         return self._filter(lambda o, c, n: self.lib.mg_compare_rect_topk_host(
             self.ctx, ref.handle, qry.handle, q_begin, q_end, k, kmer_space, max_d, max_p, topk, o, c, n), capacity, RESULT_DTYPE)
+
+    def compare_tri_topk(self, table, k, kmer_space, topk, max_d=-1.0, max_p=-1.0, row_begin=0, row_end=None, capacity=None):
+        """per row of [row_begin, row_end) its `topk` nearest neighbours in the whole table (itself excluded) among the pairs that pass
+        the filters, chosen on the device: best first by the exact fraction numer/denom, equal fractions by neighbour index, rows
+        ascending; records {row, col = neighbour} of the unordered pair (mg_compare_tri_topk_host)"""
+        row_end = table.rows if row_end is None else min(row_end, table.rows)
+        if capacity is None:
+            capacity = max(row_end - row_begin, 0) * max(min(int(topk), table.rows - 1), 0)
+        return self._filter(lambda o, c, n: self.lib.mg_compare_tri_topk_host(
+            self.ctx, table.handle, row_begin, row_end, k, kmer_space, max_d, max_p, topk, o, c, n), capacity, RESULT_DTYPE)
 
     def cluster_tri_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0):
         """single-linkage clusters of the pairs compare_tri_results returns for the whole table, found on the device: (label u32[rows]

@@ -6,6 +6,7 @@ namespace mg { void index_dump_clocks(); }
 #endif
 #include "sort_bits.h"
 #include "topk_internal.h"
+#include "knn_internal.h"
 
 /* ------------------------------------------------------------------ comparing */
 
@@ -2549,9 +2550,9 @@ struct TopkBufs {
     DevBuf<unsigned long long> row_off, total;
     DevBuf<mg::FinishEdge> edges;
     explicit TopkBufs(mg_ctx *c) : a(c), sel(c), row_n(c), row_off(c), total(c), edges(c) {}
-    bool alloc(uint64_t nrows, uint32_t k, uint32_t s, uint64_t pairs, bool filtered)
+    bool alloc(uint64_t nrows, uint32_t k, uint32_t s, uint64_t pairs, bool masked)
     {
-        return (filtered ? a.alloc(pairs, s) : a.seen.alloc((uint64_t)s + 1) == hipSuccess) && sel.alloc(nrows * k) == hipSuccess &&
+        return (masked ? a.alloc(pairs, s) : a.seen.alloc((uint64_t)s + 1) == hipSuccess) && sel.alloc(nrows * k) == hipSuccess &&
                row_n.alloc(nrows) == hipSuccess && row_off.alloc(nrows) == hipSuccess && total.alloc(2) == hipSuccess &&
                edges.alloc(nrows * k) == hipSuccess;
     }
@@ -2562,19 +2563,31 @@ struct TopkBufs {
 // eligibility by finish_mark_kernel when a filter is on (f carries tables without any extra denominator row, as in
 // finish_survivors), the rows' best k, and only then -- the denominators of the selected are known -- the distance table and the
 // records.  *n_out: the records of these rows, always; they are written to out_host only when they fit `room`.
+// knn (mg_compare_tri_topk_host; nullptr: a rect job): the rows are rows of the columns' own table and a row is no neighbour of
+// itself.  knn->nbr set: f's counts are the mirror's segments (knn.hip) -- eligible entries only, so no pass A; the selection's
+// second key and the records' columns come from nbr.  knn->nbr == nullptr: a block of the matrix, the row's own column is cleared
+// from the eligibility ballots (a mask of ones first where no filter made one).
+struct KnnSel { const uint32_t *nbr; };
+
 static int topk_select_finish(mg_ctx *ctx, mg::FinishArgs f, const TopkBufs &b, const uint32_t *seg_base, const uint32_t *seg_cnt, uint32_t nrows,
-                              uint32_t k, const Cut &cut, uint64_t room, mg_result *out_host, uint64_t *n_out)
+                              uint32_t k, const Cut &cut, uint64_t room, mg_result *out_host, uint64_t *n_out, const KnnSel *knn = nullptr)
 {
     *n_out = 0;
     if (!nrows || !f.pairs) return MG_OK;
-    const bool filtered = cut.filtered();
+    const bool mirrored = knn && knn->nbr, no_self = knn && !knn->nbr;
+    const bool filtered = cut.filtered() && !mirrored;
     if (filtered) {
         b.a.bind(f);
         HIP_TRY(ctx, mg::launch_finish_mark(f, b.total + 1, ctx->stream));
     }
+    if (no_self) {
+        if (!filtered) HIP_TRY(ctx, hipMemsetAsync(b.a.masks, 0xFF, mg::finish_mask_words(f.pairs) * 8, ctx->stream));
+        HIP_TRY(ctx, mg::launch_knn_clear_self(b.a.masks, nrows, f.ncols, f.first_row, ctx->stream));
+    }
     mg::TopkArgs a{};
     a.counts = f.counts;
-    a.masks = filtered ? b.a.masks.p : nullptr;
+    a.masks = filtered || no_self ? b.a.masks.p : nullptr;
+    a.key = mirrored ? knn->nbr : nullptr;
     a.seg_base = seg_base;
     a.seg_cnt = seg_cnt;
     a.ncols = (uint32_t)f.ncols;
@@ -2587,7 +2600,7 @@ static int topk_select_finish(mg_ctx *ctx, mg::FinishArgs f, const TopkBufs &b, 
     std::vector<uint32_t> seen((size_t)f.s + 1);
     unsigned long long n = 0;
     HIP_TRY(ctx, hipMemsetAsync(b.a.seen, 0, seen.size() * 4, ctx->stream));
-    HIP_TRY(ctx, mg::launch_topk_select(a, ctx->stream));
+    HIP_TRY(ctx, mirrored ? mg::launch_topk_select_keyed(a, ctx->stream) : mg::launch_topk_select(a, ctx->stream));
     HIP_TRY(ctx, mg::launch_topk_scan(b.row_n, b.row_off, nrows, b.total, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&n, b.total, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(seen.data(), b.a.seen, seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2599,16 +2612,18 @@ static int topk_select_finish(mg_ctx *ctx, mg::FinishArgs f, const TopkBufs &b, 
     if (rc != MG_OK) return rc;
     f.lut_start = fb.d_start;
     f.lut = fb.d_lut;
-    HIP_TRY(ctx, mg::launch_topk_finish(f, a, b.row_off, b.edges, ctx->stream));
+    HIP_TRY(ctx, mirrored ? mg::launch_knn_finish(f, a, knn->nbr, b.row_off, b.edges, ctx->stream)
+                          : mg::launch_topk_finish(f, a, b.row_off, b.edges, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_host, b.edges, n * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (!fb.complete) patch_nan_distances(out_host, n, cut.k);
     return MG_OK;
 }
 
-// queries [rb, re): few enough that rows * k records fit the device buffers
+// queries [rb, re): few enough that rows * k records fit the device buffers.  no_self (mg_compare_tri_topk_host's matrix route, rows
+// == cols): the matrix always, a row's own column masked out -- the lists of a rect job know nothing of the diagonal
 static int topk_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, const Cut &cut, uint32_t k, uint64_t capacity,
-                      mg_result *out_host, uint64_t *n_out)
+                      mg_result *out_host, uint64_t *n_out, bool no_self = false)
 {
     *n_out = 0;
     OutRange R;
@@ -2628,15 +2643,16 @@ static int topk_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, u
     TopkBufs tb(ctx);
     CutBufs bufs(ctx, ctx);
     Room room{capacity};
-    rc = cut_counts(ctx, R, cut, filtered, {1ull << 26, "MASHGPU_TOPK_BLOCK_PAIRS", "top-k", 1ull << 31}, bufs,
+    const KnnSel self{nullptr};
+    rc = cut_counts(ctx, R, cut, filtered && !no_self, {1ull << 26, "MASHGPU_TOPK_BLOCK_PAIRS", "top-k", 1ull << 31}, bufs,
                     [&](uint64_t pairs, uint64_t nrows, uint64_t, bool lists) {        // (more candidates than a 32-bit index reaches: no lists)
-        return (!lists || pairs <= most) && tb.alloc(nrows, k, R.s, pairs, filtered) ? MG_OK : kAllocFailed;
+        return (!lists || pairs <= most) && tb.alloc(nrows, k, R.s, pairs, filtered || no_self) ? MG_OK : kAllocFailed;
     },
                     [&] { tb.release(); },
                     [&](const mg::FinishArgs &f, const RowBlock &b, const CandLists *L) -> int {
         uint64_t n = 0;
         const int rcf = topk_select_finish(ctx, f, tb, L ? L->base.p : nullptr, L ? L->byrow.p : nullptr, (uint32_t)(b.r2 - b.r), k, cut, room.left(),
-                                           room.at(out_host), &n);
+                                           room.at(out_host), &n, no_self ? &self : nullptr);
         room.total += n;
         return rcf;
     });
@@ -2666,6 +2682,131 @@ int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *
     for (uint64_t q0 = q_begin; q0 < q_end; q0 += step) {
         uint64_t n = 0;
         const int rc = topk_range(ctx, qry, ref, q0, std::min(q_end, q0 + step), cut, k, room.left(), room.at(out_host), &n);
+        if (rc != MG_OK) return rc;
+        room.total += n;
+    }
+    *count_out = room.total;
+    if (room.total > capacity) return fail(ctx, MG_ERR_NOMEM, "top-k: more records than `capacity` (see *count_out)");
+    return MG_OK;
+}
+
+
+/* ------------------------------------------------- the k nearest neighbours of every row of a triangle (knn.hip) */
+
+// What the list route keeps on the device for one call: the whole triangle's candidate lists, pass A's ballots over them, and
+// their mirror
+struct KnnBufs {
+    CandLists L;
+    PassABufs pa;
+    FinishTables fa;
+    DevBuf<unsigned long long> n;
+    DevBuf<uint32_t> deg, base, cur, block_sum, nbr;
+    DevBuf<uint2> counts;
+    explicit KnnBufs(mg_ctx *c) : L(c), pa(c), fa(c), n(c), deg(c), base(c), cur(c), block_sum(c), nbr(c), counts(c) {}
+    void release()
+    {
+        L.release(); pa.release(); n.free(); deg.free(); base.free(); cur.free(); block_sum.free(); nbr.free(); counts.free();
+    }
+};
+
+// The list route's first half: every unordered pair of t compared once (cand_lists over the whole triangle), pass A over the
+// list, and the eligible entries mirrored into row-major segments (B.base / B.deg, B.counts / B.nbr).  *ok false: no lists -- the
+// engine declines or is switched off, 2 * eligible does not fit the selection's 32-bit indices, or the device has no room -- and
+// nothing is left on the device: the matrix route does the job.  *entries: 2 * eligible.
+static int knn_mirror(mg_ctx *ctx, const mg_table *t, const Cut &cut, KnnBufs &B, bool *ok, uint64_t *entries)
+{
+    *ok = false;
+    *entries = 0;
+    OutRange R;
+    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
+    if (rc != MG_OK) return rc;
+    const uint32_t n = (uint32_t)t->n;
+    bool lists = false;
+    rc = cand_lists(ctx, R, B.L, &lists, [&](uint64_t K, size_t &) { return B.pa.alloc(K, R.s) && B.n.alloc(1) == hipSuccess; });
+    if (rc != MG_OK) return rc;
+    if (!lists) { B.release(); return MG_OK; }
+    if (B.L.K == 0) { *ok = true; return MG_OK; }             // no two rows share a hash: nobody has an eligible neighbour
+    if ((rc = build_finish_tables(ctx, R.s, cut, {}, B.fa)) != MG_OK) return rc;
+    mg::FinishArgs f = finish_args(R.rows, R.cols, R.s, true, B.L.cnt, B.L.K, 0, B.fa, cut);
+    f.list_rc = B.L.rc;
+    B.pa.bind(f);
+    unsigned long long eligible = 0;
+    HIP_TRY(ctx, hipMemsetAsync(B.pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+    HIP_TRY(ctx, mg::launch_finish_mark(f, B.n, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&eligible, B.n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (eligible == 0) { *ok = true; return MG_OK; }
+    // the selection's indices into the segments are 32-bit and its streaming loop steps past a row's end by up to one chunk
+    if (2 * eligible >= 0xFFFFFFFFull - mg::TOPK_CHUNK || B.deg.alloc((uint64_t)n + 1) != hipSuccess || B.base.alloc((uint64_t)n + 1) != hipSuccess ||
+        B.cur.alloc(n) != hipSuccess || B.block_sum.alloc(mg::knn_scan_blocks(n)) != hipSuccess || B.nbr.alloc(2 * eligible) != hipSuccess ||
+        B.counts.alloc(2 * eligible) != hipSuccess) {
+        (void)hipGetLastError();
+        B.release();
+        return MG_OK;
+    }
+    mg::KnnMirror m{};
+    m.rc = B.L.rc;
+    m.cnt = B.L.cnt;
+    m.masks = B.pa.masks;
+    m.K = B.L.K;
+    m.n = n;
+    m.deg = B.deg;
+    m.base = B.base;
+    m.cur = B.cur;
+    m.block_sum = B.block_sum;
+    m.sym_counts = B.counts;
+    m.sym_nbr = B.nbr;
+    HIP_TRY(ctx, mg::launch_knn_degree(m, ctx->stream));
+    HIP_TRY(ctx, mg::launch_knn_scan(m, ctx->stream));
+    HIP_TRY(ctx, mg::launch_knn_scatter(m, ctx->stream));
+    *ok = true;
+    *entries = 2 * eligible;
+    return MG_OK;
+}
+
+int mg_compare_tri_topk_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, int kmer_size, double kmer_space,
+                             double max_distance, double max_p_value, uint32_t k, mg_result *out_host, uint64_t capacity, uint64_t *count_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!t || !count_out || (!out_host && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_topk_host: NULL argument");
+    *count_out = 0;
+    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_topk_host: the table carries no lengths");
+    if (k == 0) return fail(ctx, MG_ERR_INVALID, "mg_compare_tri_topk_host: k is 0");
+    if (k > MG_TOPK_MAX) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_compare_tri_topk_host: k exceeds MG_TOPK_MAX");
+    if (kmer_size < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    row_end = std::min(row_end, t->n);
+    if (row_begin >= row_end || t->n <= 1) return MG_OK;
+    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_compare_tri_topk_host: more than 2^31 - 1 rows");
+    k = (uint32_t)std::min<uint64_t>(k, t->n - 1);
+    uint64_t step = std::max<uint64_t>(1, (1ull << 24) / k);                // at most 2^24 records (512 MiB) on the device at a time
+    if (const char *o = ctx_opt(ctx, "MASHGPU_KNN_ROWS")) step = std::min(step, std::max<uint64_t>(1, strtoull(o, nullptr, 10)));
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    // Lists only with a filter on, for topk_range's reasons: with the filters off a row is completed by its numer = 0 pairs in index order
+    KnnBufs B(ctx);
+    bool mirrored = false;
+    uint64_t entries = 0;
+    if (cut.filtered()) {
+        const int rc = knn_mirror(ctx, t, cut, B, &mirrored, &entries);
+        if (rc != MG_OK) return rc;
+        if (mirrored && !entries) return MG_OK;
+    }
+    TopkBufs tb(ctx);
+    if (mirrored && !tb.alloc(std::min(step, row_end - row_begin), k, (uint32_t)t->s, 0, false))
+        return fail(ctx, MG_ERR_NOMEM, "top-k: device allocation failed");
+    const KnnSel sel{B.nbr};
+    Room room{capacity};
+    for (uint64_t r0 = row_begin; r0 < row_end; r0 += step) {
+        const uint64_t r1 = std::min(row_end, r0 + step);
+        uint64_t n = 0;
+        int rc;
+        if (mirrored) {
+            // (the finish reads no filter table: the tables of pass A serve until topk_select_finish builds the selected rows' own)
+            const mg::FinishArgs f = finish_args(t, t, (uint32_t)t->s, true, B.counts, entries, r0, B.fa, cut);
+            rc = topk_select_finish(ctx, f, tb, B.base + r0, B.deg + r0, (uint32_t)(r1 - r0), k, cut, room.left(), room.at(out_host), &n, &sel);
+        } else {
+            rc = topk_range(ctx, t, t, r0, r1, cut, k, room.left(), room.at(out_host), &n, true);
+        }
         if (rc != MG_OK) return rc;
         room.total += n;
     }

@@ -15,6 +15,10 @@
 // (a matrix row, a row of the candidate lists) hold a row's pairs in column order, so position order IS reference-index order,
 // and it is unique -- the order is strict, any sorting network realises it, and a tie across the k-th place is cut in column
 // order by the same comparison, not by a separate pass.
+// THE KEYED FORM (template parameter KEYED, launch_topk_select_keyed; knn.hip's mirrored triangle): the second key is key[idx],
+// unique within a row, read beside the counts -- a segment may then hold its pairs in ANY order and the answer is the same.  The
+// long kernel keeps the position beside the key (one more uint32_t[TOPK_BUF] of LDS, 32 KB in all) to report `sel`.  KEYED = false
+// is the code above and below unchanged: no key array is declared or touched.
 //
 // SELECTION, short segments (topk_select_short_kernel, a wave per row of up to 64 pairs): see the kernel.
 // SELECTION, long segments (topk_select_kernel, one workgroup of 256 per row).  The row is streamed once, coalesced, 1024 pairs at a time.
@@ -49,7 +53,8 @@ __device__ __forceinline__ bool topk_before(const TopkEnt &a, const TopkEnt &b)
 
 // buf[0 .. n) -> sorted best first, by a bitonic network over P = the power of two >= n (places n .. P filled with an entry that
 // ranks after every real one).  Uniform: every work-item calls it with the same n.  Ends behind a barrier.
-__device__ void topk_sort(uint32_t *bn, uint32_t *bd, uint32_t *bp, uint32_t n)
+template <bool KEYED>
+__device__ void topk_sort(uint32_t *bn, uint32_t *bd, uint32_t *bp, uint32_t *bq, uint32_t n)
 {
     uint32_t P = 2;
     while (P < n) P <<= 1;
@@ -64,6 +69,7 @@ __device__ void topk_sort(uint32_t *bn, uint32_t *bd, uint32_t *bp, uint32_t n)
                 if (up ? topk_before(y, x) : topk_before(x, y)) {
                     bn[i] = y.numer; bd[i] = y.denom; bp[i] = y.pos;
                     bn[j] = x.numer; bd[j] = x.denom; bp[j] = x.pos;
+                    if constexpr (KEYED) { const uint32_t q = bq[i]; bq[i] = bq[j]; bq[j] = q; }
                 }
             }
             __syncthreads();
@@ -73,6 +79,7 @@ __device__ void topk_sort(uint32_t *bn, uint32_t *bd, uint32_t *bp, uint32_t n)
 // Short segments (n <= TOPK_SHORT = 64, most rows of a candidate list): a wave per row, a lane per pair, no LDS and no barrier.
 // A pair's place in the row's list is the number of eligible pairs that rank before it -- the order is strict, so the places of
 // the eligible pairs are 0, 1, 2, ... without a gap -- and the pairs with a place below k are the answer.
+template <bool KEYED>
 __global__ __launch_bounds__(TOPK_NT) void topk_select_short_kernel(TopkArgs a)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -89,10 +96,11 @@ __global__ __launch_bounds__(TOPK_NT) void topk_select_short_kernel(TopkArgs a)
         e.numer = c.x;
         e.denom = c.y;
         if (a.masks) elig = (a.masks[idx >> 6] >> (idx & 63u)) & 1ull;
+        if constexpr (KEYED) e.pos = a.key[idx];
     }
     uint32_t place = 0;
     for (uint32_t l = 0; l < n; l++) {
-        const TopkEnt o{__shfl(e.numer, l), __shfl(e.denom, l), l};
+        const TopkEnt o{__shfl(e.numer, l), __shfl(e.denom, l), KEYED ? __shfl(e.pos, l) : l};
         const uint32_t oe = __shfl((uint32_t)elig, l);
         if (oe && topk_before(o, e)) place++;
     }
@@ -107,9 +115,11 @@ __global__ __launch_bounds__(TOPK_NT) void topk_select_short_kernel(TopkArgs a)
     }
 }
 
+template <bool KEYED>
 __global__ __launch_bounds__(TOPK_NT) void topk_select_kernel(TopkArgs a)
 {
     __shared__ uint32_t bn[TOPK_BUF], bd[TOPK_BUF], bp[TOPK_BUF];
+    __shared__ uint32_t bq[KEYED ? TOPK_BUF : 1];                         // KEYED: bp holds the key, bq the position
     __shared__ uint32_t fill;                                             // entries in the buffer
     const uint32_t row = blockIdx.x, lane = threadIdx.x & 63u;
     const unsigned long long begin = a.seg_base ? a.seg_base[row] : (unsigned long long)row * a.ncols;
@@ -121,6 +131,7 @@ __global__ __launch_bounds__(TOPK_NT) void topk_select_kernel(TopkArgs a)
     TopkEnt bound{0, 1, 0};
     for (uint32_t c0 = 0; c0 < n; c0 += TOPK_CHUNK) {                     // (uniform)
         uint2 c[4];
+        uint32_t key[KEYED ? 4 : 1];
         bool take[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {                                     // four loads in flight per lane
@@ -131,12 +142,14 @@ __global__ __launch_bounds__(TOPK_NT) void topk_select_kernel(TopkArgs a)
                 const unsigned long long idx = begin + pos;
                 c[j] = a.counts[idx];
                 if (a.masks) take[j] = (a.masks[idx >> 6] >> (idx & 63u)) & 1ull;
+                if constexpr (KEYED) key[j] = a.key[idx];
             }
         }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t pos = c0 + (uint32_t)j * TOPK_NT + threadIdx.x;
-            const TopkEnt e{c[j].x, c[j].y, pos};
+            TopkEnt e{c[j].x, c[j].y, pos};
+            if constexpr (KEYED) e.pos = take[j] ? key[j] : 0u;
             const bool t = take[j] && (!bounded || topk_before(e, bound));
             const unsigned long long m = __ballot(t);
             uint32_t at = 0;
@@ -145,13 +158,14 @@ __global__ __launch_bounds__(TOPK_NT) void topk_select_kernel(TopkArgs a)
             if (t) {
                 at += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
                 bn[at] = e.numer; bd[at] = e.denom; bp[at] = e.pos;
+                if constexpr (KEYED) bq[at] = pos;
             }
         }
         __syncthreads();
         const uint32_t f = fill;
         __syncthreads();                                                  // (nobody adds to `fill` before all have read it)
         if (f > TOPK_BUF - TOPK_CHUNK || (!bounded && f >= a.k)) {        // (uniform) prune: sort, keep k, renew the bound
-            topk_sort(bn, bd, bp, f);
+            topk_sort<KEYED>(bn, bd, bp, bq, f);
             if (f >= a.k) {
                 bounded = true;
                 bound = TopkEnt{bn[a.k - 1], bd[a.k - 1], bp[a.k - 1]};
@@ -163,25 +177,34 @@ __global__ __launch_bounds__(TOPK_NT) void topk_select_kernel(TopkArgs a)
     }
     const uint32_t f = fill;
     __syncthreads();
-    if (f > 1) topk_sort(bn, bd, bp, f);
+    if (f > 1) topk_sort<KEYED>(bn, bd, bp, bq, f);
     const uint32_t keep = f < a.k ? f : a.k;
     for (uint32_t j = threadIdx.x; j < keep; j += TOPK_NT) {
-        a.sel[(unsigned long long)row * a.k + j] = (uint32_t)(begin + bp[j]);
+        a.sel[(unsigned long long)row * a.k + j] = (uint32_t)(begin + (KEYED ? bq[j] : bp[j]));
         if (a.denom_seen && bd[j] <= a.s) a.denom_seen[bd[j]] = 1u;
     }
     if (threadIdx.x == 0) a.row_n[row] = keep;
 }
 
-hipError_t launch_topk_select(const TopkArgs &a, hipStream_t stream)
+template <bool KEYED>
+static hipError_t topk_select_launch(const TopkArgs &a, hipStream_t stream)
 {
     if (a.nrows == 0) return hipSuccess;
     if (a.k == 0 || a.k > TOPK_MAX || a.nrows > 0x7FFFFFFFu) return hipErrorInvalidValue;
     // a matrix block has rows of one length; a candidate list has both kinds, and each kernel leaves the other's rows alone
     if (a.seg_cnt || a.ncols <= TOPK_SHORT)
-        hipLaunchKernelGGL(topk_select_short_kernel, dim3((a.nrows + TOPK_NT / 64u - 1u) / (TOPK_NT / 64u)), dim3(TOPK_NT), 0, stream, a);
+        hipLaunchKernelGGL(topk_select_short_kernel<KEYED>, dim3((a.nrows + TOPK_NT / 64u - 1u) / (TOPK_NT / 64u)), dim3(TOPK_NT), 0, stream, a);
     if (a.seg_cnt || a.ncols > TOPK_SHORT)
-        hipLaunchKernelGGL(topk_select_kernel, dim3(a.nrows), dim3(TOPK_NT), 0, stream, a);
+        hipLaunchKernelGGL(topk_select_kernel<KEYED>, dim3(a.nrows), dim3(TOPK_NT), 0, stream, a);
     return hipGetLastError();
+}
+
+hipError_t launch_topk_select(const TopkArgs &a, hipStream_t stream) { return topk_select_launch<false>(a, stream); }
+
+hipError_t launch_topk_select_keyed(const TopkArgs &a, hipStream_t stream)
+{
+    if (!a.key || !a.seg_base || !a.seg_cnt) return hipErrorInvalidValue;
+    return topk_select_launch<true>(a, stream);
 }
 
 #ifndef MG_HIP_EMU

@@ -29,9 +29,13 @@ struct TopkArgs {
     uint32_t *row_n;                   // [nrows] min(k, eligible)
     uint32_t *denom_seen;              // [s + 1] denominators of the selected (for the distance table); may be nullptr
     uint32_t s;
+    const uint32_t *key;               // launch_topk_select_keyed only: pair idx's second key, unique within its row (else nullptr)
 };
 
 hipError_t launch_topk_select(const TopkArgs &a, hipStream_t stream);
+// the same selection with equal fractions by ascending key[idx] instead of by position: a row's pairs may lie in any order
+// (candidate-list layout only: seg_base and seg_cnt are set)
+hipError_t launch_topk_select_keyed(const TopkArgs &a, hipStream_t stream);
 
 #ifndef MG_HIP_EMU
 // row_off = exclusive scan of row_n, *total = its sum (one workgroup)

@@ -1367,18 +1367,23 @@ int cmd_triangle(int argc, const char **argv)
     c.add("edge", Opt::Boolean, "E");
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "1.0", 0., 1.);
+    c.add("nearest", Opt::Integer, "N", "", 1, (float)MG_TOPK_MAX);          // (not in the reference)
     c.use_sketch_options();
     if (c.parse(argc, argv)) return 1;
     if (c.args.empty() || c.o("help").active) {
         cout << "\nUsage:\n\n  mash triangle [options] <seq1> [<seq2>] ...\n\n"
                 "Lower-triangular distance matrix in relaxed Phylip format (or -E edge list).\n"
-                "Options: -l -C -E -v <max p> -d <max dist> and the sketch options of `mash sketch`.\n\n";
+                "Options: -l -C -E -v <max p> -d <max dist> -N <int> and the sketch options of `mash sketch`.\n"
+                "  -N <int>  Per sketch, in input order, at most <int> edge-list lines (1-" << MG_TOPK_MAX << "): its nearest neighbours among the other\n"
+                "            sketches that pass -d and -v, best first by shared-hashes as an exact fraction, equal fractions in input\n"
+                "            order.  Implies -E; a pair can appear under both its sketches.\n\n";
         return 0;
     }
+    const uint32_t nearest = c.o("nearest").active ? (uint32_t)c.o("nearest").num : 0;
     const bool comment = c.o("comment").active;
     bool edge = c.o("edge").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
-    if (c.o("pvalue").active || c.o("distance").active) edge = true;
+    if (c.o("pvalue").active || c.o("distance").active || nearest) edge = true;
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // CommandTriangle.cpp:74-77
@@ -1405,6 +1410,65 @@ int cmd_triangle(int argc, const char **argv)
     uint64_t r0 = 1;
     StageClock clk;
     FastOut out;
+    if (nearest) {
+        // -N: per sketch its nearest neighbours, ranked and cut on the device (mg_compare_tri_topk_host; one device: the first of
+        // those selected): N records per sketch cross PCIe.  MASH_AMD_HOST_FINISH=1: the triangle of counts, the host tail, both
+        // rows of a passing pair note it, and the same selection here.
+        vector<mg_result> res;
+        const uint64_t keep = std::min<uint64_t>(nearest, n - 1);
+        if (!keep) { mg_dtable_free(dt); return 0; }
+        auto emit = [&] {
+            emit_rows(out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
+                const mg_result &e = res[x];
+                o << label(set.refs[e.row]) << '\t' << label(set.refs[e.col]) << '\t' << e.distance << '\t' << e.p_value << '\t' << e.numer << '/'
+                  << e.denom;
+                o.eol();
+            });
+        };
+        if (!host_finish_wanted()) {
+            const uint64_t nblock = std::max<uint64_t>(1, (1ull << 24) / keep);
+            for (uint64_t b0 = 0; b0 < n; b0 += nblock) {
+                const uint64_t b1 = std::min(n, b0 + nblock);
+                if (res.size() < (b1 - b0) * keep) res.resize((b1 - b0) * keep);                // the largest possible answer: one call
+                if (!fetch_results(gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *cnt) {
+                        return mg_compare_tri_topk_host(gpu.ctx, t, b0, b1, set.p.kmer, kspace, d_max, p_max, nearest, o, cap, cnt); }))
+                    return 1;
+                emit();
+            }
+        } else {
+            vector<vector<mg_result>> rows(n);                     // a row's passing pairs as {row, neighbour, ...}
+            while (r0 < n) {
+                uint64_t r1 = r0, npairs = 0;
+                while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 24))) { npairs += r1; r1++; }
+                counts.resize(npairs);
+                pairs.resize(npairs);
+                if (mg_compare_tri_sharded_host(gpu.comm, dt, r0, r1, counts.data()) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; return 1; }
+                mg_finish_tri_host(counts.data(), lengths.data(), r0, r1, set.p.kmer, kspace, d_max, p_max, pairs.data());
+                uint64_t idx = 0;
+                for (uint64_t i = r0; i < r1; i++)
+                    for (uint64_t j = 0; j < i; j++, idx++) {
+                        const mg_pair &a = pairs[idx];
+                        if (!a.pass) continue;
+                        rows[i].push_back(mg_result{(uint32_t)i, (uint32_t)j, a.numer, a.denom, a.distance, a.p_value});
+                        rows[j].push_back(mg_result{(uint32_t)j, (uint32_t)i, a.numer, a.denom, a.distance, a.p_value});
+                    }
+                r0 = r1;
+            }
+            res.clear();
+            for (vector<mg_result> &row : rows) {
+                const size_t take = std::min<size_t>(row.size(), keep);
+                std::partial_sort(row.begin(), row.begin() + (ptrdiff_t)take, row.end(), [](const mg_result &a, const mg_result &b) {
+                    const uint64_t l = (uint64_t)a.numer * (b.denom ? b.denom : 1u), r = (uint64_t)b.numer * (a.denom ? a.denom : 1u);
+                    return l > r || (l == r && a.col < b.col);    // the order of mg_compare_tri_topk_host
+                });
+                res.insert(res.end(), row.begin(), row.begin() + (ptrdiff_t)take);
+            }
+            emit();
+        }
+        mg_dtable_free(dt);
+        if (w.count > 0 && !p.reads) warn_kmer_size(set, w);
+        return 0;
+    }
     if (edge && edge_filter_wanted(d_max, p_max)) {
         vector<mg_edge> edges;
         vector<mg_result> res;
