@@ -529,3 +529,224 @@ def check_tri_case_conditions(name, case, numer, denom, dist, pval):
         assert 0.08 * s < np.percentile(numer, 1) and np.percentile(numer, 99) < 0.6 * s      # 37 .. 102 of 256
     else:
         raise AssertionError(name)
+
+
+# ---------------------------------------------------------------------------------------------- screen probes against the oracle
+#
+# `mash screen` counts, for every hash of every database row, how often the mixture holds a k-mer of that hash.  The judge hashes
+# every valid k-mer of the mixture with the oracle and counts; the cases below steer the fused sketch + probe kernel onto the
+# paths that exist to keep a k-mer from being counted twice (a steady tile that overflows the candidate buffer, a seeded batch
+# that comes out short and is run again).  tests/test_screen_probe_oracle.py asserts, on the oracle's output alone, that they do.
+
+SCREEN_PROTEIN = "ACDEFGHIKLMNPQRSTVWY"
+RECORD_SEP = b"\n"                                                         # MG_RECORD_SEP (include/mashgpu.h)
+
+
+def _all_kmer_hashes(oracle, records, p):
+    bases = np.frombuffer(b"".join(records), dtype=np.uint8).copy()       # (the oracle upper-cases in place)
+    off = np.zeros(len(records) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in records], dtype=np.uint64)
+    return oracle.kmer_hashes(bases, off, p).copy()
+
+
+def screen_batch_hashes(oracle, params_kw, records, translate=False):
+    """the hash of every valid k-mer of one batch, occurrences repeated (translate: of every frame of six_frames(record))"""
+    if translate:
+        records = [fr for r in records for fr in oracle.six_frames(r)]
+    return _all_kmer_hashes(oracle, records, oracle.params(**params_kw))
+
+
+def screen_expected(oracle, params_kw, batches, translate=False):
+    """What a screen of the mixture `batches` (lists of records) must report, by the oracle alone:
+    (counts: dict hash -> occurrences over every record of every batch, mix: u64[<= s], the s smallest distinct hashes)."""
+    parts = [screen_batch_hashes(oracle, params_kw, recs, translate) for recs in batches]
+    allh = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+    u, c = np.unique(allh, return_counts=True)
+    return dict(zip(u.tolist(), c.tolist())), u[: params_kw.get("s", 1000)].copy()
+
+
+def screen_expected_rows(counts, table, nhash):
+    """the dense u32[n, s] result of the database (table, nhash) out of screen_expected's dict: zero behind a row's nhash"""
+    out = np.zeros(table.shape, dtype=np.uint32)
+    for i in range(table.shape[0]):
+        out[i, : nhash[i]] = [counts.get(h, 0) for h in table[i, : nhash[i]].tolist()]
+    return out
+
+
+def hits_equal_counts(hits, counts, table, nhash):
+    """tests/test_gpu_parity.py's _hits_equal_counts: hits == the non-zero cells of the dense counts matrix, hash values included,
+    ordered by row then hash"""
+    from mash_amd import abi
+    r, c = np.nonzero(counts)
+    assert len(hits) == len(r)
+    want = np.zeros(len(r), dtype=abi.HIT_DTYPE)
+    want["row"], want["count"], want["hash"] = r, counts[r, c], table[r, c]
+    want = want[np.lexsort((want["hash"], want["row"]))]
+    assert np.array_equal(hits, want)
+
+
+def screen_db(oracle, case):
+    """the database of a case, sketched by the oracle: (table u64[n, s] padded, nhash u32[n], lengths u64[n])"""
+    kw = case["params"]
+    s = kw["s"]
+    p = oracle.params(**kw)
+    table = np.full((len(case["db"]), s), PAD, dtype=np.uint64)
+    nhash = np.zeros(len(case["db"]), dtype=np.uint32)
+    for i, recs in enumerate(case["db"]):
+        if i in case.get("db_six_frames", ()):                            # a nucleotide row of an amino-acid database
+            recs = [fr for r in recs for fr in oracle.six_frames(r)]
+        h = oracle.sketch_records(list(recs), p)[0]
+        table[i, : len(h)] = h
+        nhash[i] = len(h)
+    lengths = np.array([max(sum(len(r) for r in recs), 1) for recs in case["db"]], dtype=np.uint64)
+    return table, nhash, lengths
+
+
+def screen_blob(records):
+    """one batch as mg_screen_add_host takes it: the records joined with the separator"""
+    return np.frombuffer(RECORD_SEP.join(records), dtype=np.uint8)
+
+
+def screen_batch_npos(case, records):
+    """the k-mer starts the sketch kernel sees in one batch -- what seed_thresholds (host_sketch.cpp) calls npos: the joined bytes
+    are one sketch; a translated batch is six frames of nbases / 3 + 1 bytes each, rounded up to 16 (screen_add_translated,
+    host_screen.cpp)"""
+    nbases = len(RECORD_SEP.join(records))
+    if case["translate"]:
+        nbases = 6 * ((nbases // 3 + 1 + 15) & ~15)
+    return nbases - case["params"]["k"] + 1
+
+
+def _revcomp(b):
+    return bytes({65: 84, 67: 71, 71: 67, 84: 65, 78: 78}[x] for x in reversed(b))
+
+
+def _screen_reads(rng, genomes, n, lo=120, hi=150, fresh=2 / 3, revcomp=True):
+    """n reads of lo .. hi bases: `fresh` of them random sequence of their own, the others cut out of `genomes`; some with an N,
+    some lower case, half of them reverse complements.  (The fresh ones keep a batch's distinct k-mers above a third of its
+    k-mer starts: a batch of genome reads and a 10^5-base run alone comes out short of its seeded threshold and is run again.)"""
+    from workloads import synth
+    out = []
+    for _ in range(n):
+        l = int(rng.integers(lo, hi + 1))
+        if rng.random() < fresh:
+            r = bytearray(synth._rand_dna(rng, l))
+        else:
+            g = genomes[int(rng.integers(0, len(genomes)))]
+            st = int(rng.integers(0, len(g) - l))
+            r = bytearray(g[st:st + l])
+        u = rng.random()
+        if u < 0.2:
+            r[int(rng.integers(0, l))] = ord("N")
+        elif u < 0.35:
+            r = bytearray(bytes(r).lower())
+        out.append(bytes(r) if not revcomp or rng.random() < 0.5 else _revcomp(bytes(r).upper()))
+    return out
+
+
+def _screen_dna_parts():
+    """what every DNA case shares: four 30 kbp genomes (the last is never sampled) and the two repeat units"""
+    from workloads import synth
+    rng = np.random.default_rng(2024)
+    genomes = [synth._rand_dna(rng, 30000) for _ in range(4)]
+    return genomes, synth._rand_dna(rng, 700), synth._rand_dna(rng, 2500), synth._rand_dna(rng, 23)
+
+
+def _screen_dna_db(k):
+    """rows 0, 1: one hash, twice (rows that share a key each get their hit); row 2: the T run's hash (the same key when k-mers
+    are canonical); rows 3 .. 5: the genomes the reads come from; row 6: a genome never sampled; rows 7, 8: the two repeat units
+    with the k-mers across their seam (ragged rows where the unit has fewer than s distinct k-mers)"""
+    genomes, unit_small, unit_mid, _ = _screen_dna_parts()
+    return [[b"A" * 100], [b"A" * 100], [b"T" * 100]] + [[g] for g in genomes] + [[unit_small + unit_small[: k - 1]], [unit_mid + unit_mid[: k - 1]]]
+
+
+SCREEN_DNA_UNSAMPLED = (6,)
+
+# Hash seeds found by a search with the oracle (get_hash over seeds 1, 2, ...); test_screen_probe_oracle.py checks what they are for
+SCREEN_SEED_FLOOD = 6713            # hash64("A" * 21) at 7.4e-6 of the range
+SCREEN_SEED_FORWARD = 1490799       # hash32("A" * 16) at 8.8e-4 and hash32("T" * 16) at 7.0e-4 of the 32-bit range
+SCREEN_SEED_TRANSLATED = 87512      # hash32("K" * 7) at 3.4e-6 of the 32-bit range
+
+
+def _flood_batches(rng, genomes, unit23):
+    from workloads import synth
+    long_record = synth._rand_dna(rng, 3000) + b"A" * 50000 + synth._rand_dna(rng, 2000) + unit23 * 4000 + b"T" * 50000
+    one = _screen_reads(rng, genomes[:3], 1500) + [long_record] + _screen_reads(rng, genomes[:3], 500)
+    return [one, _screen_reads(rng, genomes[:3], 1500)]
+
+
+def screen_case_flood(s=1000):
+    """canonical 21-mers: 2 000 reads around one record with a run of 50 000 A, 4 000 copies of a 23-mer and a run of 50 000 T
+    (the A run's canonical key again); a second batch of reads only"""
+    genomes, _, _, unit23 = _screen_dna_parts()
+    rng = np.random.default_rng(301)
+    return {"params": {"k": 21, "s": s, "seed": SCREEN_SEED_FLOOD}, "translate": False, "db": _screen_dna_db(21),
+            "batches": _flood_batches(rng, genomes, unit23), "runs": [(0, b"A" * 21, 50000 - 20), (0, b"T" * 21, 50000 - 20)],
+            "short": {}, "hot": 10000, "unsampled": SCREEN_DNA_UNSAMPLED}
+
+
+def screen_case_flood_wide():
+    """screen_case_flood at s = 3000: the NT = 1024 kernels, tiles of 28 672; the runs are 100 000 long"""
+    from workloads import synth
+    genomes, _, _, unit23 = _screen_dna_parts()
+    rng = np.random.default_rng(302)
+    long_record = synth._rand_dna(rng, 3000) + b"A" * 100000 + synth._rand_dna(rng, 2000) + unit23 * 4000 + b"T" * 100000
+    one = _screen_reads(rng, genomes[:3], 2500) + [long_record] + _screen_reads(rng, genomes[:3], 1000)
+    return {"params": {"k": 21, "s": 3000, "seed": SCREEN_SEED_FLOOD}, "translate": False, "db": _screen_dna_db(21),
+            "batches": [one, _screen_reads(rng, genomes[:3], 1500)], "runs": [(0, b"A" * 21, 100000 - 20), (0, b"T" * 21, 100000 - 20)],
+            "short": {}, "hot": 10000, "unsampled": SCREEN_DNA_UNSAMPLED}
+
+
+def screen_case_flood_forward():
+    """forward-only 16-mers (MODE 1, 32-bit hashes): the A run and the T run are different keys"""
+    genomes, _, _, unit23 = _screen_dna_parts()
+    rng = np.random.default_rng(303)
+    return {"params": {"k": 16, "s": 1000, "seed": SCREEN_SEED_FORWARD, "noncanonical": True}, "translate": False, "db": _screen_dna_db(16),
+            "batches": _flood_batches(rng, genomes, unit23), "runs": [(0, b"A" * 16, 50000 - 15), (0, b"T" * 16, 50000 - 15)],
+            "short": {}, "hot": 10000, "unsampled": SCREEN_DNA_UNSAMPLED}
+
+
+def screen_case_flood_translated():
+    """amino-acid 7-mers against a nucleotide mixture translated in six frames: 150 000 A give a run of 50 000 K in each forward
+    frame.  Rows 0 .. 2: the six frames of three 9 kbp genomes (the last never sampled, but random sequence meets some of its
+    7-mers by chance); rows 3, 4: the sketch of K * 50, twice; row 5: a peptide of M and W, one codon each, which random
+    sequence does not meet (a ragged row: at most 2^7 k-mers)."""
+    from workloads import synth
+    rng = np.random.default_rng(304)
+    genomes = [synth._rand_dna(rng, 9000) for _ in range(3)]
+    rare = np.frombuffer(b"MW", dtype=np.uint8)[rng.integers(0, 2, 400)].tobytes()
+    reads = lambda n: _screen_reads(rng, genomes[:2], n, lo=150, hi=300, fresh=3 / 4)
+    one = reads(1200) + [b"AC", b"A" * 150000, b""] + reads(700)
+    return {"params": {"k": 7, "s": 300, "seed": SCREEN_SEED_TRANSLATED, "alphabet": SCREEN_PROTEIN, "noncanonical": True}, "translate": True,
+            "db": [[g] for g in genomes] + [[b"K" * 50], [b"K" * 50], [rare]], "db_six_frames": (0, 1, 2),
+            "batches": [one, reads(600)], "runs": [(0, b"K" * 7, 50000 - 6)], "short": {}, "hot": 10000, "unsampled": (5,)}
+
+
+def screen_case_short():
+    """canonical 21-mers, three batches: 400 copies of a 700-base unit (fewer than s distinct k-mers), 120 copies of a 2 500-base
+    unit (s distinct k-mers, but next to none below the seeded threshold), ordinary reads"""
+    genomes, unit_small, unit_mid, _ = _screen_dna_parts()
+    rng = np.random.default_rng(305)
+    return {"params": {"k": 21, "s": 1000, "seed": SCREEN_SEED_FLOOD}, "translate": False, "db": _screen_dna_db(21),
+            "batches": [[unit_small * 400], [unit_mid * 120], _screen_reads(rng, genomes[:3], 1500)], "runs": [],
+            "short": {0: "a", 1: "b"}, "hot": 100, "unsampled": SCREEN_DNA_UNSAMPLED}
+
+
+def screen_case_batch_edges():
+    """canonical 21-mers, batches at the edges of the batch format: shorter than k, exactly k bytes (one k-mer, a database key),
+    k bytes with a separator among them (one k-mer start, no k-mer), separators first and last, empty records, nothing but
+    separators"""
+    genomes, _, _, _ = _screen_dna_parts()
+    rng = np.random.default_rng(306)
+    r = lambda n: _screen_reads(rng, genomes[:3], n, fresh=0.0)
+    return {"params": {"k": 21, "s": 1000, "seed": SCREEN_SEED_FLOOD}, "translate": False, "db": _screen_dna_db(21),
+            "batches": [[b"ACGTACGTAC"], [b"A" * 21], [b"A" * 10, b"C" * 10], [b""] + r(40) + [b""], r(3) + [b"", b""] + r(20) + [b""] + r(7),
+                        [b"", b"", b""], [b"", b"", genomes[0][500:521], b"", b""]],
+            "runs": [], "short": {}, "hot": None, "unsampled": SCREEN_DNA_UNSAMPLED}
+
+
+SCREEN_CASES = ("flood", "flood_wide", "flood_forward", "flood_translated", "short", "batch_edges")
+
+
+def screen_case(name):
+    return globals()["screen_case_" + name]()
