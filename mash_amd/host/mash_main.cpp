@@ -408,7 +408,9 @@ struct StageClock {
     ~StageClock()
     {
         if (!on) return;
-        lap("teardown");                             // (declared before the Gpu: its destruction is in here)
+        // (where the clock is declared before the Gpu -- sketch, screen -- the Gpu's destruction is in here; in triangle
+        //  and cluster it is declared after it: the lap ends with the tables freed and the last lines written)
+        lap("teardown");
         cerr << "timing:";
         for (auto &a : acc) cerr << ' ' << a.first << ' ' << a.second << " s;";
         cerr << endl;
@@ -899,6 +901,14 @@ void warn_kmer_size(const SketchSet &set, const KmerWarning &w)
          << w.k_min << " is required. See: -k, -w." << endl << endl;
 }
 
+// the sharded calls record their error in the communicator, the calls on one context in that context
+int report_error(Gpu &gpu)
+{
+    const char *m = mg_comm_last_error(gpu.comm);
+    cerr << "ERROR: " << ((m && *m) ? m : mg_last_error(gpu.ctx)) << endl;
+    return 1;
+}
+
 // dense table upload
 // the same table on EVERY device of the communicator (host -> GPU 0 -> RCCL broadcast)
 mg_dtable *upload_all(Gpu &gpu, const SketchSet &set, uint64_t s, vector<uint64_t> *lengths_out = nullptr, bool by_rows = false)
@@ -916,10 +926,8 @@ mg_dtable *upload_all(Gpu &gpu, const SketchSet &set, uint64_t s, vector<uint64_
     mg_dtable *d = nullptr;
     // by_rows: the larger side of a rect job -- every GPU gets a block of its rows instead of a replica
     if ((by_rows ? mg_dtable_upload_rows(gpu.comm, h.data(), nh.data(), len.data(), n, s, &d)
-                 : mg_dtable_upload(gpu.comm, h.data(), nh.data(), len.data(), n, s, &d)) != MG_OK) {
-        cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl;
-        exit(1);
-    }
+                 : mg_dtable_upload(gpu.comm, h.data(), nh.data(), len.data(), n, s, &d)) != MG_OK)
+        exit(report_error(gpu));
     if (lengths_out) *lengths_out = len;
     return d;
 }
@@ -1064,13 +1072,23 @@ void emit_rows(FastOut &out, uint64_t r0, uint64_t r1, CostFn cost, RowFn fn)
     }
 }
 
-void print_pair_line(FastOut &out, const Ref &ref, const Ref &qry, bool comment, const mg_pair &pr)
+// One line of `mash dist` (writeOutput, CommandDistance.cpp:247-304)
+inline void print_pair_line(FastOut &out, const Ref &ref, const Ref &qry, bool comment, uint32_t numer, uint32_t denom, double distance, double p)
 {
     out << ref.name;
     if (comment) out << ':' << ref.comment;
     out << '\t' << qry.name;
     if (comment) out << ':' << qry.comment;
-    out << '\t' << pr.distance << '\t' << pr.p_value << '\t' << pr.numer << '/' << pr.denom;
+    out << '\t' << distance << '\t' << p << '\t' << numer << '/' << denom;
+    out.eol();
+}
+template <class Rec>                          // mg_pair, mg_result
+inline void print_pair_line(FastOut &out, const Ref &ref, const Ref &qry, bool comment, const Rec &r) { print_pair_line(out, ref, qry, comment, r.numer, r.denom, r.distance, r.p_value); }
+
+// One line of `mash triangle -E` (CommandTriangle.cpp:159-198)
+inline void print_edge_line(FastOut &out, const string &row_label, const string &col_label, uint32_t numer, uint32_t denom, double distance, double p)
+{
+    out << row_label << '\t' << col_label << '\t' << distance << '\t' << p << '\t' << numer << '/' << denom;
     out.eol();
 }
 
@@ -1081,38 +1099,19 @@ void print_pair_line(FastOut &out, const Ref &ref, const Ref &qry, bool comment,
 bool edge_filter_wanted(double d_max, double p_max) { return (d_max < 1.0 || p_max < 1.0) && !getenv("MASH_AMD_NO_FILTER"); }
 bool host_finish_wanted() { return getenv("MASH_AMD_HOST_FINISH") != nullptr; }
 
-template <class Call>
-bool fetch_results(Gpu &gpu, vector<mg_result> &res, Call call)
+// A list result (mg_result, mg_edge) of unknown length: a second call once the library has said how long it is
+template <class T, class Call>
+bool fetch_list(Gpu &gpu, vector<T> &v, Call call)
 {
     uint64_t n = 0;
-    if (res.size() < (1u << 16)) res.resize(1u << 16);
-    int rc = call(res.data(), (uint64_t)res.size(), &n);
-    if (rc == MG_ERR_NOMEM && n > res.size()) {
-        res.resize(n);
-        rc = call(res.data(), (uint64_t)res.size(), &n);
+    if (v.size() < (1u << 16)) v.resize(1u << 16);
+    int rc = call(v.data(), (uint64_t)v.size(), &n);
+    if (rc == MG_ERR_NOMEM && n > v.size()) {
+        v.resize(n);
+        rc = call(v.data(), (uint64_t)v.size(), &n);
     }
-    if (rc != MG_OK) {
-        // the sharded calls record their error in the communicator (or a shard's context)
-        const char *m = mg_comm_last_error(gpu.comm);
-        cerr << "ERROR: " << ((m && *m) ? m : mg_last_error(gpu.ctx)) << endl;
-        return false;
-    }
-    res.resize(n);
-    return true;
-}
-
-template <class Call>
-bool fetch_edges(Gpu &gpu, vector<mg_edge> &edges, Call call)
-{
-    uint64_t n = 0;
-    if (edges.size() < (1u << 16)) edges.resize(1u << 16);
-    int rc = call(edges.data(), (uint64_t)edges.size(), &n);
-    if (rc == MG_ERR_NOMEM && n > edges.size()) {
-        edges.resize(n);
-        rc = call(edges.data(), (uint64_t)edges.size(), &n);
-    }
-    if (rc != MG_OK) { cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl; return false; }
-    edges.resize(n);
+    if (rc != MG_OK) { report_error(gpu); return false; }
+    v.resize(n);
     return true;
 }
 
@@ -1124,6 +1123,281 @@ bool finish_edge(const mg_edge &e, uint64_t len_ref, uint64_t len_qry, int k, do
     pr.p_value = mg_p_value(e.numer, len_ref, len_qry, kspace, e.denom);
     pr.pass = pr.p_value <= p_max;                           // CommandDistance.cpp:419-422
     return pr.pass;
+}
+
+// MASH_AMD_BLOCK_PAIRS=<n> (for tests): no route's block budget is larger than n, so that a small input crosses
+// block boundaries.  It can only lower a budget; read once per process.
+uint64_t block_budget(uint64_t budget)
+{
+    static const char *e = getenv("MASH_AMD_BLOCK_PAIRS");
+    static const uint64_t knob = e ? std::max<uint64_t>(1, strtoull(e, nullptr, 10)) : ~0ull;
+    return std::min(knob, budget);
+}
+
+// The row blocks [r0, r1) of a compare and their pair counts: of a triangle (ncols == 0: row i has i pairs) or of a
+// rectangle (every row has ncols).  A block always takes its first row; a row is added while the sum stays within the
+// budget.  for (Blocks b(begin, end, budget, ncols); b.next();) ...
+struct Blocks {
+    const uint64_t end, ncols, budget;
+    uint64_t r0, r1, npairs = 0;
+    Blocks(uint64_t begin, uint64_t end_, uint64_t budget_, uint64_t ncols_ = 0)
+        : end(end_), ncols(ncols_), budget(block_budget(budget_)), r0(begin), r1(begin) {}
+    bool next()
+    {
+        r0 = r1;
+        npairs = 0;
+        while (r1 < end && (npairs == 0 || (ncols ? npairs + ncols : npairs + r1) <= budget)) { npairs += ncols ? ncols : r1; r1++; }
+        return r0 < r1;
+    }
+};
+
+// -N on the host (MASH_AMD_HOST_FINISH=1): appends the `keep` nearest of one row's passing pairs {row, neighbour, ...} to
+// res, in the order of mg_compare_*_topk_host: by shared hashes as an exact fraction, equal fractions by neighbour index
+void select_nearest(vector<mg_result> &row, uint64_t keep, vector<mg_result> &res)
+{
+    const size_t take = std::min<size_t>(row.size(), keep);
+    std::partial_sort(row.begin(), row.begin() + (ptrdiff_t)take, row.end(), [](const mg_result &a, const mg_result &b) {
+        const uint64_t l = (uint64_t)a.numer * (b.denom ? b.denom : 1u), r = (uint64_t)b.numer * (a.denom ? a.denom : 1u);
+        return l > r || (l == r && a.col < b.col);
+    });
+    res.insert(res.end(), row.begin(), row.begin() + (ptrdiff_t)take);
+}
+
+// The distances of one (s, k) as text: a distance depends on (numer, denom) alone, and nearly every pair has denom == s,
+// so a cell "\t<distance>" is formatted once per numerator, not per pair.  A distance above d_max is an empty cell
+// (`dist -t`, CommandDistance.cpp:409-412).
+struct DistText {
+    uint64_t s = 0;
+    int kmer = 0;
+    double d_max = HUGE_VAL;
+    vector<string> txt;                       // empty: no table, cell() is not to be called
+    void build(uint64_t s_, int kmer_, double d_max_ = HUGE_VAL)
+    {
+        s = s_; kmer = kmer_; d_max = d_max_;
+        txt.resize(s + 1);
+        for (uint64_t x = 0; x <= s; x++) {
+            FastOut t(false);
+            put(t, mg_distance((uint32_t)x, (uint32_t)s, kmer));
+            txt[x] = t.buf;
+        }
+    }
+    bool on() const { return !txt.empty(); }
+    void put(FastOut &o, double d) const { o << '\t'; if (!(d > d_max)) o << d; }
+    void cell(FastOut &o, uint32_t numer, uint32_t denom) const
+    {
+        if (denom == s) o << txt[numer];
+        else put(o, mg_distance(numer, denom, kmer));
+    }
+};
+
+// "Max p-value" of `mash triangle`: the peak over finished blocks, and within a block one running peak per emit_rows slot.
+// The Phylip matrix prints distances only, and of the p-values just the largest (to stderr).
+// A distance depends on (numer, denom) alone -> one table per run; and a p-value can only raise
+// the peak if even the pair of the two longest genomes sharing that many hashes would: the
+// p-value grows with both lengths (larger r in CommandDistance.cpp:437-441, the binomial tail
+// grows with r), so pairs whose bound stays below the running peak skip the incomplete-beta
+// evaluation.  The bound test has a 1e-9 relative margin for the rounding of that evaluation.
+struct PeakPValue {
+    double peak = 0;
+    vector<double> slot;
+    uint64_t s = 0, l1 = 0, l2 = 0;           // the sketch size the bound holds for, the two largest lengths
+    double kspace = 0;
+    vector<double> bound;                     // NaN: not evaluated yet
+    // (the bounds are evaluated on first use: a run meets a few hundred distinct numerators, and an
+    //  exact tail costs O(x) -- all s of them up front were minutes at s = 10^5 and a large r)
+    void use_bound(const vector<uint64_t> &lengths, uint64_t s_, double kspace_)
+    {
+        s = s_; kspace = kspace_;
+        for (uint64_t v : lengths) { if (v > l1) { l2 = l1; l1 = v; } else if (v > l2) l2 = v; }
+        bound.assign(s + 1, std::nan(""));
+    }
+    // p-value of the two longest genomes sharing x hashes, with a 1e-9 margin; memoised (workers may both
+    // evaluate an entry: they store the same bits)
+    double bound_of(uint32_t x)
+    {
+        uint64_t bits = __atomic_load_n(reinterpret_cast<const uint64_t *>(&bound[x]), __ATOMIC_RELAXED);
+        double v;
+        memcpy(&v, &bits, 8);
+        if (v != v) {                                              // not evaluated yet
+            v = mg_p_value(x, l1, l2, kspace, s) * (1.0 + 1e-9);
+            memcpy(&bits, &v, 8);
+            __atomic_store_n(reinterpret_cast<uint64_t *>(&bound[x]), bits, __ATOMIC_RELAXED);
+        }
+        return v;
+    }
+    void begin() { slot.assign(emit_threads(), peak); }          // a block starts from what earlier blocks established
+    // a pair of the lean writers (use_bound): evaluated only if its p-value could raise the slot's peak
+    void note(double &slot_peak, uint32_t numer, uint32_t denom, uint64_t len_i, uint64_t len_j)
+    {
+        if (denom != s || bound_of(numer) >= slot_peak) {
+            const double pv = mg_p_value(numer, len_i, len_j, kspace, denom);
+            if (pv > slot_peak) slot_peak = pv;
+        }
+    }
+    void merge() { for (double v : slot) if (v > peak) peak = v; }
+};
+
+// the inputs of a command from argument `first` on; with -l every argument is a file of file names
+vector<string> input_files(const Cmd &c, size_t first = 0)
+{
+    vector<string> files;
+    for (size_t i = first; i < c.args.size(); i++) { if (c.o("list").active) split_file(c.args[i], files); else files.push_back(c.args[i]); }
+    return files;
+}
+
+// A table on the devices.  Declared after the Gpu, so that it is freed before mg_comm_destroy runs.
+struct DTableFree { void operator()(mg_dtable *d) const { mg_dtable_free(d); } };
+using DTable = std::unique_ptr<mg_dtable, DTableFree>;
+
+// what every compare command ends with
+int finish_run(const SketchSet &set, const KmerWarning &w, bool reads) { if (w.count > 0 && !reads) warn_kmer_size(set, w); return 0; }
+
+// ------------------------------------------------------------------------------- dist
+// Budgets of a block of query rows (MASH_AMD_BLOCK_PAIRS lowers them):
+const uint64_t kDistFullPairs = 1ull << 24;         // the whole matrix comes back: 512 MiB of mg_pair per block
+const uint64_t kDistFilteredPairs = 1ull << 30;     // only the survivors come back; the library cuts its own device blocks
+const uint64_t kDistNearestRecords = 1ull << 22;    // -N: `keep` records per query, 128 MiB of mg_result per block
+
+struct DistRun {
+    Gpu &gpu;
+    const SketchSet &ref, &qry;
+    const bool table, comment;
+    const uint32_t nearest;
+    const double d_max, p_max, kspace;
+    const int kmer;
+    const uint64_t nref, nq;
+    vector<uint64_t> len_ref, len_qry;
+    DTable dr, dq;
+    mg_table *tr, *tq;                        // device 0's replicas: what the host-tail test routes address
+    vector<mg_counts> counts;                 // (these keep their capacity over the blocks)
+    vector<mg_pair> pairs;
+    FastOut out;
+    DistRun(Gpu &g, const SketchSet &r, const SketchSet &q, bool table_, bool comment_, uint32_t nearest_, double d_max_, double p_max_, bool ref_by_rows)
+        : gpu(g), ref(r), qry(q), table(table_), comment(comment_), nearest(nearest_), d_max(d_max_), p_max(p_max_), kspace(r.kmer_space()),
+          kmer(r.p.kmer), nref(r.refs.size()), nq(q.refs.size()), dr(upload_all(g, r, r.p.sketch_size, &len_ref, ref_by_rows)),
+          dq(upload_all(g, q, q.p.sketch_size, &len_qry)), tr(mg_dtable_local(dr.get(), 0)), tq(mg_dtable_local(dq.get(), 0)) {}
+};
+
+// the counts of a block of query rows x all references; with finish (MASH_AMD_HOST_FINISH=1) distances, p-values and filters
+// of those on the host
+int dist_counts(DistRun &r, const Blocks &b, bool finish)
+{
+    r.counts.resize(b.npairs);
+    if (mg_compare_rect_sharded_host(r.gpu.comm, r.dr.get(), r.dq.get(), b.r0, b.r1, r.counts.data()) != MG_OK) return report_error(r.gpu);
+    if (finish) {
+        r.pairs.resize(b.npairs);
+        mg_finish_rect_host(r.counts.data(), r.len_ref.data(), r.nref, r.len_qry.data() + b.r0, b.r1 - b.r0, r.kmer, r.kspace, r.d_max, r.p_max, r.pairs.data());
+    }
+    return 0;
+}
+
+void dist_emit_results(DistRun &r, const vector<mg_result> &res)
+{
+    emit_rows(r.out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
+        const mg_result &e = res[x];
+        print_pair_line(o, r.ref.refs[e.col], r.qry.refs[e.row], r.comment, e);
+    });
+}
+
+// -N: per query its nearest references, ranked and cut on the device (mg_compare_rect_topk_sharded_host): N records per
+// query cross PCIe.
+int dist_nearest(DistRun &r)
+{
+    const uint64_t keep = std::min<uint64_t>(r.nearest, r.nref);
+    vector<mg_result> res, row;
+    if (!host_finish_wanted()) {
+        for (Blocks b(0, r.nq, kDistNearestRecords, keep); b.next();) {
+            if (res.size() < b.npairs) res.resize(b.npairs);                            // the largest possible answer: one call
+            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_rect_topk_sharded_host(r.gpu.comm, r.dr.get(), r.dq.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, r.nearest, o, cap, n); }))
+                return 1;
+            dist_emit_results(r, res);
+        }
+        return 0;
+    }
+    // MASH_AMD_HOST_FINISH=1: the matrix of counts, the host tail, and the same selection here
+    for (Blocks b(0, r.nq, kDistFullPairs, r.nref); b.next();) {
+        if (dist_counts(r, b, true)) return 1;
+        res.clear();
+        for (uint64_t q = b.r0; q < b.r1; q++) {
+            const mg_pair *pr = r.pairs.data() + (q - b.r0) * r.nref;
+            row.clear();                                        // the query's passing pairs as {query, reference, ...}
+            for (uint64_t x = 0; x < r.nref; x++)
+                if (pr[x].pass) row.push_back(mg_result{(uint32_t)q, (uint32_t)x, pr[x].numer, pr[x].denom, pr[x].distance, pr[x].p_value});
+            select_nearest(row, keep, res);
+        }
+        dist_emit_results(r, res);
+    }
+    return 0;
+}
+
+// -d / -v without -t: the surviving pairs as finished records
+int dist_filtered(DistRun &r)
+{
+    vector<mg_result> res;
+    vector<mg_edge> edges;
+    for (Blocks b(0, r.nq, kDistFilteredPairs, r.nref); b.next();) {
+        if (!host_finish_wanted()) {
+            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_rect_results_sharded_host(r.gpu.comm, r.dr.get(), r.dq.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, n); }))
+                return 1;
+            dist_emit_results(r, res);
+        } else {
+            // MASH_AMD_HOST_FINISH=1: the pairs within -d from device 0's replicas, p-values and the -v filter here
+            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_rect_filter_host(r.gpu.ctx, r.tr, r.tq, b.r0, b.r1, r.kmer, r.d_max, o, cap, n); }))
+                return 1;
+            emit_rows(r.out, 0, edges.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
+                const mg_edge &e = edges[x];
+                mg_pair pr;
+                if (finish_edge(e, r.len_ref[e.col], r.len_qry[e.row], r.kmer, r.kspace, r.p_max, pr))
+                    print_pair_line(o, r.ref.refs[e.col], r.qry.refs[e.row], r.comment, pr);
+            });
+        }
+    }
+    return 0;
+}
+
+// Every pair: lines, or with -t one row of cells per query (writeOutput, CommandDistance.cpp:247-304)
+int dist_full(DistRun &r)
+{
+    // -t without a p-value filter prints distances only: they come from one table per run
+    // (a distance depends on numer / denom alone) and no p-value is evaluated
+    DistText dtxt;
+    const uint64_t s_tab = std::min(r.ref.p.sketch_size, r.qry.p.sketch_size);
+    if (r.table && r.p_max >= 1.0 && s_tab <= (1u << 20) && !getenv("MASH_AMD_FULL_FINISH")) dtxt.build(s_tab, r.kmer, r.d_max);
+    for (Blocks b(0, r.nq, kDistFullPairs, r.nref); b.next();) {
+        const uint64_t q0 = b.r0;
+        if (dtxt.on() || host_finish_wanted()) {
+            if (dist_counts(r, b, !dtxt.on())) return 1;
+        } else {
+            // compare + distance + p-value + filters on the device, finished records back
+            r.pairs.resize(b.npairs);
+            if (mg_compare_rect_pairs_sharded_host(r.gpu.comm, r.dr.get(), r.dq.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, r.pairs.data()) != MG_OK)
+                return report_error(r.gpu);
+        }
+        if (dtxt.on())
+            emit_rows(r.out, b.r0, b.r1, [&](uint64_t) { return r.nref; }, [&](FastOut &o, uint64_t q, unsigned) {
+                o << r.qry.refs[q].name;
+                for (uint64_t x = 0; x < r.nref; x++) {
+                    const mg_counts &c = r.counts[(q - q0) * r.nref + x];
+                    dtxt.cell(o, c.numer, c.denom);
+                    o.room();
+                }
+                o.eol();
+            });
+        else
+            emit_rows(r.out, b.r0, b.r1, [&](uint64_t) { return r.nref; }, [&](FastOut &o, uint64_t q, unsigned) {
+                if (r.table) o << r.qry.refs[q].name;
+                for (uint64_t x = 0; x < r.nref; x++) {
+                    const mg_pair &pr = r.pairs[(q - q0) * r.nref + x];
+                    if (r.table) { o << '\t'; if (pr.pass) o << pr.distance; o.room(); }
+                    else if (pr.pass) print_pair_line(o, r.ref.refs[x], r.qry.refs[q], r.comment, pr);
+                }
+                if (r.table) o.eol();
+            });
+    }
+    return 0;
 }
 
 int cmd_dist(int argc, const char **argv)
@@ -1191,169 +1465,248 @@ int cmd_dist(int argc, const char **argv)
         for (const Ref &r : ref.refs) cout << '\t' << r.name;
         cout << endl;
     }
-    vector<string> qfiles;
-    for (size_t i = 1; i < c.args.size(); i++) { if (c.o("list").active) split_file(c.args[i], qfiles); else qfiles.push_back(c.args[i]); }
     SketchSet qry;
-    init_from_files(gpu, qry, qfiles, p, 0, true);
+    init_from_files(gpu, qry, input_files(c, 1), p, 0, true);
     const uint64_t nref = ref.refs.size(), nq = qry.refs.size();
     if (nref == 0 || nq == 0) return 0;
-    vector<uint64_t> len_ref, len_qry;
     // several GPUs: the larger side is cut into row blocks; references larger than the queries
     // are then not even replicated (the host-tail test paths address device 0's table as a whole)
     const bool ref_by_rows = mg_comm_size(gpu.comm) > 1 && nref > nq && !host_finish_wanted() && !getenv("MASH_AMD_NO_FILTER");
-    mg_dtable *dr = upload_all(gpu, ref, ref.p.sketch_size, &len_ref, ref_by_rows);
-    mg_dtable *dq = upload_all(gpu, qry, qry.p.sketch_size, &len_qry);
-    mg_table *tr = mg_dtable_local(dr, 0), *tq = mg_dtable_local(dq, 0);
-    const double kspace = ref.kmer_space();
-    const uint64_t qblock = std::max<uint64_t>(1, (1ull << 24) / nref);
-    vector<mg_counts> counts;
+    DistRun run(gpu, ref, qry, table, comment, nearest, d_max, p_max, ref_by_rows);
+    if (nearest ? dist_nearest(run) : !table && edge_filter_wanted(d_max, p_max) ? dist_filtered(run) : dist_full(run)) return 1;
+    return finish_run(ref, w, p.reads);
+}
+
+// ------------------------------------------------------------------------------- triangle
+// Budgets of a block of rows (MASH_AMD_BLOCK_PAIRS lowers them):
+const uint64_t kTriDensePairs = 1ull << 24;         // the whole block comes back: 128 MiB of mg_counts, 512 MiB of mg_pair
+const uint64_t kTriSparsePairs = 1ull << 26;        // only the pairs that share a hash come back: at most an eighth of these
+const uint64_t kTriFilteredPairs = 1ull << 31;      // only the survivors come back; the library cuts its own device blocks
+const uint64_t kTriNearestRecords = 1ull << 24;     // -N: `keep` records per row, 512 MiB of mg_result per block
+
+struct TriRun {
+    Gpu &gpu;
+    const SketchSet &set;
+    const bool comment, edge;
+    const uint32_t nearest;
+    const double d_max, p_max, kspace;
+    const int kmer;
+    const uint64_t n;
+    vector<uint64_t> lengths;
+    DTable dt;
+    mg_table *t;                              // device 0's replica: what the calls on one context address
+    DistText dtxt;                            // on: the Phylip rows are the lean ones (distances from the table,
+    PeakPValue peak;                          //     p-values only where they can raise the peak)
+    vector<mg_counts> counts;                 // (these keep their capacity over the blocks)
     vector<mg_pair> pairs;
+    StageClock clk;                           // (starts when the table is on the devices)
     FastOut out;
-    if (nearest) {
-        // -N: per query its nearest references, ranked and cut on the device (mg_compare_rect_topk_sharded_host): N records per
-        // query cross PCIe.  MASH_AMD_HOST_FINISH=1: the matrix of counts, the host tail, and the same selection here.
-        vector<mg_result> res;
-        const uint64_t keep = std::min<uint64_t>(nearest, nref);
-        const uint64_t nblock = host_finish_wanted() ? qblock : std::max<uint64_t>(1, (1ull << 22) / keep);
-        for (uint64_t q0 = 0; q0 < nq; q0 += nblock) {
-            const uint64_t q1 = std::min(nq, q0 + nblock);
-            if (!host_finish_wanted()) {
-                if (res.size() < (q1 - q0) * keep) res.resize((q1 - q0) * keep);        // the largest possible answer: one call
-                if (!fetch_results(gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
-                        return mg_compare_rect_topk_sharded_host(gpu.comm, dr, dq, q0, q1, ref.p.kmer, kspace, d_max, p_max, nearest, o, cap, n); }))
-                    return 1;
-            } else {
-                counts.resize((q1 - q0) * nref);
-                if (mg_compare_rect_sharded_host(gpu.comm, dr, dq, q0, q1, counts.data()) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; return 1; }
-                pairs.resize(counts.size());
-                mg_finish_rect_host(counts.data(), len_ref.data(), nref, len_qry.data() + q0, q1 - q0, ref.p.kmer, kspace, d_max, p_max, pairs.data());
-                res.clear();
-                vector<uint32_t> order;
-                for (uint64_t q = q0; q < q1; q++) {
-                    const mg_pair *row = pairs.data() + (q - q0) * nref;
-                    order.clear();
-                    for (uint64_t r = 0; r < nref; r++)
-                        if (row[r].pass) order.push_back((uint32_t)r);
-                    const size_t take = std::min<size_t>(order.size(), keep);
-                    std::partial_sort(order.begin(), order.begin() + (ptrdiff_t)take, order.end(), [&](uint32_t x, uint32_t y) {
-                        const mg_pair &a = row[x], &b = row[y];           // the order of mg_compare_rect_topk_host
-                        const uint64_t l = (uint64_t)a.numer * (b.denom ? b.denom : 1u), r = (uint64_t)b.numer * (a.denom ? a.denom : 1u);
-                        return l > r || (l == r && x < y);
-                    });
-                    for (size_t i = 0; i < take; i++) {
-                        const mg_pair &a = row[order[i]];
-                        res.push_back(mg_result{(uint32_t)q, order[i], a.numer, a.denom, a.distance, a.p_value});
-                    }
-                }
-            }
-            emit_rows(out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
-                const mg_result &e = res[x];
-                mg_pair pr;
-                pr.numer = e.numer; pr.denom = e.denom; pr.distance = e.distance; pr.p_value = e.p_value; pr.pass = 1;
-                print_pair_line(o, ref.refs[e.col], qry.refs[e.row], comment, pr);
-            });
+    TriRun(Gpu &g, const SketchSet &s, bool comment_, bool edge_, uint32_t nearest_, double d_max_, double p_max_)
+        : gpu(g), set(s), comment(comment_), edge(edge_), nearest(nearest_), d_max(d_max_), p_max(p_max_), kspace(s.kmer_space()), kmer(s.p.kmer),
+          n(s.refs.size()), dt(upload_all(g, s, s.p.sketch_size, &lengths)), t(mg_dtable_local(dt.get(), 0))
+    {
+        if (edge || s.p.sketch_size > (1u << 20) || getenv("MASH_AMD_FULL_FINISH")) return;          // (env: the plain path, for tests)
+        dtxt.build(s.p.sketch_size, kmer);
+        peak.use_bound(lengths, s.p.sketch_size, kspace);
+    }
+    const string &label(uint64_t i) const { return comment ? set.refs[i].comment : set.refs[i].name; }
+};
+
+void tri_emit_results(TriRun &r, const vector<mg_result> &res)
+{
+    emit_rows(r.out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
+        const mg_result &e = res[x];
+        print_edge_line(o, r.label(e.row), r.label(e.col), e.numer, e.denom, e.distance, e.p_value);
+    });
+}
+
+// -N: per sketch its nearest neighbours, ranked and cut on the device (mg_compare_tri_topk_host; one device: the first of
+// those selected): N records per sketch cross PCIe.
+int tri_nearest(TriRun &r, uint64_t keep)
+{
+    vector<mg_result> res;
+    if (!host_finish_wanted()) {
+        for (Blocks b(0, r.n, kTriNearestRecords, keep); b.next();) {
+            if (res.size() < b.npairs) res.resize(b.npairs);                            // the largest possible answer: one call
+            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *cnt) {
+                    return mg_compare_tri_topk_host(r.gpu.ctx, r.t, b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, r.nearest, o, cap, cnt); }))
+                return 1;
+            tri_emit_results(r, res);
         }
-        mg_dtable_free(dr);
-        mg_dtable_free(dq);
-        if (w.count > 0 && !p.reads) warn_kmer_size(ref, w);
         return 0;
     }
-    if (!table && edge_filter_wanted(d_max, p_max)) {
-        vector<mg_edge> edges;
-        vector<mg_result> res;
-        const uint64_t fblock = std::max<uint64_t>(1, (1ull << 30) / nref);
-        for (uint64_t q0 = 0; q0 < nq; q0 += fblock) {
-            const uint64_t q1 = std::min(nq, q0 + fblock);
-            if (!host_finish_wanted()) {
-                if (!fetch_results(gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
-                        return mg_compare_rect_results_sharded_host(gpu.comm, dr, dq, q0, q1, ref.p.kmer, kspace, d_max, p_max, o, cap, n); }))
-                    return 1;
-                emit_rows(out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
-                    const mg_result &e = res[x];
-                    mg_pair pr;
-                    pr.numer = e.numer; pr.denom = e.denom; pr.distance = e.distance; pr.p_value = e.p_value; pr.pass = 1;
-                    print_pair_line(o, ref.refs[e.col], qry.refs[e.row], comment, pr);
-                });
-                continue;
+    // MASH_AMD_HOST_FINISH=1: the triangle of counts, the host tail, both rows of a passing pair note it, and the same
+    // selection here
+    vector<vector<mg_result>> rows(r.n);                        // a row's passing pairs as {row, neighbour, ...}
+    for (Blocks b(1, r.n, kTriDensePairs); b.next();) {
+        r.counts.resize(b.npairs);
+        r.pairs.resize(b.npairs);
+        if (mg_compare_tri_sharded_host(r.gpu.comm, r.dt.get(), b.r0, b.r1, r.counts.data()) != MG_OK) return report_error(r.gpu);
+        mg_finish_tri_host(r.counts.data(), r.lengths.data(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, r.pairs.data());
+        uint64_t idx = 0;
+        for (uint64_t i = b.r0; i < b.r1; i++)
+            for (uint64_t j = 0; j < i; j++, idx++) {
+                const mg_pair &a = r.pairs[idx];
+                if (!a.pass) continue;
+                rows[i].push_back(mg_result{(uint32_t)i, (uint32_t)j, a.numer, a.denom, a.distance, a.p_value});
+                rows[j].push_back(mg_result{(uint32_t)j, (uint32_t)i, a.numer, a.denom, a.distance, a.p_value});
             }
-            if (!fetch_edges(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *n) {
-                    return mg_compare_rect_filter_host(gpu.ctx, tr, tq, q0, q1, ref.p.kmer, d_max, o, cap, n); }))
+    }
+    for (vector<mg_result> &row : rows) select_nearest(row, keep, res);
+    tri_emit_results(r, res);
+    return 0;
+}
+
+// -E with -d / -v: the surviving pairs as finished records
+int tri_filtered(TriRun &r)
+{
+    vector<mg_result> res;
+    vector<mg_edge> edges;
+    for (Blocks b(1, r.n, kTriFilteredPairs); b.next();) {
+        if (!host_finish_wanted()) {
+            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *cnt) {
+                    return mg_compare_tri_results_sharded_host(r.gpu.comm, r.dt.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, cnt); }))
                 return 1;
-            emit_rows(out, 0, edges.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
+            r.clk.lap("compare+finish+filter+copy");
+            tri_emit_results(r, res);
+            r.clk.lap("format+write");
+        } else {
+            // MASH_AMD_HOST_FINISH=1: the pairs within -d from device 0's replica, p-values and the -v filter here
+            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                    return mg_compare_tri_filter_host(r.gpu.ctx, r.t, b.r0, b.r1, r.kmer, r.d_max, o, cap, cnt); }))
+                return 1;
+            r.clk.lap("compare+filter+copy");
+            emit_rows(r.out, 0, edges.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
                 const mg_edge &e = edges[x];
                 mg_pair pr;
-                if (finish_edge(e, len_ref[e.col], len_qry[e.row], ref.p.kmer, kspace, p_max, pr))
-                    print_pair_line(o, ref.refs[e.col], qry.refs[e.row], comment, pr);
+                if (finish_edge(e, r.lengths[e.row], r.lengths[e.col], r.kmer, r.kspace, r.p_max, pr))
+                    print_edge_line(o, r.label(e.row), r.label(e.col), pr.numer, pr.denom, pr.distance, pr.p_value);
             });
-        }
-        mg_dtable_free(dr);
-        mg_dtable_free(dq);
-        if (w.count > 0 && !p.reads) warn_kmer_size(ref, w);
-        return 0;
-    }
-    // -t without a p-value filter prints distances only: they come from one table per run
-    // (a distance depends on numer / denom alone) and no p-value is evaluated
-    const uint64_t s_tab = std::min(ref.p.sketch_size, qry.p.sketch_size);
-    vector<double> dist_lut;
-    vector<string> dist_txt;
-    if (table && p_max >= 1.0 && s_tab <= (1u << 20) && !getenv("MASH_AMD_FULL_FINISH")) {
-        dist_lut.resize(s_tab + 1);
-        for (uint64_t x = 0; x <= s_tab; x++) dist_lut[x] = mg_distance((uint32_t)x, (uint32_t)s_tab, ref.p.kmer);
-        dist_txt.resize(s_tab + 1);                                // the cell of the table, formatted once
-        for (uint64_t x = 0; x <= s_tab; x++) {
-            FastOut t(false);
-            t << '\t';
-            if (!(dist_lut[x] > d_max)) t << dist_lut[x];          // CommandDistance.cpp:409-412
-            dist_txt[x] = t.buf;
+            r.clk.lap("finish+format+write");
         }
     }
-    for (uint64_t q0 = 0; q0 < nq; q0 += qblock) {
-        const uint64_t q1 = std::min(nq, q0 + qblock);
-        if (dist_lut.empty() && !host_finish_wanted()) {
-            // compare + distance + p-value + filters on the device, finished records back
-            pairs.resize((q1 - q0) * nref);
-            if (mg_compare_rect_pairs_sharded_host(gpu.comm, dr, dq, q0, q1, ref.p.kmer, kspace, d_max, p_max, pairs.data()) != MG_OK) {
-                cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl;
-                return 1;
-            }
-        } else {
-            counts.resize((q1 - q0) * nref);
-            if (mg_compare_rect_sharded_host(gpu.comm, dr, dq, q0, q1, counts.data()) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; return 1; }
-        }
-        if (!dist_lut.empty()) {
-            emit_rows(out, q0, q1, [&](uint64_t) { return nref; }, [&](FastOut &o, uint64_t q, unsigned) {
-                o << qry.refs[q].name;                            // writeOutput, CommandDistance.cpp:247-304
-                for (uint64_t r = 0; r < nref; r++) {
-                    const mg_counts &c = counts[(q - q0) * nref + r];
-                    if (c.denom == s_tab) o << dist_txt[c.numer];
-                    else {
-                        const double d = mg_distance(c.numer, c.denom, ref.p.kmer);
-                        o << '\t';
-                        if (!(d > d_max)) o << d;                  // CommandDistance.cpp:409-412
-                    }
-                    o.room();
+    return 0;
+}
+
+// The Phylip matrix from the SPARSE result (mg_compare_tri_sparse_host): a pair that shares no hash is {0, min(s, |A| + |B|)}
+// -- distance 1, p-value 1 -- and in a collection nearly every pair is such a pair: what crosses PCIe and is looked at are
+// the exceptions, a row's text is runs of "\t1" between them (CommandTriangle.cpp:159-198 writes the same cells).  One
+// device; a block whose exceptions outnumber an eighth of its pairs (one species: every pair shares hashes) ends this route
+// with r0 at its first row: tri_dense, which has the engines for that, takes the rest of the run.
+int tri_sparse(TriRun &r, uint64_t &r0)
+{
+    if (!r.dtxt.on() || mg_comm_size(r.gpu.comm) != 1 || getenv("MASH_AMD_DENSE_MATRIX")) return 0;      // (env: dense from the start)
+    const DistText &dtxt = r.dtxt;
+    vector<mg_edge> exc;
+    vector<uint64_t> exc_at;
+    string ones;
+    for (int k = 0; k < 4096; k++) ones += "\t1";
+    for (Blocks b(r0, r.n, kTriSparsePairs); b.next(); r0 = b.r1) {
+        r.clk.lap("setup");
+        const uint64_t cap = b.npairs / 8 + 4096, b0 = b.r0;
+        if (exc.size() < cap) exc.resize(cap);
+        uint64_t cnt = 0;
+        const int rc = mg_compare_tri_sparse_host(r.gpu.ctx, r.t, b.r0, b.r1, exc.data(), cap, &cnt);
+        if (rc == MG_ERR_NOMEM) return 0;
+        if (rc != MG_OK) return report_error(r.gpu);
+        r.clk.lap("compare+sparse result+copy");
+        exc_at.assign(b.r1 - b0 + 1, cnt);                     // exceptions of row i: exc[exc_at[i - b0] .. exc_at[i - b0 + 1])
+        for (uint64_t x = cnt; x-- > 0;) exc_at[exc[x].row - b0] = x;
+        for (uint64_t i = b.r1 - b0; i-- > 0;) if (exc_at[i] > exc_at[i + 1]) exc_at[i] = exc_at[i + 1];
+        r.peak.begin();
+        emit_rows(r.out, b.r0, b.r1, [](uint64_t i) { return i / 16 + 64; }, [&](FastOut &o, uint64_t i, unsigned slot) {
+            double pk = r.peak.slot[slot];
+            o << r.label(i);
+            const bool empty_row = r.set.refs[i].hashes.empty();
+            auto defaults = [&](uint64_t c0, uint64_t c1) {       // columns [c0, c1) share nothing with row i
+                if (c0 >= c1) return;
+                if (pk < 1.0) pk = 1.0;                          // pValue(0, ...) = 1 (CommandDistance.cpp:431-434)
+                if (!empty_row) {
+                    for (uint64_t m = c1 - c0; m;) { const uint64_t k = std::min<uint64_t>(m, 4096); o.buf.append(ones, 0, 2 * k); m -= k; }
+                } else {
+                    // (two empty sketches: 0 / 0 union elements, common == denom: distance 0, CommandDistance.cpp:390-393)
+                    for (uint64_t j = c0; j < c1; j++) o << (r.set.refs[j].hashes.empty() ? "\t0" : "\t1");
                 }
+                o.room();
+            };
+            uint64_t c = 0;
+            for (uint64_t x = exc_at[i - b0]; x < exc_at[i - b0 + 1]; x++) {
+                const mg_edge &e = exc[x];
+                defaults(c, e.col);
+                dtxt.cell(o, e.numer, e.denom);
+                r.peak.note(pk, e.numer, e.denom, r.lengths[i], r.lengths[e.col]);
+                c = (uint64_t)e.col + 1;
+            }
+            defaults(c, i);
+            r.peak.slot[slot] = pk;
+            o.eol();
+        });
+        r.peak.merge();
+        r.clk.lap("format+write");
+    }
+    return 0;
+}
+
+// Rows [r0, n) from the whole matrix of counts: the lean Phylip rows (dtxt: distances from the table, p-values only where
+// they can raise the peak), or every pair finished -- on the device, with MASH_AMD_HOST_FINISH=1 on the host -- for the
+// plain Phylip rows (MASH_AMD_FULL_FINISH=1) and the unfiltered edge list (writeOutput, CommandTriangle.cpp:159-198)
+int tri_dense(TriRun &r, uint64_t r0)
+{
+    const DistText &dtxt = r.dtxt;
+    const bool lean = dtxt.on(), edge = r.edge;
+    for (Blocks b(r0, r.n, kTriDensePairs); b.next();) {
+        const bool dev_finish = !lean && !host_finish_wanted();
+        if (!dev_finish) r.counts.resize(b.npairs);
+        if (!lean) r.pairs.resize(b.npairs);
+        r.clk.lap("setup");
+        if (dev_finish) {
+            if (mg_compare_tri_pairs_sharded_host(r.gpu.comm, r.dt.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, r.pairs.data()) != MG_OK)
+                return report_error(r.gpu);
+            r.clk.lap("compare+finish+copy");
+        } else {
+            if (mg_compare_tri_sharded_host(r.gpu.comm, r.dt.get(), b.r0, b.r1, r.counts.data()) != MG_OK) return report_error(r.gpu);
+            r.clk.lap("compare+copy");
+            if (!lean) mg_finish_tri_host(r.counts.data(), r.lengths.data(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, r.pairs.data());
+            r.clk.lap("finish");
+        }
+        const uint64_t base = b.r0 * (b.r0 - 1) / 2;
+        r.peak.begin();
+        if (lean) {
+            emit_rows(r.out, b.r0, b.r1, [](uint64_t i) { return i; }, [&](FastOut &o, uint64_t i, unsigned slot) {
+                uint64_t idx = i * (i - 1) / 2 - base;
+                double pk = r.peak.slot[slot];
+                o << r.label(i);
+                for (uint64_t j = 0; j < i; j++, idx++) {
+                    const mg_counts &c = r.counts[idx];
+                    dtxt.cell(o, c.numer, c.denom);
+                    o.room();
+                    r.peak.note(pk, c.numer, c.denom, r.lengths[i], r.lengths[j]);
+                }
+                r.peak.slot[slot] = pk;
                 o.eol();
             });
-            continue;
+        } else {
+            emit_rows(r.out, b.r0, b.r1, [](uint64_t i) { return i; }, [&](FastOut &o, uint64_t i, unsigned slot) {
+                uint64_t idx = i * (i - 1) / 2 - base;
+                double pk = r.peak.slot[slot];
+                if (!edge) o << r.label(i);
+                for (uint64_t j = 0; j < i; j++, idx++) {
+                    const mg_pair &pr = r.pairs[idx];
+                    if (edge) {
+                        if (pr.pass) print_edge_line(o, r.label(i), r.label(j), pr.numer, pr.denom, pr.distance, pr.p_value);
+                    } else {
+                        o << '\t' << pr.distance;
+                        o.room();
+                    }
+                    if (pr.p_value > pk) pk = pr.p_value;
+                }
+                r.peak.slot[slot] = pk;
+                if (!edge) o.eol();
+            });
         }
-        if (host_finish_wanted()) {
-            pairs.resize(counts.size());
-            mg_finish_rect_host(counts.data(), len_ref.data(), nref, len_qry.data() + q0, q1 - q0, ref.p.kmer, kspace, d_max, p_max, pairs.data());
-        }
-        emit_rows(out, q0, q1, [&](uint64_t) { return nref; }, [&](FastOut &o, uint64_t q, unsigned) {
-            if (table) o << qry.refs[q].name;                // writeOutput, CommandDistance.cpp:247-304
-            for (uint64_t r = 0; r < nref; r++) {
-                const mg_pair &pr = pairs[(q - q0) * nref + r];
-                if (table) { o << '\t'; if (pr.pass) o << pr.distance; o.room(); }
-                else if (pr.pass) print_pair_line(o, ref.refs[r], qry.refs[q], comment, pr);
-            }
-            if (table) o.eol();
-        });
+        r.peak.merge();
+        r.clk.lap("format+write");
     }
-    mg_dtable_free(dr);
-    mg_dtable_free(dq);
-    if (w.count > 0 && !p.reads) warn_kmer_size(ref, w);
     return 0;
 }
 
@@ -1387,313 +1740,30 @@ int cmd_triangle(int argc, const char **argv)
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // CommandTriangle.cpp:74-77
-    vector<string> files;
-    for (const string &a : c.args) { if (c.o("list").active) split_file(a, files); else files.push_back(a); }
     Gpu gpu;
     SketchSet set;
-    init_from_files(gpu, set, files, p, 1);
+    init_from_files(gpu, set, input_files(c), p, 1);
     const KmerWarning w = scan_kmer_warning(set);
     const uint64_t n = set.refs.size();
     if (n == 0) return 0;
-    auto label = [&](const Ref &r) -> const string & { return comment ? r.comment : r.name; };
     if (!edge) {
         cout << '\t' << n << endl;
-        cout << label(set.refs[0]) << endl;
+        cout << (comment ? set.refs[0].comment : set.refs[0].name) << endl;
     }
-    vector<uint64_t> lengths;
-    mg_dtable *dt = upload_all(gpu, set, set.p.sketch_size, &lengths);
-    mg_table *t = mg_dtable_local(dt, 0);
-    const double kspace = set.kmer_space();
-    double p_peak = 0;
-    vector<mg_counts> counts;
-    vector<mg_pair> pairs;
-    uint64_t r0 = 1;
-    StageClock clk;
-    FastOut out;
-    if (nearest) {
-        // -N: per sketch its nearest neighbours, ranked and cut on the device (mg_compare_tri_topk_host; one device: the first of
-        // those selected): N records per sketch cross PCIe.  MASH_AMD_HOST_FINISH=1: the triangle of counts, the host tail, both
-        // rows of a passing pair note it, and the same selection here.
-        vector<mg_result> res;
-        const uint64_t keep = std::min<uint64_t>(nearest, n - 1);
-        if (!keep) { mg_dtable_free(dt); return 0; }
-        auto emit = [&] {
-            emit_rows(out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
-                const mg_result &e = res[x];
-                o << label(set.refs[e.row]) << '\t' << label(set.refs[e.col]) << '\t' << e.distance << '\t' << e.p_value << '\t' << e.numer << '/'
-                  << e.denom;
-                o.eol();
-            });
-        };
-        if (!host_finish_wanted()) {
-            const uint64_t nblock = std::max<uint64_t>(1, (1ull << 24) / keep);
-            for (uint64_t b0 = 0; b0 < n; b0 += nblock) {
-                const uint64_t b1 = std::min(n, b0 + nblock);
-                if (res.size() < (b1 - b0) * keep) res.resize((b1 - b0) * keep);                // the largest possible answer: one call
-                if (!fetch_results(gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *cnt) {
-                        return mg_compare_tri_topk_host(gpu.ctx, t, b0, b1, set.p.kmer, kspace, d_max, p_max, nearest, o, cap, cnt); }))
-                    return 1;
-                emit();
-            }
-        } else {
-            vector<vector<mg_result>> rows(n);                     // a row's passing pairs as {row, neighbour, ...}
-            while (r0 < n) {
-                uint64_t r1 = r0, npairs = 0;
-                while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 24))) { npairs += r1; r1++; }
-                counts.resize(npairs);
-                pairs.resize(npairs);
-                if (mg_compare_tri_sharded_host(gpu.comm, dt, r0, r1, counts.data()) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; return 1; }
-                mg_finish_tri_host(counts.data(), lengths.data(), r0, r1, set.p.kmer, kspace, d_max, p_max, pairs.data());
-                uint64_t idx = 0;
-                for (uint64_t i = r0; i < r1; i++)
-                    for (uint64_t j = 0; j < i; j++, idx++) {
-                        const mg_pair &a = pairs[idx];
-                        if (!a.pass) continue;
-                        rows[i].push_back(mg_result{(uint32_t)i, (uint32_t)j, a.numer, a.denom, a.distance, a.p_value});
-                        rows[j].push_back(mg_result{(uint32_t)j, (uint32_t)i, a.numer, a.denom, a.distance, a.p_value});
-                    }
-                r0 = r1;
-            }
-            res.clear();
-            for (vector<mg_result> &row : rows) {
-                const size_t take = std::min<size_t>(row.size(), keep);
-                std::partial_sort(row.begin(), row.begin() + (ptrdiff_t)take, row.end(), [](const mg_result &a, const mg_result &b) {
-                    const uint64_t l = (uint64_t)a.numer * (b.denom ? b.denom : 1u), r = (uint64_t)b.numer * (a.denom ? a.denom : 1u);
-                    return l > r || (l == r && a.col < b.col);    // the order of mg_compare_tri_topk_host
-                });
-                res.insert(res.end(), row.begin(), row.begin() + (ptrdiff_t)take);
-            }
-            emit();
-        }
-        mg_dtable_free(dt);
-        if (w.count > 0 && !p.reads) warn_kmer_size(set, w);
-        return 0;
-    }
-    if (edge && edge_filter_wanted(d_max, p_max)) {
-        vector<mg_edge> edges;
-        vector<mg_result> res;
-        while (r0 < n) {
-            uint64_t r1 = r0, npairs = 0;
-            while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 31))) { npairs += r1; r1++; }
-            if (!host_finish_wanted()) {
-                if (!fetch_results(gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *cnt) {
-                        return mg_compare_tri_results_sharded_host(gpu.comm, dt, r0, r1, set.p.kmer, kspace, d_max, p_max, o, cap, cnt); }))
-                    return 1;
-                clk.lap("compare+finish+filter+copy");
-                emit_rows(out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
-                    const mg_result &e = res[x];
-                    o << label(set.refs[e.row]) << '\t' << label(set.refs[e.col]) << '\t' << e.distance << '\t'
-                      << e.p_value << '\t' << e.numer << '/' << e.denom;
-                    o.eol();
-                });
-                clk.lap("format+write");
-                r0 = r1;
-                continue;
-            }
-            if (!fetch_edges(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
-                    return mg_compare_tri_filter_host(gpu.ctx, t, r0, r1, set.p.kmer, d_max, o, cap, cnt); }))
-                return 1;
-            clk.lap("compare+filter+copy");
-            emit_rows(out, 0, edges.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
-                const mg_edge &e = edges[x];
-                mg_pair pr;
-                if (finish_edge(e, lengths[e.row], lengths[e.col], set.p.kmer, kspace, p_max, pr)) {
-                    o << label(set.refs[e.row]) << '\t' << label(set.refs[e.col]) << '\t' << pr.distance << '\t'
-                      << pr.p_value << '\t' << pr.numer << '/' << pr.denom;
-                    o.eol();
-                }
-            });
-            clk.lap("finish+format+write");
-            r0 = r1;
-        }
-    }
-    // The Phylip matrix prints distances only, and of the p-values just the largest (to stderr).
-    // A distance depends on (numer, denom) alone -> one table per run; and a p-value can only raise
-    // the peak if even the pair of the two longest genomes sharing that many hashes would: the
-    // p-value grows with both lengths (larger r in CommandDistance.cpp:437-441, the binomial tail
-    // grows with r), so pairs whose bound stays below the running peak skip the incomplete-beta
-    // evaluation.  The bound test has a 1e-9 relative margin for the rounding of that evaluation.
-    const uint64_t s_tab = set.p.sketch_size;
-    vector<double> dist_lut, p_bound;
-    uint64_t bound_l1 = 0, bound_l2 = 0;
-    // p-value of the two longest genomes sharing x hashes, with a 1e-9 margin; memoised (workers may both
-    // evaluate an entry: they store the same bits)
-    auto bound_of = [&](uint32_t x) -> double {
-        uint64_t bits = __atomic_load_n(reinterpret_cast<const uint64_t *>(&p_bound[x]), __ATOMIC_RELAXED);
-        double v;
-        memcpy(&v, &bits, 8);
-        if (v != v) {                                              // not evaluated yet
-            v = mg_p_value(x, bound_l1, bound_l2, kspace, s_tab) * (1.0 + 1e-9);
-            memcpy(&bits, &v, 8);
-            __atomic_store_n(reinterpret_cast<uint64_t *>(&p_bound[x]), bits, __ATOMIC_RELAXED);
-        }
-        return v;
-    };
-    vector<string> dist_txt;                                       // "\t" + the text of dist_lut[x]: formatted once, not per pair
-    if (!edge && s_tab <= (1u << 20) && !getenv("MASH_AMD_FULL_FINISH")) {          // (env: the plain path, for tests)
-        uint64_t l1 = 0, l2 = 0;                                   // the two largest lengths
-        for (uint64_t v : lengths) { if (v > l1) { l2 = l1; l1 = v; } else if (v > l2) l2 = v; }
-        dist_lut.resize(s_tab + 1);
-        p_bound.resize(s_tab + 1);
-        // (the bounds are evaluated on first use: a run meets a few hundred distinct numerators, and an
-        //  exact tail costs O(x) -- all s of them up front were minutes at s = 10^5 and a large r)
-        for (uint64_t x = 0; x <= s_tab; x++) {
-            dist_lut[x] = mg_distance((uint32_t)x, (uint32_t)s_tab, set.p.kmer);
-            p_bound[x] = std::nan("");
-        }
-        bound_l1 = l1;
-        bound_l2 = l2;
-        dist_txt.resize(s_tab + 1);
-        for (uint64_t x = 0; x <= s_tab; x++) {
-            FastOut t(false);
-            t << '\t' << dist_lut[x];
-            dist_txt[x] = t.buf;
-        }
-    }
-    const bool lean = !dist_lut.empty();
-    // The Phylip matrix from the SPARSE result (mg_compare_tri_sparse_host): a pair that shares no hash is {0, min(s, |A| + |B|)}
-    // -- distance 1, p-value 1 -- and in a collection nearly every pair is such a pair: what crosses PCIe and is looked at are
-    // the exceptions, a row's text is runs of "\t1" between them (CommandTriangle.cpp:159-198 writes the same cells).  One
-    // device; a block whose exceptions outnumber an eighth of its pairs (one species: every pair shares hashes) sends the
-    // rest of the run down the dense path below, which has the engines for that.  (MASH_AMD_DENSE_MATRIX=1: dense from the start.)
-    bool sparse_rows = lean && mg_comm_size(gpu.comm) == 1 && !getenv("MASH_AMD_DENSE_MATRIX");
-    vector<mg_edge> exc;
-    vector<uint64_t> exc_at;
-    string ones;
-    if (sparse_rows) for (int k = 0; k < 4096; k++) ones += "\t1";
-    while (r0 < n && sparse_rows) {
-        uint64_t r1 = r0, npairs = 0;
-        while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 26))) { npairs += r1; r1++; }
-        clk.lap("setup");
-        const uint64_t cap = npairs / 8 + 4096;
-        if (exc.size() < cap) exc.resize(cap);
-        uint64_t cnt = 0;
-        const int rc = mg_compare_tri_sparse_host(gpu.ctx, t, r0, r1, exc.data(), cap, &cnt);
-        if (rc == MG_ERR_NOMEM) { sparse_rows = false; break; }
-        if (rc != MG_OK) { cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl; return 1; }
-        clk.lap("compare+sparse result+copy");
-        exc_at.assign(r1 - r0 + 1, cnt);                      // exceptions of row i: exc[exc_at[i - r0] .. exc_at[i - r0 + 1])
-        for (uint64_t x = cnt; x-- > 0;) exc_at[exc[x].row - r0] = x;
-        for (uint64_t i = r1 - r0; i-- > 0;) if (exc_at[i] > exc_at[i + 1]) exc_at[i] = exc_at[i + 1];
-        vector<double> peak(emit_threads(), p_peak);
-        emit_rows(out, r0, r1, [](uint64_t i) { return i / 16 + 64; }, [&](FastOut &o, uint64_t i, unsigned slot) {
-            double pk = peak[slot];
-            o << label(set.refs[i]);
-            const bool empty_row = set.refs[i].hashes.empty();
-            auto defaults = [&](uint64_t c0, uint64_t c1) {       // columns [c0, c1) share nothing with row i
-                if (c0 >= c1) return;
-                if (pk < 1.0) pk = 1.0;                          // pValue(0, ...) = 1 (CommandDistance.cpp:431-434)
-                if (!empty_row) {
-                    for (uint64_t m = c1 - c0; m;) { const uint64_t k = std::min<uint64_t>(m, 4096); o.buf.append(ones, 0, 2 * k); m -= k; }
-                } else {
-                    // (two empty sketches: 0 / 0 union elements, common == denom: distance 0, CommandDistance.cpp:390-393)
-                    for (uint64_t j = c0; j < c1; j++) o << (set.refs[j].hashes.empty() ? "\t0" : "\t1");
-                }
-                o.room();
-            };
-            uint64_t c = 0;
-            for (uint64_t x = exc_at[i - r0]; x < exc_at[i - r0 + 1]; x++) {
-                const mg_edge &e = exc[x];
-                defaults(c, e.col);
-                const bool full = e.denom == s_tab;
-                if (full) o << dist_txt[e.numer];
-                else o << '\t' << mg_distance(e.numer, e.denom, set.p.kmer);
-                if (!full || bound_of(e.numer) >= pk) {
-                    const double pv = mg_p_value(e.numer, lengths[i], lengths[e.col], kspace, e.denom);
-                    if (pv > pk) pk = pv;
-                }
-                c = (uint64_t)e.col + 1;
-            }
-            defaults(c, i);
-            peak[slot] = pk;
-            o.eol();
-        });
-        for (double v : peak) if (v > p_peak) p_peak = v;
-        clk.lap("format+write");
-        r0 = r1;
-    }
-    while (r0 < n) {
-        uint64_t r1 = r0, npairs = 0;
-        while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 24))) { npairs += r1; r1++; }
-        const bool dev_finish = !lean && !host_finish_wanted();
-        if (!dev_finish) counts.resize(npairs);
-        if (!lean) pairs.resize(npairs);
-        clk.lap("setup");
-        if (dev_finish) {
-            if (mg_compare_tri_pairs_sharded_host(gpu.comm, dt, r0, r1, set.p.kmer, kspace, d_max, p_max, pairs.data()) != MG_OK) {
-                cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl;
-                return 1;
-            }
-            clk.lap("compare+finish+copy");
-        } else {
-            if (mg_compare_tri_sharded_host(gpu.comm, dt, r0, r1, counts.data()) != MG_OK) { cerr << "ERROR: " << mg_comm_last_error(gpu.comm) << endl; return 1; }
-            clk.lap("compare+copy");
-            if (!lean) mg_finish_tri_host(counts.data(), lengths.data(), r0, r1, set.p.kmer, kspace, d_max, p_max, pairs.data());
-            clk.lap("finish");
-        }
-        const uint64_t base = r0 * (r0 - 1) / 2;
-        vector<double> peak(emit_threads(), 0.0);
-        if (lean) {
-            for (double &v : peak) v = p_peak;                     // what earlier blocks established
-            emit_rows(out, r0, r1, [](uint64_t i) { return i; }, [&](FastOut &o, uint64_t i, unsigned slot) {
-                uint64_t idx = i * (i - 1) / 2 - base;             // writeOutput, CommandTriangle.cpp:159-198
-                double pk = peak[slot];
-                o << label(set.refs[i]);
-                for (uint64_t j = 0; j < i; j++, idx++) {
-                    const mg_counts &c = counts[idx];
-                    const bool full = c.denom == s_tab;
-                    if (full) o << dist_txt[c.numer];
-                    else o << '\t' << mg_distance(c.numer, c.denom, set.p.kmer);
-                    o.room();
-                    if (!full || bound_of(c.numer) >= pk) {
-                        const double pv = mg_p_value(c.numer, lengths[i], lengths[j], kspace, c.denom);
-                        if (pv > pk) pk = pv;
-                    }
-                }
-                peak[slot] = pk;
-                o.eol();
-            });
-            for (double v : peak) if (v > p_peak) p_peak = v;
-            clk.lap("format+write");
-            r0 = r1;
-            continue;
-        }
-        emit_rows(out, r0, r1, [](uint64_t i) { return i; }, [&](FastOut &o, uint64_t i, unsigned slot) {
-            const Ref &ref = set.refs[i];                     // writeOutput, CommandTriangle.cpp:159-198
-            uint64_t idx = i * (i - 1) / 2 - base;
-            double pk = peak[slot];
-            if (!edge) o << label(ref);
-            for (uint64_t j = 0; j < i; j++, idx++) {
-                const mg_pair &pr = pairs[idx];
-                if (edge) {
-                    if (pr.pass) {
-                        o << label(ref) << '\t' << label(set.refs[j]) << '\t' << pr.distance << '\t' << pr.p_value << '\t'
-                          << pr.numer << '/' << pr.denom;
-                        o.eol();
-                    }
-                } else {
-                    o << '\t' << pr.distance;
-                    o.room();
-                }
-                if (pr.p_value > pk) pk = pr.p_value;
-            }
-            peak[slot] = pk;
-            if (!edge) o.eol();
-        });
-        for (double v : peak) if (v > p_peak) p_peak = v;
-        clk.lap("format+write");
-        r0 = r1;
-    }
-    mg_dtable_free(dt);
-    if (!edge) cerr << "Max p-value: " << p_peak << endl;
-    if (w.count > 0 && !p.reads) warn_kmer_size(set, w);
-    return 0;
+    TriRun run(gpu, set, comment, edge, nearest, d_max, p_max);
+    const uint64_t keep = std::min<uint64_t>(nearest, n - 1);
+    if (nearest && !keep) return 0;                              // one sketch: no neighbour to rank
+    uint64_t r0 = 1;                                             // the row at which the sparse route hands over to the dense one
+    if (nearest ? tri_nearest(run, keep) : edge && edge_filter_wanted(d_max, p_max) ? tri_filtered(run) : tri_sparse(run, r0) || tri_dense(run, r0)) return 1;
+    run.dt.reset();                                              // (inside the "teardown" lap, as the later lines)
+    if (!edge) cerr << "Max p-value: " << run.peak.peak << endl;
+    return finish_run(set, w, p.reads);
 }
 
 // `mash cluster`: single-linkage clusters of the pairs `mash triangle -E -d -v` would print (the reference has no such command;
 // include/mashgpu.h: mg_cluster_tri_host).  One line per sketch in input order: cluster number (from 1, in order of the
 // clusters' first members), cluster size, name.  The clusters are found on the device and one label per sketch comes back;
-// MASH_AMD_HOST_FINISH=1 takes cmd_triangle's host edge route and a union-find here.
+// MASH_AMD_HOST_FINISH=1 takes the edges of tri_filtered's host call and a union-find here.
 // -R: greedy representative clusters of the same pairs instead (mg_cluster_tri_greedy_host): walking the sketches in input
 // order, a sketch opens a cluster iff no earlier representative is within the threshold, else it joins the first one that is.
 // Lines and numbering are the same (the label is the representative); the host route runs that walk here.
@@ -1732,17 +1802,15 @@ int cmd_cluster(int argc, const char **argv)
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // as `mash triangle` (CommandTriangle.cpp:74-77)
-    vector<string> files;
-    for (const string &a : c.args) { if (c.o("list").active) split_file(a, files); else files.push_back(a); }
     Gpu gpu;
     SketchSet set;
-    init_from_files(gpu, set, files, p, 1);
+    init_from_files(gpu, set, input_files(c), p, 1);
     const KmerWarning w = scan_kmer_warning(set);
     const uint64_t n = set.refs.size();
     if (n == 0) return 0;
     vector<uint64_t> lengths;
-    mg_dtable *dt = upload_all(gpu, set, set.p.sketch_size, &lengths);
-    mg_table *t = mg_dtable_local(dt, 0);                        // (several devices selected: the first one's replica)
+    DTable dt(upload_all(gpu, set, set.p.sketch_size, &lengths));
+    mg_table *t = mg_dtable_local(dt.get(), 0);                  // (several devices selected: the first one's replica)
     const double kspace = set.kmer_space();
     StageClock clk;
     vector<uint32_t> lab(n);
@@ -1750,21 +1818,16 @@ int cmd_cluster(int argc, const char **argv)
         uint64_t n_clusters = 0, n_edges = 0;
         const int rc = greedy ? mg_cluster_tri_greedy_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
                               : mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges);
-        if (rc != MG_OK) {
-            cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl;
-            return 1;
-        }
+        if (rc != MG_OK) return report_error(gpu);
         clk.lap(greedy ? "compare+mark+append+rounds+assign+copy" : "compare+mark+union+label+copy");
     } else {
         for (uint64_t i = 0; i < n; i++) lab[i] = (uint32_t)i;
         auto find = [&](uint32_t x) { while (lab[x] != x) { lab[x] = lab[lab[x]]; x = lab[x]; } return x; };
         vector<mg_edge> edges;
         vector<vector<uint32_t>> smaller(greedy ? n : 0);      // -R: per sketch its neighbours with a smaller index
-        for (uint64_t r0 = 1; r0 < n;) {
-            uint64_t r1 = r0, npairs = 0;
-            while (r1 < n && (npairs == 0 || npairs + r1 <= (1ull << 31))) { npairs += r1; r1++; }
-            if (!fetch_edges(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
-                    return mg_compare_tri_filter_host(gpu.ctx, t, r0, r1, set.p.kmer, d_max, o, cap, cnt); }))
+        for (Blocks b(1, n, kTriFilteredPairs); b.next();) {
+            if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                    return mg_compare_tri_filter_host(gpu.ctx, t, b.r0, b.r1, set.p.kmer, d_max, o, cap, cnt); }))
                 return 1;
             for (const mg_edge &e : edges) {
                 mg_pair pr;
@@ -1773,10 +1836,9 @@ int cmd_cluster(int argc, const char **argv)
                     smaller[std::max(e.row, e.col)].push_back(std::min(e.row, e.col));
                     continue;
                 }
-                const uint32_t a = find(e.row), b = find(e.col);
-                if (a != b) lab[std::max(a, b)] = std::min(a, b);
+                const uint32_t a = find(e.row), b2 = find(e.col);
+                if (a != b2) lab[std::max(a, b2)] = std::min(a, b2);
             }
-            r0 = r1;
         }
         if (greedy) {
             // the walk in input order: lab[j] == j says that j, decided before i, is a representative
@@ -1801,9 +1863,8 @@ int cmd_cluster(int argc, const char **argv)
         out.eol();
     }
     clk.lap("format+write");
-    mg_dtable_free(dt);
-    if (w.count > 0 && !p.reads) warn_kmer_size(set, w);
-    return 0;
+    dt.reset();                                                  // (inside the "teardown" lap, as the later lines)
+    return finish_run(set, w, p.reads);
 }
 
 void print_columns(const vector<vector<string>> &cols, int indent, int spacing, const char *missing)

@@ -656,6 +656,64 @@ def test_large_outputs_do_not_depend_on_formatting_threads(built, tmp_path):
     assert d[1000 * 7 + 3].split("\t")[:2] == ["r3", "r7"]
 
 
+@pytest.mark.gpu
+def test_outputs_do_not_depend_on_block_boundaries(built, tmp_path):
+    """The compare commands work through their rows in blocks of a pair budget per route (mash_main.cpp::Blocks) and carry
+    state over them: the running "Max p-value", the offset of a block in the triangle, the exceptions of a row, the query
+    lengths of a block.  MASH_AMD_BLOCK_PAIRS lowers every budget: 1000 gives blocks of several rows, 1 one row per block
+    (a block always takes its first row).  stdout, stderr and exit status must equal the run with the default budgets,
+    which this table (299 sketches, 44 551 pairs) fits into as one block.
+    The input: 300 records, mutated copies of one 3 kb base as in the test above; one of them is shorter than k, which
+    `sketch -i` drops as the reference does, and one has no valid k-mer: that one is the empty sketch of the table."""
+    rng = np.random.default_rng(37)
+    base = np.frombuffer(synth._rand_dna(rng, 3000), dtype=np.uint8)
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
+    with open(tmp_path / "many.fa", "wb") as f:
+        for i in range(300):
+            seq = base.copy()
+            idx = rng.integers(0, 3000, int(rng.integers(0, 600)))
+            seq[idx] = lut[rng.integers(0, 4, len(idx))]
+            text = seq.tobytes()
+            if i == 120:
+                text = text[:9]                                    # shorter than k
+            if i == 211:
+                text = b"N" * 100                                  # no k-mer to hash
+            f.write(b">r%d c%d\n%s\n" % (i, i, text))
+    run("sketch", "-i", "-s", "64", "-k", "15", "-o", "many", "many.fa", cwd=tmp_path)
+    nhashes = [l.split("\t")[0] for l in run("info", "-t", "many.msh", cwd=tmp_path).stdout.splitlines()[1:]]
+    assert len(nhashes) == 299 and nhashes.count("0") == 1
+    one, two = ("many.msh",), ("many.msh", "many.msh")
+    host, nofilter = {"MASH_AMD_HOST_FINISH": "1"}, {"MASH_AMD_NO_FILTER": "1"}
+    tri_edges, tri_near = ("triangle", "-E", "-d", "0.1", "-v", "1e-5") + one, ("triangle", "-N", "3", "-d", "0.2") + one
+    dist_cut, dist_near, dist_tab_cut = ("dist", "-d", "0.1") + two, ("dist", "-N", "3") + two, ("dist", "-t", "-v", "1e-8") + two
+    cluster = ("cluster", "-d", "0.05") + one
+    cases = [(("triangle",) + one, {}), (("triangle",) + one, {"MASH_AMD_DENSE_MATRIX": "1"}), (("triangle",) + one, {"MASH_AMD_FULL_FINISH": "1"}),
+             (("triangle", "-E") + one, {}), (tri_edges, {}), (tri_near, {}),
+             (("dist",) + two, {}), (("dist", "-t") + two, {}), (dist_tab_cut, {}), (dist_cut, {}), (dist_near, {}), (cluster, {}),
+             (tri_edges, host), (tri_near, host), (dist_tab_cut, host), (dist_cut, host), (dist_near, host), (cluster, host),
+             (tri_edges, nofilter), (dist_cut, nofilter)]
+    plain = {}
+    for cmd, env in cases:
+        a = run(*cmd, cwd=tmp_path, env=env)
+        assert len(a.stdout) > 0, (cmd, env)
+        if not env:
+            plain[cmd] = a.stdout
+        for budget in ("1000", "1"):
+            b = run(*cmd, cwd=tmp_path, env=dict(env, MASH_AMD_BLOCK_PAIRS=budget), check=False)
+            assert (b.returncode, b.stdout, b.stderr) == (a.returncode, a.stdout, a.stderr), (cmd, env, budget)
+        if cmd[0] == "triangle" and "-E" not in cmd and "-N" not in cmd:
+            assert "Max p-value:" in a.stderr
+    # the filters cut somewhere in the middle, or the thresholded routes above were vacuous
+    nlines = {cmd: out.count("\n") for cmd, out in plain.items()}
+    assert 0 < nlines[tri_edges] < nlines[("triangle", "-E") + one]
+    assert 0 < nlines[tri_near] < nlines[("triangle", "-E") + one]
+    assert 0 < nlines[dist_cut] < nlines[("dist",) + two]
+    assert 0 < nlines[dist_near] <= 3 * 299 < nlines[("dist",) + two]
+    cells = lambda out: sum(1 for l in out.splitlines()[1:] for c in l.split("\t")[1:] if c)
+    assert 0 < cells(plain[dist_tab_cut]) < cells(plain[("dist", "-t") + two])
+    assert 1 < max(int(l.split("\t")[0]) for l in plain[cluster].splitlines()) < 299      # neither one cluster nor all singletons
+
+
 def test_msh_reader_survives_corrupted_files(built, tmp_path):
     """Truncated or bit-flipped .msh files (wrong segment table, pointers past the end, absurd
     list lengths) must end in an error message and exit status 1, never in a crash."""
