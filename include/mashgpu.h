@@ -457,6 +457,37 @@ int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, dou
                               uint64_t *n_edges_out);
 int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out,
                             uint64_t *edge_capacity_out);
+/* The minimum spanning forest of the same thresholded all-vs-all, found ON THE DEVICE (cluster_forest.hip) -- `mash cluster -T`.
+ * The reference has no such command (its user pipes `mash triangle -E -d` through a sort on column 5 and a union-find script, once
+ * per threshold they want to look at); the definition stands on those lines:
+ *   edge     : exactly a pair {row, col}, col < row, that mg_compare_tri_results_host(ctx, t, 0, rows, kmer_size, kmer_space,
+ *              max_distance, max_p_value, ...) returns -- the edge of mg_cluster_tri_host;
+ *   order    : edge a before edge b iff numer_a * denom_b > numer_b * denom_a (64-bit integers; a pair of two empty sketches, 0/0,
+ *              counts as 0/1); equal fractions, also under different denominators, by ascending row, then ascending col -- a
+ *              STABLE sort of the lines of `mash triangle -E` by column 5 as a fraction, descending;
+ *   forest   : walk the edges in that order and keep an edge iff its ends are not yet connected by kept edges (Kruskal).  The order
+ *              is strict, so this is THE minimum spanning forest: it depends on no execution order, route or blocking;
+ *   result   : the kept edges in that order, best first, as the records mg_compare_tri_results_host gives for them (doubles
+ *              bit-equal); *count_out = rows - *n_clusters_out of them.
+ * The forest cut at any fraction is the forest, and so the single-linkage partition, of that stricter threshold; read in order it
+ * is the single-linkage dendrogram.  label_out_host (may be NULL), *n_clusters_out and *n_edges_out are mg_cluster_tri_host's.
+ * capacity / *count_out / MG_ERR_NOMEM as for mg_compare_tri_results_host (the labels and counts are valid then); rows - 1 always
+ * suffices.  The whole table only, one device, at most 2^31 - 1 rows; a sketch size of 2^21 or more: MG_ERR_UNSUPPORTED (the 64-bit
+ * weight key that picks a component's best edge is exact for denominators below 2^21).  Both filters disabled (each < 0 or >= 1):
+ * MG_ERR_INVALID; everything else fails as mg_compare_tri_results_host does.  A table of 0 or 1 rows: MG_OK, no record.
+ * The edges are kept on the device as 16 bytes each while the call runs (the list grows on demand; the context option
+ * MASHGPU_FOREST_EDGE_CAP sets its first capacity in edges, a test knob); if they do not fit the call returns MG_ERR_NOMEM, it
+ * never drops an edge.  Only the rows - n_clusters records and rows x 4 bytes cross PCIe.
+ * mg_cluster_forest_stats: what the context's last such call needed -- rounds (at most floor(log2 rows) + 1, the last of them
+ * finding nothing; 0 without an edge), times the edge list was regrown, its final capacity in edges (any pointer may be NULL). */
+int mg_cluster_tri_forest_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                               double max_p_value, mg_result *out_host, uint64_t capacity, uint64_t *count_out,
+                               uint32_t *label_out_host /* [rows] or NULL */, uint64_t *n_clusters_out, uint64_t *n_edges_out);
+int mg_cluster_forest_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *regrows_out, uint64_t *edge_capacity_out);
+/* The rounds of the context's last mg_cluster_tri_forest_host call one by one (a measuring aid, tools/forest_bench.py): for round
+ * r < min(*rounds_out, capacity), live_out[r] = the edges whose ends lay in two components when it began, chosen_out[r] = the forest
+ * edges it chose (0 in the last round).  *rounds_out = mg_cluster_forest_stats' rounds, always. */
+int mg_cluster_forest_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *chosen_out, uint64_t capacity, uint64_t *rounds_out);
 /* Scalar helpers (same arithmetic as the bulk calls). */
 double mg_distance(uint32_t numer, uint32_t denom, int kmer_size);
 double mg_p_value(uint64_t x, uint64_t len_ref, uint64_t len_qry, double kmer_space,

@@ -33,6 +33,7 @@ EXPORTS = [
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host", "mg_compare_tri_topk_host",
     "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
+    "mg_cluster_tri_forest_host", "mg_cluster_forest_stats", "mg_cluster_forest_rounds",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
@@ -362,6 +363,9 @@ def load_library():
     lib.mg_cluster_tri_greedy_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_greedy_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_greedy_stats.argtypes = [vp, vp, vp, vp, vp]
+    lib.mg_cluster_tri_forest_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, u64, vp, vp, vp, vp]
+    lib.mg_cluster_forest_stats.argtypes = [vp, vp, vp, vp]
+    lib.mg_cluster_forest_rounds.argtypes = [vp, vp, vp, u64, vp]
     lib.mg_compare_rect_topk_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_dscreen_create.argtypes = [vp, C.POINTER(MgParams), vp, i32, C.POINTER(vp)]
     lib.mg_dscreen_add_host.argtypes = [vp, vp, u64]
@@ -1027,6 +1031,33 @@ class MashGpu:
         v = [C.c_uint64(0) for _ in range(4)]
         self._check(self.lib.mg_cluster_greedy_stats(self.ctx, *[C.byref(x) for x in v]))
         return dict(zip(("rounds", "batches", "regrows", "edge_capacity"), (int(x.value) for x in v)))
+
+    def cluster_tri_forest_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=None, want_label=True):
+        """the minimum spanning forest of the pairs compare_tri_results returns for the whole table, found on the device: (records
+        RESULT_DTYPE best first by the exact fraction numer/denom, equal fractions by row then col; label u32[rows] as cluster_tri_host
+        gives it, or None; clusters; edges).  capacity: room for the records, rows - 1 by default (always enough)
+        (mg_cluster_tri_forest_host)"""
+        capacity = max(table.rows - 1, 0) if capacity is None else int(capacity)
+        out = np.zeros(max(capacity, 1), dtype=RESULT_DTYPE)
+        label = np.zeros(table.rows, dtype=np.uint32) if want_label else None
+        n, nc, ne = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_forest_host(self.ctx, table.handle, k, kmer_space, max_d, max_p, out.ctypes.data, capacity, C.byref(n),
+                                                        label.ctypes.data if want_label else None, C.byref(nc), C.byref(ne)))
+        return out[:n.value], label, int(nc.value), int(ne.value)
+
+    def cluster_forest_stats(self):
+        """what this context's last cluster_tri_forest_host call needed: {rounds, regrows, edge_capacity} (mg_cluster_forest_stats)"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        self._check(self.lib.mg_cluster_forest_stats(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("rounds", "regrows", "edge_capacity"), (int(x.value) for x in v)))
+
+    def cluster_forest_rounds(self):
+        """the rounds of this context's last cluster_tri_forest_host call: (live edges each began with, forest edges each chose)
+        (mg_cluster_forest_rounds)"""
+        live, chosen = np.zeros(64, dtype=np.uint64), np.zeros(64, dtype=np.uint64)
+        n = C.c_uint64(0)
+        self._check(self.lib.mg_cluster_forest_rounds(self.ctx, live.ctypes.data, chosen.ctypes.data, 64, C.byref(n)))
+        return live[:n.value].tolist(), chosen[:n.value].tolist()
 
     def finish_tri_dev(self, table, counts_ptr, row_begin, row_end, k, kmer_space, max_d, max_p, out_ptr):
         self._check(self.lib.mg_finish_tri_dev(self.ctx, table.handle, counts_ptr, row_begin, row_end, k, kmer_space,

@@ -22,40 +22,12 @@
 //     hi's tree then hangs under a row inside lo's tree, which is the same union.
 // Labels are read in a LATER launch (cl_label_kernel): the kernel boundary makes every link visible, its walks end at the true
 // roots.
+// cl_load, cl_find and cl_unite stand in cluster_internal.h: cluster_forest.hip unites with the same ones.
 #include "cluster_internal.h"
 
 namespace mg {
 
 constexpr int CL_NT = 256;
-
-__device__ __forceinline__ uint32_t cl_load(uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root above x as far as this work-item can see, halving the path on the way
-__device__ __forceinline__ uint32_t cl_find(uint32_t *parent, uint32_t x)
-{
-    for (;;) {
-        const uint32_t p = cl_load(parent + x);
-        if (p == x) return x;
-        const uint32_t g = cl_load(parent + p);
-        if (g == p) return p;
-        atomicMin(parent + x, g);
-        x = g;
-    }
-}
-
-__device__ __forceinline__ void cl_unite(uint32_t *parent, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = cl_find(parent, a);
-        b = cl_find(parent, b);
-        if (a == b) return;                                    // one tree already: no atomic (nearly every edge of a dense cluster)
-        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const uint32_t was = atomicCAS(parent + hi, hi, lo);
-        if (was == hi) return;
-        a = was;                                               // hi had been linked by somebody else: go on from where it points
-        b = lo;
-    }
-}
 
 __global__ __launch_bounds__(CL_NT) void cl_init_kernel(uint32_t *parent, uint32_t n)
 {

@@ -1,10 +1,41 @@
-// cluster_internal.h — launch interface between host_compare.cpp and cluster.hip (single-linkage clusters of a thresholded triangle)
-// and cluster_greedy.hip (greedy representative clusters of the same graph).
+// cluster_internal.h — launch interface between host_compare.cpp and cluster.hip (single-linkage clusters of a thresholded triangle),
+// cluster_greedy.hip (greedy representative clusters of the same graph) and cluster_forest.hip (its minimum spanning forest), and the
+// lock-free union-find that cluster.hip and cluster_forest.hip share.
 #pragma once
 #include "finish_internal.h"          // (under MG_HIP_EMU that header brings tools/hipemu: tests/test_cluster_emu.py)
 #include <stdint.h>
 
 namespace mg {
+
+// ---- the union-find over parent[n] (invariants and the staleness argument: the head of cluster.hip)
+__device__ __forceinline__ uint32_t cl_load(uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root above x as far as this work-item can see, halving the path on the way
+__device__ __forceinline__ uint32_t cl_find(uint32_t *parent, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = cl_load(parent + x);
+        if (p == x) return x;
+        const uint32_t g = cl_load(parent + p);
+        if (g == p) return p;
+        atomicMin(parent + x, g);
+        x = g;
+    }
+}
+
+__device__ __forceinline__ void cl_unite(uint32_t *parent, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = cl_find(parent, a);
+        b = cl_find(parent, b);
+        if (a == b) return;                                    // one tree already: no atomic (nearly every edge of a dense cluster)
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const uint32_t was = atomicCAS(parent + hi, hi, lo);
+        if (was == hi) return;
+        a = was;                                               // hi had been linked by somebody else: go on from where it points
+        b = lo;
+    }
+}
 
 // parent[i] = i for the n rows
 hipError_t launch_cluster_init(uint32_t *parent, uint32_t n, hipStream_t stream);
@@ -28,5 +59,29 @@ hipError_t launch_greedy_rounds(const uint2 *edges, uint64_t m, uint32_t *state,
 // Behind the fixpoint: rep[i] = i for a representative, else the smallest representative i has an edge to; *n_reps = representatives.
 hipError_t launch_greedy_assign(const uint2 *edges, uint64_t m, const uint32_t *state, uint32_t n, uint32_t *rep, unsigned long long *n_reps,
                                 hipStream_t stream);
+
+// ---- cluster_forest.hip
+// launch_greedy_append with the pair's counts beside it: {x = larger, y = smaller index, z = numer, w = denom} of a.counts, 16 bytes an
+// edge.  Cursor, `cap` and *overflow as there.
+hipError_t launch_forest_append(const FinishArgs &a, uint32_t n, uint4 *edges, uint64_t cap, unsigned long long *cursor, uint32_t *overflow,
+                                hipStream_t stream);
+// What the rounds work on, all of it written by the launches below (nothing has to be cleared before the call)
+struct ForestBufs {
+    uint32_t *parent, *comp;                   // [n] the union-find; the flat component of a row as of the end of the round before
+    unsigned long long *best_key, *best_rc;    // [n] per component of this round: its best weight key, the smallest {hi, lo} that has it
+    uint4 *forest;                             // [forest_room(n)] the chosen edges: in the order they were picked, then sorted
+    unsigned long long *count;                 // [1] how many of them
+    uint32_t *merged;                          // [forest_rounds(n)] edges chosen by round r
+    unsigned long long *live;                  // [forest_rounds(n)] edges that were live when round r began
+};
+uint32_t forest_rounds(uint32_t n);            // floor(log2 n) + 2: one more than any graph of n rows needs, the last of them finds nothing
+uint64_t forest_room(uint32_t n);              // the power of two >= max(n, 2): room for the n - 1 edges and the sort's padding
+// Everything behind the last append, queued as one batch: the rounds (a round behind one that chose no edge does nothing), then
+// label / *n_roots as launch_cluster_label gives them, then the chosen edges best first by the exact comparator, forest[*count ..
+// forest_room(n)) padded, and seen[d] = 1 for every denominator d <= s they carry (seen[0 .. s] cleared first).
+hipError_t launch_forest_rounds(const uint4 *edges, uint64_t m, const ForestBufs &b, uint32_t n, uint32_t *label, unsigned long long *n_roots,
+                                uint32_t *seen, uint32_t s, hipStream_t stream);
+// out[i] = the finished record of forest[i], i < count: f's distance table and lengths, the device functions of finish.hip
+hipError_t launch_forest_finish(const FinishArgs &f, const uint4 *forest, uint64_t count, FinishEdge *out, hipStream_t stream);
 
 }  // namespace mg

@@ -2386,19 +2386,21 @@ int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kme
 
 /* ------------------------------------------------- greedy representative clusters of the thresholded triangle (cluster_greedy.hip) */
 
-// The edge list of one call: grown on demand, the pairs of every block appended behind those of the blocks before it
-struct GreedyEdges {
+// The edge list of one call: grown on demand, the pairs of every block appended behind those of the blocks before it.  E: an edge as
+// Append writes it ({hi, lo} for the greedy rounds, with the pair's counts beside them for the forest)
+template <class E, hipError_t (*Append)(const mg::FinishArgs &, uint32_t, E *, uint64_t, unsigned long long *, uint32_t *, hipStream_t)>
+struct EdgeList {
     mg_ctx *ctx;
-    DevBuf<uint2> buf;
+    DevBuf<E> buf;
     DevBuf<unsigned long long> ctl;                           // [0] cursor, [1] pass A's count of the block, [2] overflow flag (its low word)
     uint64_t cap = 0, used = 0, n_edges = 0, regrows = 0;
-    explicit GreedyEdges(mg_ctx *c) : ctx(c), buf(c), ctl(c) {}
+    explicit EdgeList(mg_ctx *c) : ctx(c), buf(c), ctl(c) {}
     int init(uint64_t want)
     {
         cap = std::max<uint64_t>(want, 1);
         if (buf.alloc(cap) != hipSuccess || ctl.alloc(3) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(cap * sizeof(uint2)) + " bytes)");
+            return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(cap * sizeof(E)) + " bytes)");
         }
         HIP_TRY(ctx, hipMemsetAsync(ctl, 0, 24, ctx->stream));
         return MG_OK;
@@ -2412,19 +2414,19 @@ struct GreedyEdges {
         unsigned long long h[3] = {0, 0, 0};
         HIP_TRY(ctx, mg::launch_finish_mark(f, ctl + 1, ctx->stream));
         for (int attempt = 0;; attempt++) {
-            HIP_TRY(ctx, mg::launch_greedy_append(f, n, buf, cap, ctl, reinterpret_cast<uint32_t *>(ctl + 2), ctx->stream));
+            HIP_TRY(ctx, Append(f, n, buf, cap, ctl, reinterpret_cast<uint32_t *>(ctl + 2), ctx->stream));
             HIP_TRY(ctx, hipMemcpyAsync(h, ctl, 24, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (h[0] <= cap && !h[2]) break;
             if (attempt) return fail(ctx, MG_ERR_HIP, "cluster: the edge list overflowed after it was regrown");
             const uint64_t want = std::max<uint64_t>(h[0], 2 * cap);
-            DevBuf<uint2> bigger(ctx);
+            DevBuf<E> bigger(ctx);
             if (bigger.alloc(want) != hipSuccess) {
                 (void)hipGetLastError();
-                return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(want * sizeof(uint2)) + " bytes for " +
+                return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(want * sizeof(E)) + " bytes for " +
                                                    std::to_string(h[0]) + " edges so far)");
             }
-            if (used) HIP_TRY(ctx, hipMemcpyAsync(bigger, buf, used * sizeof(uint2), hipMemcpyDeviceToDevice, ctx->stream));
+            if (used) HIP_TRY(ctx, hipMemcpyAsync(bigger, buf, used * sizeof(E), hipMemcpyDeviceToDevice, ctx->stream));
             const unsigned long long back[3] = {used, h[1], 0};
             HIP_TRY(ctx, hipMemcpyAsync(ctl, back, 24, hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the old list goes back to the pool behind the copy)
@@ -2437,6 +2439,7 @@ struct GreedyEdges {
         return MG_OK;
     }
 };
+using GreedyEdges = EdgeList<uint2, mg::launch_greedy_append>;
 
 // The whole triangle of t: cluster_tri's way to the thresholded counts (cut_counts) with GreedyEdges::append as their consumer -- one
 // wait per block --, then the rounds in batches (one wait per batch: the rows each of its rounds left open), then the assignment
@@ -2534,6 +2537,137 @@ int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches
     if (batches_out) *batches_out = ctx->greedy_batches;
     if (regrows_out) *regrows_out = ctx->greedy_regrows;
     if (edge_capacity_out) *edge_capacity_out = ctx->greedy_edge_cap;
+    return MG_OK;
+}
+
+
+/* ------------------------------------------------- the minimum spanning forest of the thresholded triangle (cluster_forest.hip) */
+
+using ForestEdges = EdgeList<uint4, mg::launch_forest_append>;
+
+// The whole triangle of t: cluster_greedy_tri's way to the edge list (cut_counts with ForestEdges::append as the consumer, one wait per
+// block), then ONE batch -- the rounds, the labels, the sort, the denominators -- and one wait for it, then the distance rows of exactly
+// those denominators and the records
+static int cluster_forest_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, mg_result *out_host, uint64_t capacity, uint64_t *count_out,
+                              uint32_t *label_out, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    *count_out = *n_clusters_out = *n_edges_out = 0;
+    ctx->forest_rounds = ctx->forest_regrows = ctx->forest_edge_cap = 0;
+    ctx->forest_live.clear();
+    ctx->forest_chosen.clear();
+    OutRange R;
+    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
+    if (rc != MG_OK || R.empty()) return rc;
+    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
+    if (R.s >= mg::FOREST_DENOM_LIMIT)
+        return fail(ctx, MG_ERR_UNSUPPORTED, "cluster forest: sketch size 2^21 or more (the weight key orders denominators below 2^21 exactly)");
+    const uint32_t n = (uint32_t)t->n;
+    uint64_t edge_cap = 1ull << 23;                           // 128 MB; the list doubles, or grows to what a block needs, when it is short
+    if (const char *o = ctx_opt(ctx, "MASHGPU_FOREST_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
+    ForestEdges E(ctx);
+    CutBufs bufs(ctx, ctx);
+    PassABufs pa(ctx);
+    // the list starts no longer than the pairs its route can bring: the candidates, or the whole triangle
+    auto begin = [&](uint64_t most_edges) -> int {
+        const int rci = E.init(std::min<uint64_t>(edge_cap, most_edges));
+        if (rci != MG_OK) return rci;
+        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+        return MG_OK;
+    };
+    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
+                    [&](uint64_t pairs, uint64_t, uint64_t, bool lists) -> int {
+        if (!pa.alloc(pairs, R.s)) return kAllocFailed;
+        return lists ? MG_OK : begin(R.pairs);                // (the list route begins once its tables stand: below)
+    },
+                    [&] { pa.release(); },
+                    [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
+        const int rcb = L ? begin(L->K) : MG_OK;
+        return rcb != MG_OK ? rcb : E.append(f, pa, n);
+    });
+    if (rc != MG_OK) return rc;
+    const uint32_t rounds_queued = mg::forest_rounds(n);
+    DevBuf<uint32_t> parent(ctx), comp(ctx), merged(ctx), label(ctx), seen(ctx);
+    DevBuf<unsigned long long> best_key(ctx), best_rc(ctx), live(ctx), d_n(ctx);      // d_n: [0] the chosen edges, [1] the clusters
+    DevBuf<uint4> forest(ctx);
+    if (parent.alloc(n) != hipSuccess || comp.alloc(n) != hipSuccess || merged.alloc(rounds_queued) != hipSuccess || label.alloc(n) != hipSuccess ||
+        seen.alloc((uint64_t)R.s + 1) != hipSuccess || best_key.alloc(n) != hipSuccess || best_rc.alloc(n) != hipSuccess || live.alloc(rounds_queued) != hipSuccess ||
+        d_n.alloc(2) != hipSuccess ||
+        forest.alloc(mg::forest_room(n)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+    }
+    const mg::ForestBufs fb{parent, comp, best_key, best_rc, forest, d_n, merged, live};
+    std::vector<uint32_t> h_merged(rounds_queued), h_seen((size_t)R.s + 1);
+    std::vector<unsigned long long> h_live(rounds_queued);
+    unsigned long long h_n[2] = {0, 0};
+    HIP_TRY(ctx, mg::launch_forest_rounds(E.buf, E.used, fb, n, label, d_n + 1, seen, R.s, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h_merged.data(), merged, (size_t)rounds_queued * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h_live.data(), live, (size_t)rounds_queued * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h_seen.data(), seen, h_seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h_n, d_n, 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (label_out) HIP_TRY(ctx, hipMemcpyAsync(label_out, label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t r = 0;
+    while (r < rounds_queued && h_merged[r]) r++;
+    if (E.used && r == rounds_queued) return fail(ctx, MG_ERR_HIP, "cluster forest: the rounds did not reach their fixpoint");   // (floor(log2 n) + 1 suffice)
+    const uint64_t count = h_n[0];
+    if (count + h_n[1] != n) return fail(ctx, MG_ERR_HIP, "cluster forest: the chosen edges do not span the clusters");
+    *count_out = count;
+    *n_clusters_out = h_n[1];
+    *n_edges_out = E.n_edges;
+    ctx->forest_rounds = E.used ? r + 1 : 0;
+    ctx->forest_live.assign(h_live.begin(), h_live.begin() + ctx->forest_rounds);
+    ctx->forest_chosen.assign(h_merged.begin(), h_merged.begin() + ctx->forest_rounds);
+    ctx->forest_regrows = E.regrows;
+    ctx->forest_edge_cap = E.cap;
+    if (count > capacity) return fail(ctx, MG_ERR_NOMEM, "cluster forest: more forest edges than `capacity` (see *count_out)");
+    if (!count) return MG_OK;
+    FinishTables ft(ctx);
+    if ((rc = build_finish_tables(ctx, R.s, cut, h_seen, ft)) != MG_OK) return rc;
+    DevBuf<mg::FinishEdge> recs(ctx);
+    HIP_TRY(ctx, recs.alloc(count));
+    HIP_TRY(ctx, mg::launch_forest_finish(finish_args(R.rows, R.cols, R.s, true, nullptr, count, 0, ft, cut), forest, count, recs, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_host, recs, count * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!ft.complete) patch_nan_distances(out_host, count, cut.k);
+    return MG_OK;
+}
+
+int mg_cluster_tri_forest_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                               mg_result *out_host, uint64_t capacity, uint64_t *count_out, uint32_t *label_out_host, uint64_t *n_clusters_out,
+                               uint64_t *n_edges_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!t || !count_out || !n_clusters_out || !n_edges_out || (!out_host && capacity))
+        return fail(ctx, MG_ERR_INVALID, "mg_cluster_tri_forest_host: NULL argument");
+    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_cluster_tri_forest_host: the table carries no lengths");
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, "mg_cluster_tri_forest_host: both filters are off (every pair would be an edge)");
+    return cluster_forest_tri(ctx, t, cut, out_host, capacity, count_out, label_out_host, n_clusters_out, n_edges_out);
+}
+
+int mg_cluster_forest_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *regrows_out, uint64_t *edge_capacity_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (rounds_out) *rounds_out = ctx->forest_rounds;
+    if (regrows_out) *regrows_out = ctx->forest_regrows;
+    if (edge_capacity_out) *edge_capacity_out = ctx->forest_edge_cap;
+    return MG_OK;
+}
+
+int mg_cluster_forest_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *chosen_out, uint64_t capacity, uint64_t *rounds_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!rounds_out || ((!live_out || !chosen_out) && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_cluster_forest_rounds: NULL argument");
+    *rounds_out = ctx->forest_live.size();
+    for (uint64_t r = 0; r < capacity && r < ctx->forest_live.size(); r++) {
+        live_out[r] = ctx->forest_live[r];
+        chosen_out[r] = ctx->forest_chosen[r];
+    }
     return MG_OK;
 }
 

@@ -32,6 +32,7 @@
 
 #include "../../include/mashgpu.h"
 #include "cluster_internal.h"
+#include "forest_key.h"
 #include "compare_internal.h"
 #include "finish_internal.h"
 #include "pvalue.h"
@@ -108,6 +109,9 @@ struct mg_ctx {
     std::map<std::string, std::string> options;
     // mg_cluster_greedy_stats: what the last mg_cluster_tri_greedy_* call of this context needed
     uint64_t greedy_rounds = 0, greedy_batches = 0, greedy_regrows = 0, greedy_edge_cap = 0;
+    // mg_cluster_forest_stats: the same for the last mg_cluster_tri_forest_host call
+    uint64_t forest_rounds = 0, forest_regrows = 0, forest_edge_cap = 0;
+    std::vector<uint64_t> forest_live, forest_chosen;       // mg_cluster_forest_rounds: per round, the live edges it began with and the edges it chose
     // the compare dispatch's prices, corrected from this context's own launches; the event pairs that time a phase
     SparseCosts costs;
     struct CostClock { hipEvent_t a = nullptr, b = nullptr; };

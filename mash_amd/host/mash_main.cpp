@@ -39,6 +39,7 @@
 #include "parse_pool.h"
 #include "taxdb.h"
 #include "../csrc/pvalue.h"
+#include "../csrc/forest_key.h"
 
 using std::cerr;
 using std::cout;
@@ -1767,6 +1768,52 @@ int cmd_triangle(int argc, const char **argv)
 // -R: greedy representative clusters of the same pairs instead (mg_cluster_tri_greedy_host): walking the sketches in input
 // order, a sketch opens a cluster iff no earlier representative is within the threshold, else it joins the first one that is.
 // Lines and numbering are the same (the label is the representative); the host route runs that walk here.
+// -T: the minimum spanning forest of the same pairs instead (cluster_forest below): edge-list lines, not cluster lines.
+
+// `mash cluster -T`: one `triangle -E` line per edge of the minimum spanning forest of the pairs within -d / -v, best first.  The
+// forest is found on the device and its rows - clusters records come back (mg_cluster_tri_forest_host); MASH_AMD_HOST_FINISH=1 takes
+// the edges of tri_filtered's host call, sorts them by the exact fraction and runs Kruskal here.
+int cluster_forest(TriRun &r)
+{
+    vector<mg_result> res;
+    if (!host_finish_wanted()) {
+        res.resize(r.n - 1);
+        uint64_t count = 0, n_clusters = 0, n_edges = 0;
+        if (mg_cluster_tri_forest_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, res.data(), res.size(), &count, nullptr, &n_clusters, &n_edges) != MG_OK)
+            return report_error(r.gpu);
+        res.resize(count);
+        r.clk.lap("compare+mark+append+rounds+sort+finish+copy");
+    } else {
+        vector<mg_edge> edges;
+        vector<mg_result> all;
+        for (Blocks b(1, r.n, kTriFilteredPairs); b.next();) {
+            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                    return mg_compare_tri_filter_host(r.gpu.ctx, r.t, b.r0, b.r1, r.kmer, r.d_max, o, cap, cnt); }))
+                return 1;
+            for (const mg_edge &e : edges) {
+                mg_pair pr;
+                if (finish_edge(e, r.lengths[e.row], r.lengths[e.col], r.kmer, r.kspace, r.p_max, pr))
+                    all.push_back(mg_result{e.row, e.col, pr.numer, pr.denom, pr.distance, pr.p_value});
+            }
+        }
+        std::sort(all.begin(), all.end(), [](const mg_result &a, const mg_result &b) {
+            return mg::forest_before(a.numer, a.denom, mg::forest_rc(a.row, a.col), b.numer, b.denom, mg::forest_rc(b.row, b.col)); });
+        vector<uint32_t> up(r.n);
+        for (uint64_t i = 0; i < r.n; i++) up[i] = (uint32_t)i;
+        auto find = [&](uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; };
+        for (const mg_result &e : all) {
+            const uint32_t a = find(e.row), b = find(e.col);
+            if (a == b) continue;
+            up[std::max(a, b)] = std::min(a, b);
+            res.push_back(e);
+        }
+        r.clk.lap("compare+filter+copy+sort+kruskal");
+    }
+    tri_emit_results(r, res);
+    r.clk.lap("format+write");
+    return 0;
+}
+
 int cmd_cluster(int argc, const char **argv)
 {
     Cmd c;
@@ -1775,6 +1822,7 @@ int cmd_cluster(int argc, const char **argv)
     c.add("list", Opt::Boolean, "l");
     c.add("comment", Opt::Boolean, "C");
     c.add("representatives", Opt::Boolean, "R");
+    c.add("tree", Opt::Boolean, "T");
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "0.05", 0., 1.);
     c.use_sketch_options();
@@ -1790,11 +1838,19 @@ int cmd_cluster(int argc, const char **argv)
                 "  -R        Greedy representative clusters instead of single linkage: in input order, a sketch\n"
                 "            becomes a representative if no earlier representative has an edge to it, and joins the\n"
                 "            first representative that has one otherwise.  No two representatives share an edge and\n"
-                "            every member has an edge to its representative.\n\n";
+                "            every member has an edge to its representative.\n"
+                "  -T        The minimum spanning forest of those pairs instead of clusters: one `mash triangle -E` line\n"
+                "            per forest edge, best first by shared-hashes as an exact fraction, equal fractions in the\n"
+                "            order of `mash triangle -E`.  The lines down to any fraction are the forest, and give the\n"
+                "            single-linkage clusters, of that stricter threshold.  Not with -R.\n\n";
         return 0;
     }
-    const bool comment = c.o("comment").active, greedy = c.o("representatives").active;
+    const bool comment = c.o("comment").active, greedy = c.o("representatives").active, forest = c.o("tree").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
+    if (forest && greedy) {
+        cerr << "ERROR: -" << c.o("tree").id << " and -" << c.o("representatives").id << " cannot be given together." << endl;
+        return 1;
+    }
     if (d_max >= 1.0 && p_max >= 1.0) {
         cerr << "ERROR: With -" << c.o("distance").id << " 1 and -" << c.o("pvalue").id << " 1 every pair is an edge; give a smaller maximum." << endl;
         return 1;
@@ -1808,6 +1864,12 @@ int cmd_cluster(int argc, const char **argv)
     const KmerWarning w = scan_kmer_warning(set);
     const uint64_t n = set.refs.size();
     if (n == 0) return 0;
+    if (forest) {
+        TriRun run(gpu, set, comment, true, 0, d_max, p_max);
+        if (cluster_forest(run)) return 1;
+        run.dt.reset();                                          // (inside the "teardown" lap, as the later lines)
+        return finish_run(set, w, p.reads);
+    }
     vector<uint64_t> lengths;
     DTable dt(upload_all(gpu, set, set.p.sketch_size, &lengths));
     mg_table *t = mg_dtable_local(dt.get(), 0);                  // (several devices selected: the first one's replica)
@@ -2404,7 +2466,7 @@ int main(int argc, const char **argv)
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
         "  dist      Estimate the distance of query sequences to references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n"
-        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance.\n  info      Display information about sketch files.\n"
+        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"

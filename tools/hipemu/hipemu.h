@@ -316,6 +316,12 @@ static inline unsigned long long atomicMin(unsigned long long *p, unsigned long 
     while (o > v && !__atomic_compare_exchange_n(p, &o, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
     return o;
 }
+static inline unsigned long long atomicMax(unsigned long long *p, unsigned long long v)
+{
+    unsigned long long o = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (o < v && !__atomic_compare_exchange_n(p, &o, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return o;
+}
 static inline uint32_t atomicOr(uint32_t *p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
 static inline uint32_t atomicMax(uint32_t *p, uint32_t v)
 {
