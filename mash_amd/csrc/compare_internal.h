@@ -134,6 +134,9 @@ hipError_t launch_sparse_class_pairs(uint2 *out, const uint32_t *cls_rows, const
                                      const uint32_t *inv, hipStream_t stream);
 hipError_t launch_sparse_row_digest(const uint64_t *hashes, uint64_t stride, const uint32_t *cnt, uint32_t n,
                                     unsigned long long *digest, hipStream_t stream);
+// the copy gate's digest: over the positions copy_gate.h names (at most 32 of a row), otherwise as launch_sparse_row_digest
+hipError_t launch_sparse_row_gate(const uint64_t *hashes, uint64_t stride, const uint32_t *cnt, uint32_t n, unsigned long long *digest,
+                                  hipStream_t stream);
 hipError_t launch_sparse_row_equal(const uint64_t *hashes, uint64_t stride, const uint32_t *cnt, const uint2 *pairs, uint32_t npairs,
                                    uint32_t *equal, hipStream_t stream);
 hipError_t launch_sparse_row_counts(const uint32_t *nhash, uint32_t n, uint32_t cap, uint32_t *cnt, hipStream_t stream);
@@ -142,12 +145,13 @@ size_t sparse_offsets_temp_bytes(uint32_t n);
 hipError_t launch_sparse_offsets(const uint32_t *cnt, const uint32_t *inv, uint32_t n, void *temp, uint32_t *off, hipStream_t stream);
 size_t sparse_sort_temp_bytes(uint32_t E, uint32_t end_bit, uint32_t begin_bit);
 uint32_t sparse_img_stride(uint32_t s);          // row stride of a code image
+// rowmap: index row r is read at hashes + rowmap[r] * stride (nullptr: row r) -- only the first kernel reads the table
 hipError_t sparse_build_index(const uint64_t *hashes, uint64_t stride, const uint32_t *off, uint32_t n, uint32_t E,
                               uint32_t rs, uint32_t end_bit, void *temp, size_t temp_bytes, uint64_t *keys_a,
                               uint32_t *idx_a, uint64_t *keys_sorted, uint32_t *idx_sorted, uint32_t *head, uint32_t *gs_of,
                               uint32_t *sorted_rows, uint32_t *gend, uint32_t *code_img, uint32_t *pos_img, void *stat_scratch,
                               uint32_t begin_bit, void *tie_scratch, unsigned long long *incidences, uint32_t *max_group, uint32_t *groups,
-                              uint32_t *bad, uint32_t *tie_overflow, hipStream_t stream);
+                              uint32_t *bad, uint32_t *tie_overflow, hipStream_t stream, const uint32_t *rowmap = nullptr);
 size_t sparse_stat_scratch_bytes();
 uint32_t sparse_sort_begin_bit(uint32_t E, uint32_t end_bit, const char *forced_bits, bool all_bits);
 size_t sparse_tie_scratch_bytes();

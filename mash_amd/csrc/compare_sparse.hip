@@ -37,6 +37,7 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "compare_internal.h"
+#include "copy_gate.h"
 
 namespace mg {
 
@@ -51,13 +52,14 @@ namespace mg {
 // The sort's payload is the entry's index in the images (row * rs + position in the row): the pass that writes
 // the images back needs neither a search for the row nor the compact entry ids.
 
-// keys[e] = value, idx[e] = image index; row r owns the compact range [off[r], off[r + 1]) -- its first min(nhash, s) hashes
-__global__ __launch_bounds__(256) void sp_fill_entries_kernel(const uint64_t *hashes, uint64_t stride, const uint32_t *off,
+// keys[e] = value, idx[e] = image index; row r owns the compact range [off[r], off[r + 1]) -- its first min(nhash, s) hashes.
+// rowmap (nullptr: identity): the table holds index row r at row rowmap[r] (the clustered order read in place).
+__global__ __launch_bounds__(256) void sp_fill_entries_kernel(const uint64_t *hashes, uint64_t stride, const uint32_t *rowmap, const uint32_t *off,
                                                               uint32_t rs, uint64_t *keys, uint32_t *idx)
 {
     const uint32_t row = blockIdx.x;
     const uint32_t b = off[row], cnt = off[row + 1] - b;
-    const uint64_t *src = hashes + (uint64_t)row * stride;
+    const uint64_t *src = hashes + (uint64_t)(rowmap ? rowmap[row] : row) * stride;
     const uint32_t ib = row * rs;
     for (uint32_t p = threadIdx.x; p < cnt; p += 256) {
         keys[b + p] = src[p];
@@ -257,6 +259,27 @@ __global__ __launch_bounds__(256) void sp_row_digest_kernel(const uint64_t *hash
     if (threadIdx.x == 0) digest[row] = s_h[0] + s_h[1] + s_h[2] + s_h[3];
 }
 
+// The copy GATE (copy_gate.h): the same digest over at most 32 sampled positions of the row -- what scan_rows asks of every row
+// to learn whether the table may hold copies at all.  Half a wave per row, a sample per lane: a row costs its 32 sectors, not
+// its 8 KB.  Equal rows still have equal digests; rows that differ between the samples are told apart by find_copies().
+__global__ __launch_bounds__(256) void sp_row_gate_kernel(const uint64_t *hashes, uint64_t stride, const uint32_t *cnt, uint32_t nrows,
+                                                          unsigned long long *digest)
+{
+    static_assert(COPY_GATE_SAMPLES == 32, "half a wave per row");
+    const uint32_t row = blockIdx.x * 8u + (threadIdx.x >> 5), k = threadIdx.x & 31u;
+    const uint32_t n = row < nrows ? cnt[row] : 0u;
+    unsigned long long h = 0;
+    if (k < copy_gate_samples(n)) {
+        const uint32_t p = copy_gate_position(k, n);
+        unsigned long long z = hashes[(uint64_t)row * stride + p] + 0x9E3779B97F4A7C15ull * (unsigned long long)(p + 1);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        h = z ^ (z >> 31);
+    }
+    for (int d = 16; d > 0; d >>= 1) h += __shfl_xor(h, d);
+    if (k == 0 && row < nrows) digest[row] = h;
+}
+
 // pairs[k] = {row, candidate representative}: equal[k] = 1 iff the two rows hold the same cnt values
 __global__ __launch_bounds__(256) void sp_row_equal_kernel(const uint64_t *hashes, uint64_t stride, const uint32_t *cnt,
                                                            const uint2 *pairs, uint32_t npairs, uint32_t *equal)
@@ -277,6 +300,14 @@ hipError_t launch_sparse_row_digest(const uint64_t *hashes, uint64_t stride, con
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(sp_row_digest_kernel, dim3(n), dim3(256), 0, stream, hashes, stride, cnt, digest);
+    return hipGetLastError();
+}
+
+hipError_t launch_sparse_row_gate(const uint64_t *hashes, uint64_t stride, const uint32_t *cnt, uint32_t n, unsigned long long *digest,
+                                  hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(sp_row_gate_kernel, dim3((n + 7u) / 8u), dim3(256), 0, stream, hashes, stride, cnt, n, digest);
     return hipGetLastError();
 }
 
@@ -571,10 +602,10 @@ hipError_t sparse_build_index(const uint64_t *hashes, uint64_t stride, const uin
                               uint32_t *idx_a, uint64_t *keys_sorted, uint32_t *idx_sorted, uint32_t *head, uint32_t *gs_of,
                               uint32_t *sorted_rows, uint32_t *gend, uint32_t *code_img, uint32_t *pos_img, void *stat_scratch,
                               uint32_t begin_bit, void *tie_scratch, unsigned long long *incidences, uint32_t *max_group, uint32_t *groups,
-                              uint32_t *bad, uint32_t *tie_overflow, hipStream_t stream)
+                              uint32_t *bad, uint32_t *tie_overflow, hipStream_t stream, const uint32_t *rowmap)
 {
     if (n == 0 || E == 0) return hipSuccess;
-    hipLaunchKernelGGL(sp_fill_entries_kernel, dim3(n), dim3(256), 0, stream, hashes, stride, off, rs, keys_a, idx_a);
+    hipLaunchKernelGGL(sp_fill_entries_kernel, dim3(n), dim3(256), 0, stream, hashes, stride, rowmap, off, rs, keys_a, idx_a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = rocprim::radix_sort_pairs(temp, temp_bytes, (const uint64_t *)keys_a, keys_sorted, (const uint32_t *)idx_a, idx_sorted,

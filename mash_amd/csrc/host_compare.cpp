@@ -629,7 +629,8 @@ int SparseJobRun::open_index()
 // on round trips, wait behind them (round 5 measured exactly that with 2 - 16 workgroups per CU and dropped it; 64
 // workgroups write ~4 TB/s and the build takes 10 ms instead of 8, with the fill's 6.7 ms gone).  What is left when the build
 // has ended is taken from the same counter at full speed on the context's stream (end_prefill), so a pace that is too slow
-// costs little.  C3 per table: 15.4 -> 11.8 ms (tools/aside_sweep.sh).
+// costs little.  C3 per table: 15.4 -> 11.8 ms (tools/aside_sweep.sh).  (Swept again since the build reads the table in place:
+// no naps gained 0.06 - 0.14 ms per table, which is the spread of the runs -- the pace stays)
 // MASHGPU_FILL_ASIDE = "<workgroups>[,<naps of 64 cycles per 4 KB>[,<work-items>]]"; 0: off.
 int SparseJobRun::prefill()
 {

@@ -12,11 +12,16 @@
 // real hash equal to the padding value, no memory) is marked unusable and keeps the tile engine.
 //
 // The build is one object (SparseIndexBuild) with one function per phase, run in this order:
-//   scan_rows       everything the host must know about the rows is LAUNCHED (classes, copy suspects, clustering or
-//                   neighbour links) and read back behind through one pinned block: the first of three waits;
-//   order_rows      the first host pass over the rows (counts, densities), the table copied in clustered order (with
-//                   the build's window offsets if the plan is known already), which neighbours form chains;
-//   find_copies     only if there are suspects: rows verified value by value, classes of identical rows;
+//   scan_rows       everything the host must know about the rows is LAUNCHED (classes, copy suspects from a SAMPLE of every
+//                   row -- copy_gate.h --, clustering or neighbour links) and read back behind through one pinned block: the
+//                   first of three waits;
+//   order_rows      the first host pass over the rows (counts, densities); the clustered order becomes a ROW MAP through
+//                   which the tiles read the table in place (the build's window offsets, K0, are queued here if the plan is
+//                   known already); which neighbours form chains;
+//   copy_rows       the table copied in the index's order -- only for find_copies with suspects, whose kernels compare rows by
+//                   index row (MASHGPU_COMPARE_ROWCOPY=1: always, up front, the build as it was); the general sort reads
+//                   through the map like the tiles;
+//   find_copies     only if there are suspects: every row digested in full, rows verified value by value, classes of identical rows;
 //   lay_out         offsets, short rows, the sort's bits, the tiles' plan, every buffer, the uploads;
 //   build_by_tiles  index_build.hip in three stages with the candidate groups laid out in between: the second wait
 //                   (an event behind the bucket sorts);  build_by_sort: rounds 3-4's way, for what the tiles refuse;
@@ -116,7 +121,7 @@ struct SparseIndexBuild {
     std::vector<uint64_t> hc_last;
     std::vector<uint32_t> hc_nh, inv_v, lab_v;
     const uint32_t *inv = nullptr, *lab_sorted = nullptr;   // the clustering's read-backs (pinned memory or the vectors); lab_sorted == nullptr: no labels
-    uint32_t nflag = 0;
+    uint32_t nflag = 0, gate_suspects = 0;                  // suspects: of the gate's sample, then (find_copies) of the whole rows
     size_t tb_dup = 0, tb_cl = 0;
     bool cluster_q = false, links_q = false;
 
@@ -129,7 +134,9 @@ struct SparseIndexBuild {
     double dens[65] = {0};                                  // by bit length of a row's largest hash: values per unit of the hash range
     double dens0 = 0;                                       // ... and all of them: the density where the table is densest (below every row's largest hash)
     std::vector<uint32_t> rep;                              // empty: no copies
-    const uint64_t *H = nullptr;                            // what the index is built from
+    const uint64_t *H = nullptr;                            // what the index is built from ...
+    const uint32_t *rowmap = nullptr;                       // ... index row a at H + rowmap[a] * stride (nullptr: row a; the clustered order read in place: sp->inv)
+    uint64_t label_run = 0;                                 // longest_label_run of the labels order_rows settled on (none: 0)
     mg::IxPlan early_plan;                                  // the tiles' plan, if it could be made before the clustered copy ...
     DevBuf<unsigned char> d_lb;                             // ... whose kernel then left the rows' window offsets here
     bool lb_made = false;
@@ -168,6 +175,7 @@ struct SparseIndexBuild {
     {}
 
     int unusable(const char *why) { sp->usable = false; sp->why = why; stop = true; return MG_OK; }
+
 
     // the device's counts in the index's order: only if somebody asks (copy suspects, no clustering to be had)
     hipError_t counts_to_device()
@@ -213,7 +221,7 @@ struct SparseIndexBuild {
     hipError_t tiles(const TileScratch &w, int stages)
     {
         const mg::IxLeaders lv = lead.view(d_lead_rows);
-        return mg::index_build(plan, H, sp->off, d_lb, w.tcnt, w.start, w.big, w.pk, w.tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
+        return mg::index_build_mapped(plan, H, rowmap, sp->off, d_lb, w.tcnt, w.start, w.big, w.pk, w.tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
                                sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf, lead_ready ? &lv : nullptr,
                                ctx->stream, stages);
     }
@@ -232,6 +240,7 @@ struct SparseIndexBuild {
     }
 
     int scan_rows();
+    int copy_rows();
     int order_rows();
     int find_copies();
     int lay_out();
@@ -252,8 +261,9 @@ int SparseIndexBuild::scan_rows()
 {
     // ---- ONE wait for everything the host must know before it can lay the index out (round 4 waited four times here):
     //  * the rows' hash counts and largest hashes, if the table is new to the library (table_classes' kernel);
-    //  * whether any two rows may be copies of each other: every row's digest, sorted on the device; rows whose digest
-    //    and length equal their predecessor's are suspects.  Taken in the TABLE's order -- whether copies exist is a
+    //  * whether any two rows may be copies of each other: every row's digest over a sample of its entries (the GATE,
+    //    copy_gate.h: 32 positions, not the row's 8 KB), sorted on the device; rows whose digest and length equal their
+    //    predecessor's are suspects.  Taken in the TABLE's order -- whether copies exist is a
     //    property of the set of rows; only a table that has suspects digests its rows again in the index's order, has
     //    them verified value by value and keeps the copies out of the index (see compare_sparse.hip);
     //  * the clustered variant: rows that share one of their smallest hashes next to each other (labels on the device,
@@ -286,7 +296,7 @@ int SparseIndexBuild::scan_rows()
         // the rows' entry counts min(nhash, s) straight from the table's counts
         if (e == hipSuccess) e = mg::launch_sparse_row_counts(t->nhash, (uint32_t)n, (uint32_t)std::min<uint64_t>(t->s, s), d_cnt, ctx->stream);
         if (e == hipSuccess && dedup) {
-            e = mg::launch_sparse_row_digest(t->hashes, t->s, d_cnt, (uint32_t)n, d_dig, ctx->stream);
+            e = mg::launch_sparse_row_gate(t->hashes, t->s, d_cnt, (uint32_t)n, d_dig, ctx->stream);
             if (e == hipSuccess)
                 e = mg::launch_sparse_dup_suspects(d_dig, d_cnt, (uint32_t)n, d_tmp_dup, tb_dup, d_dig_sorted, d_rows_sorted, d_flags, d_nflag, ctx->stream);
         }
@@ -353,6 +363,7 @@ int SparseIndexBuild::scan_rows()
         if (cluster_q) { inv = p_inv; lab_sorted = p_lab; }
         if (e != hipSuccess) return fail(ctx, MG_ERR_HIP, std::string("compare (index: rows, copies, order): ") + hipGetErrorString(e));
     }
+    gate_suspects = nflag;
     if (need_classes) {
         t->cls.swap(hc_cls);
         t->last.swap(hc_last);
@@ -387,8 +398,7 @@ int SparseIndexBuild::order_rows()
             dens0 += d;
         }
     }
-    // ---- the clustered variant: the table copied in the clustered order; everything below then works on the copy as if
-    // it were the table
+    // ---- the clustered variant: index row a is table row inv[a]
     H = t->hashes;
     // A job over a RANGE of rows (split != 0) pays for the permuted copy and the clustering's order only where the collection
     // has large families: the split order keeps the pairs INSIDE each segment of a family dense, the pairs across the cut are
@@ -398,7 +408,10 @@ int SparseIndexBuild::order_rows()
     bool keep_table_order = false;
     // (a merge costs what the sketches are long: the rule is on rows x sketch size, 128 rows at s = 1000 -- C5's families of
     //  50 + 50 rows at s = 10 000 take the split order: 7 x against 10 x their share of a whole pass)
-    if (cluster_q && split != 0 && lab_sorted && !ctx_opt(ctx, "MASHGPU_SPLIT_ALWAYS") && longest_label_run(lab_sorted, n) * (uint64_t)s < kSplitMinRun * 1000ull) {
+    // (the labels are walked ONCE: three rules ask for their longest run -- this one, the early plan below, lay_out's; what
+    //  lay_out sees is set at the end, when it is settled whether the labels are used at all)
+    const uint64_t run = cluster_q ? longest_label_run(lab_sorted, n) : 0;
+    if (cluster_q && split != 0 && lab_sorted && !ctx_opt(ctx, "MASHGPU_SPLIT_ALWAYS") && run * (uint64_t)s < kSplitMinRun * 1000ull) {
         keep_table_order = true;
         lab_sorted = nullptr;
     }
@@ -406,42 +419,54 @@ int SparseIndexBuild::order_rows()
         bool identity = true;
         for (uint64_t a = 0; a < n && identity; a++) identity = inv[a] == a;
         if (!identity && !keep_table_order) {
-            // (Measured and dropped: this copy queued BEFORE the read-backs above.  They are copies into pageable memory and
-            //  wait for whatever the stream holds in front of them -- the copy kernel included; the build started 0.4 ms later.)
+            // The table is read IN PLACE, through the map sp->inv: the tiles fetch short segments of 512 rows that lie a row
+            // stride apart wherever the rows stand, so a copy in clustered order saves them nothing and costs a pass over the
+            // table each way; the general sort (build_by_sort: MASHGPU_SPARSE_INDEX=sort and verify, a refusal by the
+            // tiles) reads every row once, from wherever it stands.  The copy (sp->phashes) is made only for the suspects of
+            // find_copies, whose kernels compare rows by index row -- and under MASHGPU_COMPARE_ROWCOPY=1, where the build is
+            // what it was (for comparisons).
+            const char *fc = ctx_opt(ctx, "MASHGPU_COMPARE_ROWCOPY");
+            const bool copy_now = fc && atoi(fc) != 0;
             void *pi = nullptr, *ph = nullptr;
-            if (ctx_malloc(ctx, &pi, n * 4) != hipSuccess || ctx_malloc(ctx, &ph, std::max<uint64_t>(n * t->s, 1) * 8) != hipSuccess) {
+            if (ctx_malloc(ctx, &pi, n * 4) != hipSuccess || (copy_now && ctx_malloc(ctx, &ph, std::max<uint64_t>(n * t->s, 1) * 8) != hipSuccess)) {
                 (void)hipGetLastError();
                 ctx_free(ctx, pi);
-                lab_sorted = nullptr;                       // no memory for the copy: the table's own order
+                lab_sorted = nullptr;                       // no memory for the map (the copy): the table's own order
             } else {
                 sp->inv = static_cast<uint32_t *>(pi);
                 sp->phashes = static_cast<uint64_t *>(ph);
                 HIP_TRY(ctx, hipMemcpyAsync(sp->inv, d_inv, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
                 // With no copy suspects every row enters the index, so its plan is known NOW (it depends on sums over the rows,
-                // not on their order): the copy kernel then leaves the rows' window offsets (K0 of index_build.hip) on its way
-                // -- one pass over the table less.
-                if (ix_tiles && !(dedup && nflag) && E_all > 0 && E_all < (1ull << 31) && longest_label_run(lab_sorted, n) <= kTilesLongestRun) {
+                // not on their order): the rows' window offsets (K0 of index_build.hip) are queued here, and the host lays the
+                // index out while they are made.  (With the copy: left by the copy kernel on its way.)
+                if (ix_tiles && !(dedup && nflag) && E_all > 0 && E_all < (1ull << 31) && run <= kTilesLongestRun) {
                     early_plan = mg::index_plan((uint32_t)n, (uint32_t)E_all, s, sp->rs, t->s, maxv, dens0, ix_verify);
                     if (early_plan.ok && d_lb.alloc(early_plan.lb_bytes) == hipSuccess) {
-                        HIP_TRY(ctx, mg::index_gather_rows(early_plan, t->hashes, sp->inv, d_cnt, sp->phashes, d_lb, ctx->stream));
+                        if (copy_now) HIP_TRY(ctx, mg::index_gather_rows(early_plan, t->hashes, sp->inv, d_cnt, sp->phashes, d_lb, ctx->stream));
+                        else HIP_TRY(ctx, mg::index_window_offsets(early_plan, t->hashes, sp->inv, d_cnt, d_lb, ctx->stream));
                         lb_made = true;
                     } else {
                         (void)hipGetLastError();
                     }
                 }
-                if (!lb_made) HIP_TRY(ctx, mg::launch_dense_gather_rows(t->hashes, t->s, sp->inv, (uint32_t)n, sp->phashes, ctx->stream));
-                H = sp->phashes;
+                if (copy_now) {
+                    if (!lb_made) HIP_TRY(ctx, mg::launch_dense_gather_rows(t->hashes, t->s, sp->inv, (uint32_t)n, sp->phashes, ctx->stream));
+                    H = sp->phashes;
+                } else {
+                    rowmap = sp->inv;
+                }
                 cnt_perm.resize(n);
                 for (uint64_t a = 0; a < n; a++) cnt_perm[a] = cnt_true[inv[a]];
                 cnt_true.swap(cnt_perm);
                 // (the device's counts follow only if somebody asks -- copy suspects, no clustering to be had: a copy from
-                //  pageable memory waits for the gather in front of it, and the host has the index to plan meanwhile)
+                //  pageable memory waits for the kernel in front of it, and the host has the index to plan meanwhile)
                 cnt_stale = true;
             }
         }
     } else {
         lab_sorted = nullptr;
     }
+    label_run = lab_sorted ? run : 0;
     // which neighbouring rows are near-copies of each other (dense groups, compare_dense.hip)
     if (want_dense && n >= 8 && s <= 16384 && lab_sorted) {
         link.assign(n, 0);                                  // clustered variant: neighbours with the same label
@@ -449,6 +474,9 @@ int SparseIndexBuild::order_rows()
         for (uint64_t a = 1; a < n; a++) link[a] = (a != split && lab_sorted[a] == lab_sorted[a - 1] && cnt_true[a] && cnt_true[a - 1]) ? 1 : 0;
     } else if (cluster_q && want_dense && n >= 8 && s <= 16384 && d_link.alloc(n) == hipSuccess) {
         // (the clustering was asked for and came to nothing: the neighbours of the table's own order after all)
+        // (its kernel addresses rows by index row: no map is set on the ways that lead here, and if one ever is, the copy)
+        const int rc = copy_rows();
+        if (rc != MG_OK || stop) return rc;
         link.resize(n);
         HIP_TRY(ctx, counts_to_device());
         HIP_TRY(ctx, mg::launch_dense_neighbors(H, t->s, d_cnt, (uint32_t)n, d_link, ctx->stream));
@@ -461,10 +489,27 @@ int SparseIndexBuild::order_rows()
     return MG_OK;
 }
 
+// The table copied in the index's order, for kernels that address rows by index row; H is the copy from here on.  (The window
+// offsets K0 may have left through the map are those of the copy's rows.)
+int SparseIndexBuild::copy_rows()
+{
+    if (!rowmap) return MG_OK;
+    void *ph = nullptr;
+    if (ctx_malloc(ctx, &ph, std::max<uint64_t>(n * t->s, 1) * 8) != hipSuccess) return no_memory();
+    sp->phashes = static_cast<uint64_t *>(ph);
+    HIP_TRY(ctx, mg::launch_dense_gather_rows(t->hashes, t->s, rowmap, (uint32_t)n, sp->phashes, ctx->stream));
+    H = sp->phashes;
+    rowmap = nullptr;
+    return MG_OK;
+}
+
 int SparseIndexBuild::find_copies()
 {
     if (dedup && nflag) {
-        // suspects: the digests again, of the rows the index will be built from and in its order
+        // suspects (of the gate's sample): the digests again -- of ALL of every row's entries, of the rows the index will be
+        // built from and in its order
+        const int rc = copy_rows();
+        if (rc != MG_OK || stop) return rc;
         HIP_TRY(ctx, counts_to_device());
         HIP_TRY(ctx, mg::launch_sparse_row_digest(H, t->s, d_cnt, (uint32_t)n, d_dig, ctx->stream));
         HIP_TRY(ctx, mg::launch_sparse_dup_suspects(d_dig, d_cnt, (uint32_t)n, d_tmp_dup, tb_dup, d_dig_sorted, d_rows_sorted, d_flags, d_nflag, ctx->stream));
@@ -550,7 +595,7 @@ int SparseIndexBuild::lay_out()
     sort_begin_bit = mg::sparse_sort_begin_bit(E, end_bit, ctx_opt(ctx, "MASHGPU_SPARSE_SORT_BITS"), ctx_opt(ctx, "MASHGPU_SPARSE_SORT_ALL_BITS") != nullptr);
     if (sort_begin_bit > 0 && !ctx_opt(ctx, "MASHGPU_SPARSE_SORT_BITS")) sort_begin_bit = mg::sort_begin_bit_from_density(dens, end_bit, sort_begin_bit);
     const bool tiles_hopeless = ix_tiles && !ix_verify && lab_sorted && !ctx_opt(ctx, "MASHGPU_SPARSE_INDEX") &&
-                                longest_label_run(lab_sorted, n) > kTilesLongestRun;
+                                label_run > kTilesLongestRun;
     if (ix_tiles && !tiles_hopeless) plan = mg::index_plan((uint32_t)n, E, s, sp->rs, t->s, maxv, dens0, ix_verify);
     else if (tiles_hopeless) plan.why = "a clade of more rows than a bucket's sort takes";
     // the tiles' plan (index_build.hip; MASHGPU_SPARSE_INDEX=sort: none).  The window offsets the clustered copy left are
@@ -707,7 +752,8 @@ int SparseIndexBuild::build_by_tiles()
 int SparseIndexBuild::build_by_sort()
 {
     if (built && !ix_verify) return MG_OK;
-    // ---- the general way: every entry through a radix sort on the values' leading bits (compare_sparse.hip)
+    // ---- the general way: every entry through a radix sort on the values' leading bits (compare_sparse.hip); its first
+    // kernel reads the rows, through the map like the tiles
     const size_t sort_bytes = mg::sparse_sort_temp_bytes(E, end_bit, sort_begin_bit);
     DevBuf<unsigned char> temp_sort(ctx), d_ties(ctx);
     DevBuf<uint64_t> keys_a(ctx), v_keys(ctx);
@@ -730,7 +776,7 @@ int SparseIndexBuild::build_by_sort()
         if (e == hipSuccess)
             e = mg::sparse_build_index(H, t->s, sp->off, (uint32_t)n, E, sp->rs, end_bit, temp_sort, sort_bytes, keys_a, idx_a, o_keys, idx_sorted,
                                        /*head=*/idx_a, o_gs, o_rows, o_gend, o_code, o_pos, d_slots, begin_bit, d_ties, &d_stat.p->shared,
-                                       &d_stat.p->max_group, &d_stat.p->groups, &d_stat.p->bad, &d_stat.p->tie_overflow, ctx->stream);
+                                       &d_stat.p->max_group, &d_stat.p->groups, &d_stat.p->bad, &d_stat.p->tie_overflow, ctx->stream, rowmap);
         // (verify: the order is the tiles'), the statistics, one wait
         if (e == hipSuccess && !built && want_order) e = row_order();
         if (e == hipSuccess) e = hipMemcpyAsync(&h_stat, d_stat, sizeof(Stat), hipMemcpyDeviceToHost, ctx->stream);
@@ -903,9 +949,12 @@ int SparseIndexBuild::dense_groups()
                     sp->dgroups_host.size(), (unsigned long long)rows_in, sp->dn_wmax);
         }
     }
-    if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+    if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG")) {
         fprintf(stderr, "compare sparse: index of %llu rows (%llu copies of earlier rows), s %u: %u entries, %u distinct, shared %llu, largest run %u, %.2f ms\n",
                 (unsigned long long)n, (unsigned long long)sp->copies, s, E, sp->G, (unsigned long long)sp->shared, sp->max_group, sp->build_ms);
+        fprintf(stderr, "compare sparse: rows %s; the copy gate had %u suspects\n",
+                !sp->inv ? "in the table's order" : sp->phashes ? "in clustered order, copied" : "in clustered order, read in place", gate_suspects);
+    }
     return MG_OK;
 }
 

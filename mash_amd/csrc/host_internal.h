@@ -177,7 +177,8 @@ struct mg_table {
         // The index may be built on the table in ANOTHER ROW ORDER (rows that belong together next to each other, so that
         // they form dense groups whatever the order of the collection; compare_dense.hip: dense_cluster_rows): `clustered`
         // says this variant was asked for, inv != nullptr that the order differs -- index row a is table row inv[a], the
-        // index reads the reordered copy `phashes`, and every kernel that writes results maps rows back.  Only the plain
+        // index build reads the table in place through inv (a reordered copy `phashes` exists only where the build had copy
+        // suspects to verify: nullptr otherwise), and every kernel that writes results maps rows back.  Only the plain
         // full-triangle job uses it (row ranges, rect and list jobs address table rows and take the other variant).
         bool clustered = false;
         uint32_t split = 0;                // clustered: the rows from `split` on form a segment of their own (a triangle job over [split, n))

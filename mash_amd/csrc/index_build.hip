@@ -167,12 +167,17 @@ __global__ __launch_bounds__(256) void ix_gather_offsets_kernel(IxGeom g, const 
     for (uint32_t x = (uint32_t)(wl + 1) + tid; x <= g.NW; x += 256u) o[x] = (uint16_t)cnt;
 }
 
-__global__ __launch_bounds__(256) void ix_window_offsets_kernel(IxGeom g, const uint64_t *H, const uint32_t *off, uint16_t *lb)
+// K0 on its own.  rowmap (nullptr: identity): index row `row` is table row rowmap[row] -- the table is read in place, no copy in
+// the index's order exists.  The row's entry count: cnt_table[table row] if given (counts in the TABLE's order: what the host has
+// before the index is laid out), else from the index's offsets.
+__global__ __launch_bounds__(256) void ix_window_offsets_kernel(IxGeom g, const uint64_t *H, const uint32_t *rowmap, const uint32_t *off,
+                                                                const uint32_t *cnt_table, uint16_t *lb)
 {
     const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (row < g.n) {
-        const uint32_t cnt = off[row + 1] - off[row];
-        const uint64_t *src = H + (uint64_t)row * g.stride;
+        const uint32_t trow = rowmap ? rowmap[row] : row;
+        const uint32_t cnt = cnt_table ? cnt_table[trow] : off[row + 1] - off[row];
+        const uint64_t *src = H + (uint64_t)trow * g.stride;
         uint16_t *out = lb + (uint64_t)row * (g.NW + 1u);
         const uint32_t wsh = g.shift + g.bw_log;
         for (uint32_t p = lane; p < cnt; p += 64u) {
@@ -188,10 +193,12 @@ __global__ __launch_bounds__(256) void ix_window_offsets_kernel(IxGeom g, const 
 // ------------------------------------------------------------------------------------------------
 // K1: cnt[blk][bucket] = entries of the block's rows in the bucket, for the buckets of the tile's window.
 // The loads of the eight rounds of rows are issued before any is used (a round at a time cost a memory latency each).
+// rowmap (nullptr: identity): where the table holds index row row0 + r; asked for in the step that asks for the row's window
+// offsets, so the values' loads wait for one round trip as before.
 constexpr uint32_t IX_ROUNDS = IX_RB / (IX_NT / IX_LPR);       // 8 rounds of 64 rows
 
-__global__ __launch_bounds__(IX_NT) void ix_tile_count_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint16_t *__restrict__ lb,
-                                                              uint32_t *__restrict__ cnt)
+__global__ __launch_bounds__(IX_NT) void ix_tile_count_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint32_t *__restrict__ rowmap,
+                                                              const uint16_t *__restrict__ lb, uint32_t *__restrict__ cnt)
 {
     __shared__ uint32_t s_hist[IX_BW_MAX];
     uint32_t blk = 0, w = 0;
@@ -199,29 +206,29 @@ __global__ __launch_bounds__(IX_NT) void ix_tile_count_kernel(IxGeom g, const ui
     const uint32_t tid = threadIdx.x, sub = tid % IX_LPR;
     const uint32_t row0 = blk * IX_RB, nrows = g.n - row0 < IX_RB ? g.n - row0 : IX_RB;
     if (tid < g.BW) s_hist[tid] = 0;
-    uint32_t lo[IX_ROUNDS], hi[IX_ROUNDS];
+    uint32_t lo[IX_ROUNDS], hi[IX_ROUNDS], tr[IX_ROUNDS];       // tr: the table's row
+    const uint32_t trow0 = rowmap ? rowmap[row0] : row0;      // (uniform: what a lane without an entry reads)
 #pragma unroll
     for (uint32_t it = 0; it < IX_ROUNDS; it++) {
-        const uint32_t r = it * (IX_NT / IX_LPR) + tid / IX_LPR;
-        const uint16_t *p = lb + (uint64_t)(row0 + (r < nrows ? r : 0u)) * (g.NW + 1u) + w;
+        const uint32_t r = it * (IX_NT / IX_LPR) + tid / IX_LPR, rc = r < nrows ? r : 0u;
+        const uint16_t *p = lb + (uint64_t)(row0 + rc) * (g.NW + 1u) + w;
         const uint32_t a = p[0], b = p[1];
+        tr[it] = rowmap ? rowmap[row0 + rc] : row0 + rc;
         lo[it] = a;
         hi[it] = r < nrows ? b : a;
     }
     uint64_t v[IX_ROUNDS];
 #pragma unroll
     for (uint32_t it = 0; it < IX_ROUNDS; it++) {
-        const uint32_t r = it * (IX_NT / IX_LPR) + tid / IX_LPR;
         const bool in = lo[it] + sub < hi[it];
-        v[it] = H[in ? (uint64_t)(row0 + r) * g.stride + lo[it] + sub : (uint64_t)row0 * g.stride];
+        v[it] = H[in ? (uint64_t)tr[it] * g.stride + lo[it] + sub : (uint64_t)trow0 * g.stride];
     }
     __syncthreads();
 #pragma unroll
     for (uint32_t it = 0; it < IX_ROUNDS; it++) {
-        const uint32_t r = it * (IX_NT / IX_LPR) + tid / IX_LPR;
         if (lo[it] + sub < hi[it]) {
             atomicAdd(&s_hist[(uint32_t)(v[it] >> g.shift) & (g.BW - 1u)], 1u);
-            const uint64_t *src = H + (uint64_t)(row0 + r) * g.stride;         // (a row with more than IX_LPR entries in the window)
+            const uint64_t *src = H + (uint64_t)tr[it] * g.stride;             // (a row with more than IX_LPR entries in the window)
             for (uint32_t k = lo[it] + sub + IX_LPR; k < hi[it]; k += IX_LPR) atomicAdd(&s_hist[(uint32_t)(src[k] >> g.shift) & (g.BW - 1u)], 1u);
         }
     }
@@ -303,6 +310,8 @@ __global__ __launch_bounds__(1024) void ix_bucket_scan_kernel(IxGeom g, uint32_t
 // read (row by row, positions ascending); LSD passes of 4 bits.  A work-item owns the entries [M t, M t + M) of the current
 // order and sixteen private counters, so the order inside a digit is kept without any ranking among lanes.
 // cnt: 16 x IX_NT u16 of LDS.  Returns the array that holds the result.  The caller has a barrier in front.
+// (K3 keeps its block's row map in cnt while no sort runs and restores it behind every piece: cnt is this function's from its
+//  first statement to the barrier that ends its last pass, and nothing of it may be expected to survive a call.)
 __device__ __forceinline__ uint32_t *ix_tile_sort(uint32_t *src, uint32_t *dst, uint16_t *cnt, uint32_t *part, uint32_t np, uint32_t npass)
 {
     const uint32_t tid = threadIdx.x, i0 = tid * IX_M;
@@ -355,7 +364,12 @@ constexpr uint32_t IXL_PACK = 0, IXL_PA = IXL_PACK + IX_PCAP * 8u, IXL_PB = IXL_
 
 // K3: the tile's entries, sorted by bucket, go to pk as one piece per bucket (stable: the block's rows in order, positions
 // ascending); where each entry went is left in the position image (K5 reads {code, position} back from there).
-__global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint16_t *__restrict__ lb,
+// rowmap (nullptr: identity): where the table holds the block's rows.  Every work-item asks for its row's with the row's window
+// offsets and keeps it; the rounds below read the rows' from LDS.  Two workgroups' LDS fill a CU to within 2 KB, so the map of
+// the block has no array of its own: it stands in the sort's counters, which are dead until the piece's entries are loaded,
+// and is put back there behind every piece.  The packed word and the images keep the INDEX row.
+__global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint32_t *__restrict__ rowmap,
+                                                                  const uint16_t *__restrict__ lb,
                                                                   const uint32_t *__restrict__ colpre, const uint32_t *__restrict__ start,
                                                                   const uint32_t *__restrict__ flags, uint64_t *__restrict__ pk,
                                                                   uint32_t *__restrict__ slot_img)
@@ -369,17 +383,20 @@ __global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, c
     uint32_t *s_hist = reinterpret_cast<uint32_t *>(lds + IXL_HIST);
     uint32_t *s_gbase = reinterpret_cast<uint32_t *>(lds + IXL_GBASE);
     uint32_t *s_part = reinterpret_cast<uint32_t *>(lds + IXL_PART);
+    uint32_t *s_trow = reinterpret_cast<uint32_t *>(lds + IXL_CNT);      // (IX_RB u32 of the sort's 16 x IX_NT u16)
+    static_assert(IX_RB * 4u <= 16u * IX_NT * 2u && IX_RB == IX_NT, "the block's row map fits the sort's counters, a row per work-item");
     uint32_t blk = 0, w = 0;
     if (!ix_tile_id(g, blk, w)) return;                  // uniform
     const uint32_t tid = threadIdx.x, sub = tid % IX_LPR;
     IX_CLK_BEGIN();
     const uint32_t row0 = blk * IX_RB, nrows = g.n - row0 < IX_RB ? g.n - row0 : IX_RB;
-    uint32_t len = 0, gb = 0;
+    uint32_t len = 0, gb = 0, trow = 0;
     if (tid < g.BW) {                                    // (asked for before the scan waits for the segments' bounds)
         const uint32_t bg = w * g.BW + tid;
         gb = start[bg] + colpre[(uint64_t)blk * g.Bp + bg];
     }
     if (tid < nrows) {
+        trow = rowmap ? rowmap[row0 + tid] : row0 + tid;
         const uint16_t *p = lb + (uint64_t)(row0 + tid) * (g.NW + 1u) + w;
         const uint32_t lo = p[0];
         len = (uint32_t)p[1] - lo;
@@ -389,6 +406,7 @@ __global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, c
     const uint32_t pre = ix_block_scan_sum(len, s_part, total);
     if (total == 0) return;                              // uniform
     s_rowpre[tid] = pre;
+    s_trow[tid] = trow;
     if (tid == IX_NT - 1u) s_rowpre[IX_NT] = total;
     if (tid < g.BW) {
         s_gbase[tid] = gb;
@@ -410,7 +428,7 @@ __global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, c
             const uint32_t i = rp + sub;
             const bool in = sub < ln && i >= i0 && i < i0 + np;
             at[it] = in ? i - i0 : 0xFFFFFFFFu;
-            v[it] = H[in ? (uint64_t)(row0 + r) * g.stride + s_lo[rc] + sub : (uint64_t)row0 * g.stride];
+            v[it] = H[in ? (uint64_t)s_trow[rc] * g.stride + s_lo[rc] + sub : (uint64_t)s_trow[0] * g.stride];
         }
 #pragma unroll
         for (uint32_t it = 0; it < IX_ROUNDS; it++) {
@@ -427,7 +445,7 @@ __global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, c
         for (uint32_t r = tid / IX_LPR; r < nrows; r += IX_NT / IX_LPR) {
             const uint32_t rp = s_rowpre[r], ln = s_rowpre[r + 1u] - rp;
             if (ln <= IX_LPR || rp + ln <= i0 || rp >= i0 + np) continue;
-            const uint64_t *src = H + (uint64_t)(row0 + r) * g.stride + s_lo[r];
+            const uint64_t *src = H + (uint64_t)s_trow[r] * g.stride + s_lo[r];
             for (uint32_t k = sub + IX_LPR; k < ln; k += IX_LPR) {
                 const uint32_t i = rp + k;
                 if (i < i0 || i >= i0 + np) continue;
@@ -494,6 +512,7 @@ __global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, c
             s_gbase[tid] += add;
             s_hist[tid] = 0;
         }
+        s_trow[tid] = trow;                               // (the sort's counters stood here)
         __syncthreads();
     }
 }
@@ -1334,10 +1353,27 @@ hipError_t index_debug_swap(const IxPlan &plan, void *pk_v, const void *start_v,
     return hipGetLastError();
 }
 
+hipError_t index_window_offsets(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *cnt_table, void *lb_v, hipStream_t stream)
+{
+    if (!plan.ok) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ix_window_offsets_kernel, dim3((plan.g.n + 3u) / 4u), dim3(256), 0, stream, plan.g, hashes, rowmap, (const uint32_t *)nullptr, cnt_table,
+                       static_cast<uint16_t *>(lb_v));
+    return hipGetLastError();
+}
+
 hipError_t index_build(const IxPlan &plan, const uint64_t *hashes, const uint32_t *off, void *lb_v, void *cnt_v, void *start_v, void *big_v, void *pk_v, void *tc_v,
                        uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of, uint32_t *code_img, uint32_t *pos_img,
                        void *stat_scratch, unsigned long long *incidences, uint32_t *max_group, uint32_t *groups, uint32_t *flags,
                        const IxLeaders *leaders, hipStream_t stream, int stages)
+{
+    return index_build_mapped(plan, hashes, nullptr, off, lb_v, cnt_v, start_v, big_v, pk_v, tc_v, keys_sorted, sorted_rows, gend, gs_of, code_img, pos_img,
+                              stat_scratch, incidences, max_group, groups, flags, leaders, stream, stages);
+}
+
+hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *off, void *lb_v, void *cnt_v, void *start_v,
+                              void *big_v, void *pk_v, void *tc_v, uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of,
+                              uint32_t *code_img, uint32_t *pos_img, void *stat_scratch, unsigned long long *incidences, uint32_t *max_group,
+                              uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages)
 {
     // (leaders: looked at by stage 2 only)
     if (!plan.ok) return hipErrorInvalidValue;
@@ -1351,13 +1387,14 @@ hipError_t index_build(const IxPlan &plan, const uint64_t *hashes, const uint32_
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(ix_tile_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)IXL_BYTES);
         if (e != hipSuccess) return e;
         const uint32_t tiles = 8u * ((g.nseq + 7u) / 8u);
-        if (!(stages & 8)) hipLaunchKernelGGL(ix_window_offsets_kernel, dim3((g.n + 3u) / 4u), dim3(256), 0, stream, g, hashes, off, lb);
-        hipLaunchKernelGGL(ix_tile_count_kernel, dim3(tiles), dim3(IX_NT), 0, stream, g, hashes, (const uint16_t *)lb, cnt);
+        if (!(stages & 8)) hipLaunchKernelGGL(ix_window_offsets_kernel, dim3((g.n + 3u) / 4u), dim3(256), 0, stream, g, hashes, rowmap, off,
+                                              (const uint32_t *)nullptr, lb);
+        hipLaunchKernelGGL(ix_tile_count_kernel, dim3(tiles), dim3(IX_NT), 0, stream, g, hashes, rowmap, (const uint16_t *)lb, cnt);
         hipLaunchKernelGGL(ix_col_scan_kernel, dim3((g.Bp + 255u) / 256u), dim3(256), 0, stream, g, cnt, start);
         hipLaunchKernelGGL(ix_bucket_scan_kernel, dim3(1), dim3(1024), 0, stream, g, start, flags, static_cast<uint32_t *>(big_v));
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ix_tile_partition_kernel, dim3(tiles), dim3(IX_NT), IXL_BYTES, stream, g, hashes, (const uint16_t *)lb, (const uint32_t *)cnt,
+        hipLaunchKernelGGL(ix_tile_partition_kernel, dim3(tiles), dim3(IX_NT), IXL_BYTES, stream, g, hashes, rowmap, (const uint16_t *)lb, (const uint32_t *)cnt,
                            (const uint32_t *)start, (const uint32_t *)flags, pk, pos_img);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
