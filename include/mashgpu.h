@@ -457,6 +457,38 @@ int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, dou
                               uint64_t *n_edges_out);
 int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out,
                             uint64_t *edge_capacity_out);
+/* An earlier clustering of `ref` (n rows) extended by the rows of `qry` (m rows), ON THE DEVICE -- `mash cluster -A`.  `cat` is
+ * the table whose rows are ref's followed by qry's: new row q has index n + q.  Only the pairs that touch a new row are compared:
+ *   new edge   : a pair {n + q, r} that mg_compare_rect_results_host(ctx, ref, qry, 0, m, kmer_size, kmer_space, max_distance,
+ *                max_p_value, ...) returns, or a pair {n + q, n + q'} that mg_compare_tri_results_host(ctx, qry, 0, m, ...) returns
+ *                -- exactly the edges of cat's thresholded triangle that touch a new row;
+ *   n_edges    : the number of new edges.
+ * mg_cluster_extend_host (single linkage): ref_label[n] is a partition of ref's rows in the form mg_cluster_tri_host writes,
+ * ref_label[i] <= i and ref_label[ref_label[i]] == ref_label[i].  label[n + m] holds the connected components of the graph
+ * {i ~ ref_label[i]} + new edges, each labelled by its smallest row; n_clusters is the number of i with label[i] == i.  A new
+ * row may join several old clusters, so the labels of old rows can change.  With ref_label = mg_cluster_tri_host(ref) under the
+ * same filters, label and n_clusters are those of mg_cluster_tri_host(cat), and n_edges(ref) + n_edges == n_edges(cat).
+ * mg_cluster_extend_greedy_host (representatives): ref_rep[n] is in the form mg_cluster_tri_greedy_host writes (the same two
+ * conditions); NULL: every row of ref is a representative.  The old rows never change -- the walk is in index order and had
+ * decided them before any new row -- and goes on over the new ones: row n + q is a representative iff no representative with a
+ * smaller index, old or new, has a new edge to it, else it joins the smallest such.  rep[m] holds the new rows only, its values
+ * are indices of cat; n_clusters counts the representatives among old and new rows together.  With ref_rep =
+ * mg_cluster_tri_greedy_host(ref), rep is rows n .. n + m - 1 of mg_cluster_tri_greedy_host(cat).  Edges from a new row to an old
+ * MEMBER decide nothing, so a caller may pass only the old representatives as `ref`, with ref_rep = NULL.
+ * Nothing here depends on execution order, route or blocking.  m = 0: the input comes back, 0 edges; n = 0: the whole-table call
+ * on qry.  Both filters disabled, sketch sizes that differ, tables without lengths, or a ref_label / ref_rep that breaks one of its
+ * two conditions (checked on the host before anything is queued; the message names the first such row): MG_ERR_INVALID.
+ * n + m > 2^31 - 1: MG_ERR_UNSUPPORTED.  Everything else fails as the whole-table calls do; they share the context options
+ * MASHGPU_CLUSTER_BLOCK_PAIRS and MASHGPU_GREEDY_EDGE_CAP, and mg_cluster_greedy_stats reports the greedy call.
+ * Limits: host output only (no *_dev form), one device, no extension of a minimum spanning forest (`-T`: it would need the old
+ * records), no removal of rows, and nothing checks that the earlier clustering was made under the same filters. */
+int mg_cluster_extend_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_label /* [n] */,
+                           int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                           uint32_t *label_out_host /* [n + m] */, uint64_t *n_clusters_out, uint64_t *n_edges_out);
+int mg_cluster_extend_greedy_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry,
+                                  const uint32_t *ref_rep /* [n] or NULL */, int kmer_size, double kmer_space,
+                                  double max_distance, double max_p_value, uint32_t *rep_out_host /* [m] */,
+                                  uint64_t *n_clusters_out, uint64_t *n_edges_out);
 /* The minimum spanning forest of the same thresholded all-vs-all, found ON THE DEVICE (cluster_forest.hip) -- `mash cluster -T`.
  * The reference has no such command (its user pipes `mash triangle -E -d` through a sort on column 5 and a union-find script, once
  * per threshold they want to look at); the definition stands on those lines:

@@ -33,6 +33,7 @@ EXPORTS = [
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host", "mg_compare_tri_topk_host",
     "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
+    "mg_cluster_extend_host", "mg_cluster_extend_greedy_host",
     "mg_cluster_tri_forest_host", "mg_cluster_forest_stats", "mg_cluster_forest_rounds",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
@@ -363,6 +364,8 @@ def load_library():
     lib.mg_cluster_tri_greedy_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_greedy_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_greedy_stats.argtypes = [vp, vp, vp, vp, vp]
+    lib.mg_cluster_extend_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_extend_greedy_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_forest_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, u64, vp, vp, vp, vp]
     lib.mg_cluster_forest_stats.argtypes = [vp, vp, vp, vp]
     lib.mg_cluster_forest_rounds.argtypes = [vp, vp, vp, u64, vp]
@@ -1027,10 +1030,38 @@ class MashGpu:
         return int(nc.value), int(ne.value)
 
     def cluster_greedy_stats(self):
-        """what this context's last cluster_tri_greedy_* call needed: {rounds, batches, regrows, edge_capacity} (mg_cluster_greedy_stats)"""
+        """what this context's last cluster_tri_greedy_* or cluster_extend_greedy_host call needed: {rounds, batches, regrows, edge_capacity} (mg_cluster_greedy_stats)"""
         v = [C.c_uint64(0) for _ in range(4)]
         self._check(self.lib.mg_cluster_greedy_stats(self.ctx, *[C.byref(x) for x in v]))
         return dict(zip(("rounds", "batches", "regrows", "edge_capacity"), (int(x.value) for x in v)))
+
+    def cluster_extend_host(self, ref, qry, ref_label, k, kmer_space, max_d=-1.0, max_p=-1.0):
+        """an earlier single-linkage clustering of `ref` (ref_label as cluster_tri_host writes it) extended by the rows of `qry`, only
+        the pairs that touch a new row compared: (label u32[ref.rows + qry.rows] over ref's rows then qry's, clusters, new edges)
+        (mg_cluster_extend_host)"""
+        seed = np.ascontiguousarray(ref_label, dtype=np.uint32)
+        if seed.shape != (ref.rows,):
+            raise ValueError("ref_label must have one entry per row of ref")
+        label = np.zeros(ref.rows + qry.rows, dtype=np.uint32)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_extend_host(self.ctx, ref.handle, qry.handle, seed.ctypes.data, k, kmer_space, max_d, max_p,
+                                                    label.ctypes.data, C.byref(nc), C.byref(ne)))
+        return label, int(nc.value), int(ne.value)
+
+    def cluster_extend_greedy_host(self, ref, qry, ref_rep, k, kmer_space, max_d=-1.0, max_p=-1.0):
+        """an earlier greedy clustering of `ref` (ref_rep as cluster_tri_greedy_host writes it; None: every row of ref is a
+        representative) extended by the rows of `qry`: (rep u32[qry.rows] for the new rows only, indices over ref's rows then qry's;
+        clusters among old and new rows; new edges) (mg_cluster_extend_greedy_host)"""
+        seed = None
+        if ref_rep is not None:
+            seed = np.ascontiguousarray(ref_rep, dtype=np.uint32)
+            if seed.shape != (ref.rows,):
+                raise ValueError("ref_rep must have one entry per row of ref")
+        rep = np.zeros(qry.rows, dtype=np.uint32)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_extend_greedy_host(self.ctx, ref.handle, qry.handle, None if seed is None else seed.ctypes.data, k, kmer_space,
+                                                           max_d, max_p, rep.ctypes.data, C.byref(nc), C.byref(ne)))
+        return rep, int(nc.value), int(ne.value)
 
     def cluster_tri_forest_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0, capacity=None, want_label=True):
         """the minimum spanning forest of the pairs compare_tri_results returns for the whole table, found on the device: (records

@@ -35,11 +35,21 @@ __global__ __launch_bounds__(CL_NT) void cl_init_kernel(uint32_t *parent, uint32
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) parent[i] = i;
 }
 
+// An earlier partition as the start: seed[i] <= i (checked by the host), so (I1) holds before the first union, every seeded tree
+// is one of (I2)'s whole trees -- a row under its root, the root its smallest row (I3) -- and nothing above has to know that the
+// links were not made by a CAS of this call.
+__global__ __launch_bounds__(CL_NT) void cl_seed_kernel(uint32_t *parent, const uint32_t *seed, uint32_t n_old, uint32_t n)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) parent[i] = i < n_old ? seed[i] : i;
+}
+
 // Pass A's ballots word by word: word w holds pairs [64 w, 64 w + 64) -- finish_mark_kernel's segment / wave / word layout
 // ((seg * 4 + wave) * 16 + it) is exactly idx / 64 -- and bits behind a.pairs are zero.  A wave loads 64 words at a time (a word
 // that is zero costs that load and nothing else), then takes the words that are not zero one after the other, a lane per bit.
-// The grid is sized by the device (launch_cluster_union), not by the pairs.
-__global__ __launch_bounds__(CL_NT) void cl_union_kernel(FinishArgs a, uint32_t *parent, uint32_t n)
+// The grid is sized by the device (launch_cluster_union), not by the pairs.  sp: the job's pairs in parent[]'s index space -- the
+// bounds are the job's own, before the bases.
+__global__ __launch_bounds__(CL_NT) void cl_union_kernel(FinishArgs a, uint32_t *parent, PairSpace sp)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t words = (a.pairs + 63) / 64;
@@ -55,7 +65,7 @@ __global__ __launch_bounds__(CL_NT) void cl_union_kernel(FinishArgs a, uint32_t 
             if (((m >> lane) & 1) && idx < a.pairs) {
                 uint64_t row, col;
                 pair_rc(a, idx, row, col);
-                if (row < n && col < n) cl_unite(parent, (uint32_t)row, (uint32_t)col);
+                if (row < sp.rows && col < sp.cols) cl_unite(parent, sp.row_base + (uint32_t)row, sp.col_base + (uint32_t)col);
             }
         }
     }
@@ -91,12 +101,24 @@ hipError_t launch_cluster_init(uint32_t *parent, uint32_t n, hipStream_t stream)
     return hipGetLastError();
 }
 
+hipError_t launch_cluster_seed(uint32_t *parent, const uint32_t *seed, uint32_t n_old, uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(cl_seed_kernel, dim3(cl_blocks(n, 2048)), dim3(CL_NT), 0, stream, parent, seed, n_old, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_union(const FinishArgs &a, uint32_t *parent, const PairSpace &sp, hipStream_t stream)
+{
+    if (a.pairs == 0 || sp.rows == 0 || sp.cols == 0) return hipSuccess;
+    // a work-item per mask word up to 2048 workgroups (8 per CU of an MI355X): beyond that the waves stride
+    hipLaunchKernelGGL(cl_union_kernel, dim3(cl_blocks((a.pairs + 63) / 64, 2048)), dim3(CL_NT), 0, stream, a, parent, sp);
+    return hipGetLastError();
+}
+
 hipError_t launch_cluster_union(const FinishArgs &a, uint32_t *parent, uint32_t n, hipStream_t stream)
 {
-    if (a.pairs == 0 || n == 0) return hipSuccess;
-    // a work-item per mask word up to 2048 workgroups (8 per CU of an MI355X): beyond that the waves stride
-    hipLaunchKernelGGL(cl_union_kernel, dim3(cl_blocks((a.pairs + 63) / 64, 2048)), dim3(CL_NT), 0, stream, a, parent, n);
-    return hipGetLastError();
+    return launch_cluster_union(a, parent, PairSpace{n, n, 0u, 0u}, stream);
 }
 
 hipError_t launch_cluster_label(uint32_t *parent, uint32_t n, uint32_t *label, unsigned long long *n_roots, hipStream_t stream)

@@ -32,6 +32,14 @@
 // rep[] is written in LATER launches (cg_rep_init_kernel, cg_assign_kernel): rep[i] = i for a REP, and over the edges
 // atomicMin(&rep[hi], lo) for a MEMBER hi beside a REP lo -- the smallest representative it has an edge to.  A representative
 // with a larger index is never `lo` of an edge of hi, so it never takes hi.
+//
+// Extending an earlier result (cg_seed_kernel): the first n_old rows start as what the earlier walk made them, REP or MEMBER, the
+// rows behind them UNDECIDED, and the rounds run unchanged over all of them.  A seeded word is >= MEMBER before the first round,
+// so by (G1) nobody ever writes it again and by (G2) a seeded REP is as visible as one of an earlier launch.  The walk is in index
+// order and the seeded rows precede every open one: what they are does not depend on any row behind them, so they ARE the walk's
+// decisions on the concatenated table, (G3)'s "a word read as MEMBER is MEMBER" and (G4)'s induction start from them, and the
+// edges from an open row to a seeded MEMBER decide nothing -- which is why a caller may leave the members out of the table.
+// Every edge of such a call has an open row as hi; the assignment writes rep[] for those rows only (`first`).
 #include "cluster_internal.h"
 
 namespace mg {
@@ -44,7 +52,8 @@ __device__ __forceinline__ uint32_t cg_load(uint32_t *p) { return __hip_atomic_l
 // Pass A's ballots as cl_union_kernel reads them: a wave loads 64 words, counts their bits, takes room for all of them with ONE
 // atomicAdd on the cursor, then writes the words that are not zero one after the other, a lane per bit.  An entry whose place
 // is at or behind `cap` is not written (the cursor still counts it: the host reads how much room the block needed).
-__global__ __launch_bounds__(CG_NT) void cg_append_kernel(FinishArgs a, uint32_t n, uint2 *edges, unsigned long long cap,
+// sp: the job's pairs in the index space of state[] (cluster_internal.h), bounds before bases.
+__global__ __launch_bounds__(CG_NT) void cg_append_kernel(FinishArgs a, PairSpace sp, uint2 *edges, unsigned long long cap,
                                                          unsigned long long *cursor, uint32_t *overflow)
 {
     const uint32_t lane = threadIdx.x & 63;
@@ -80,12 +89,22 @@ __global__ __launch_bounds__(CG_NT) void cg_append_kernel(FinishArgs a, uint32_t
                     uint64_t row, col;
                     pair_rc(a, (w0 + j) * 64 + lane, row, col);
                     uint2 e = make_uint2(0u, 0u);              // (a pair outside the table: an entry every reader skips, hi == lo)
-                    if (row < n && col < n) e = make_uint2((uint32_t)(row > col ? row : col), (uint32_t)(row > col ? col : row));
+                    if (row < sp.rows && col < sp.cols) {
+                        const uint32_t r = sp.row_base + (uint32_t)row, c = sp.col_base + (uint32_t)col;
+                        e = make_uint2(r > c ? r : c, r > c ? c : r);
+                    }
                     edges[at] = e;
                 }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(CG_NT) void cg_seed_kernel(uint32_t *state, const uint32_t *seed, uint32_t n_old, uint32_t n)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        state[i] = i >= n_old ? CG_UNDECIDED : (!seed || seed[i] == i) ? CG_REP : CG_MEMBER;
 }
 
 // `go`: the number of rows the round before left open (nullptr: the first round of a batch, the host has looked); a round
@@ -122,7 +141,8 @@ __global__ __launch_bounds__(CG_NT) void cg_round_rows_kernel(uint32_t *state, u
     if (lane == 0 && open) atomicAdd(left, open);
 }
 
-__global__ __launch_bounds__(CG_NT) void cg_rep_init_kernel(const uint32_t *state, uint32_t n, uint32_t *rep, unsigned long long *n_reps)
+// rep[] holds rows first .. n - 1; the representatives are counted over all n rows
+__global__ __launch_bounds__(CG_NT) void cg_rep_init_kernel(const uint32_t *state, uint32_t n, uint32_t first, uint32_t *rep, unsigned long long *n_reps)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -130,18 +150,18 @@ __global__ __launch_bounds__(CG_NT) void cg_rep_init_kernel(const uint32_t *stat
     for (uint32_t i0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {   // (wave-uniform: the ballot)
         const uint32_t i = i0 + lane;
         const bool is_rep = i < n && state[i] == CG_REP;
-        if (i < n) rep[i] = is_rep ? i : 0xFFFFFFFFu;
+        if (i < n && i >= first) rep[i - first] = is_rep ? i : 0xFFFFFFFFu;
         reps += (uint32_t)__popcll(__ballot(is_rep));
     }
     if (lane == 0 && reps) atomicAdd(n_reps, (unsigned long long)reps);
 }
 
-__global__ __launch_bounds__(CG_NT) void cg_assign_kernel(const uint2 *edges, unsigned long long m, const uint32_t *state, uint32_t *rep)
+__global__ __launch_bounds__(CG_NT) void cg_assign_kernel(const uint2 *edges, unsigned long long m, const uint32_t *state, uint32_t first, uint32_t *rep)
 {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += stride) {
         const uint2 x = edges[e];
-        if (x.x > x.y && state[x.y] == CG_REP && state[x.x] == CG_MEMBER) atomicMin(rep + x.x, x.y);
+        if (x.x > x.y && x.x >= first && state[x.y] == CG_REP && state[x.x] == CG_MEMBER) atomicMin(rep + (x.x - first), x.y);
     }
 }
 
@@ -151,13 +171,26 @@ static uint32_t cg_blocks(uint64_t items, uint32_t cap)
     return (uint32_t)(b < 1 ? 1 : b > cap ? cap : b);
 }
 
+hipError_t launch_greedy_append(const FinishArgs &a, const PairSpace &sp, uint2 *edges, uint64_t cap, unsigned long long *cursor,
+                                uint32_t *overflow, hipStream_t stream)
+{
+    if (a.pairs == 0 || sp.rows == 0 || sp.cols == 0) return hipSuccess;
+    // a work-item per mask word up to 2048 workgroups (8 per CU of an MI355X): beyond that the waves stride
+    hipLaunchKernelGGL(cg_append_kernel, dim3(cg_blocks((a.pairs + 63) / 64, 2048)), dim3(CG_NT), 0, stream, a, sp, edges, (unsigned long long)cap,
+                       cursor, overflow);
+    return hipGetLastError();
+}
+
 hipError_t launch_greedy_append(const FinishArgs &a, uint32_t n, uint2 *edges, uint64_t cap, unsigned long long *cursor, uint32_t *overflow,
                                 hipStream_t stream)
 {
-    if (a.pairs == 0 || n == 0) return hipSuccess;
-    // a work-item per mask word up to 2048 workgroups (8 per CU of an MI355X): beyond that the waves stride
-    hipLaunchKernelGGL(cg_append_kernel, dim3(cg_blocks((a.pairs + 63) / 64, 2048)), dim3(CG_NT), 0, stream, a, n, edges, (unsigned long long)cap,
-                       cursor, overflow);
+    return launch_greedy_append(a, PairSpace{n, n, 0u, 0u}, edges, cap, cursor, overflow, stream);
+}
+
+hipError_t launch_greedy_seed(uint32_t *state, const uint32_t *seed, uint32_t n_old, uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(cg_seed_kernel, dim3(cg_blocks(n, 2048)), dim3(CG_NT), 0, stream, state, seed, n_old, n);
     return hipGetLastError();
 }
 
@@ -175,12 +208,12 @@ hipError_t launch_greedy_rounds(const uint2 *edges, uint64_t m, uint32_t *state,
 }
 
 hipError_t launch_greedy_assign(const uint2 *edges, uint64_t m, const uint32_t *state, uint32_t n, uint32_t *rep, unsigned long long *n_reps,
-                                hipStream_t stream)
+                                hipStream_t stream, uint32_t first)
 {
     hipError_t e = hipMemsetAsync(n_reps, 0, sizeof(unsigned long long), stream);
     if (e != hipSuccess || n == 0) return e;
-    hipLaunchKernelGGL(cg_rep_init_kernel, dim3(cg_blocks(n, 2048)), dim3(CG_NT), 0, stream, state, n, rep, n_reps);
-    if (m) hipLaunchKernelGGL(cg_assign_kernel, dim3(cg_blocks(m, 2048)), dim3(CG_NT), 0, stream, edges, (unsigned long long)m, state, rep);
+    hipLaunchKernelGGL(cg_rep_init_kernel, dim3(cg_blocks(n, 2048)), dim3(CG_NT), 0, stream, state, n, first, rep, n_reps);
+    if (m && first < n) hipLaunchKernelGGL(cg_assign_kernel, dim3(cg_blocks(m, 2048)), dim3(CG_NT), 0, stream, edges, (unsigned long long)m, state, first, rep);
     return hipGetLastError();
 }
 

@@ -37,12 +37,23 @@ __device__ __forceinline__ void cl_unite(uint32_t *parent, uint32_t a, uint32_t 
     }
 }
 
+// Where the pairs of a job stand in the index space of a larger table (extending an earlier clustering: ref's rows, then qry's):
+// the job's own {row, col} must be below {rows, cols}, and the pair is {row_base + row, col_base + col} there.  The whole
+// triangle of a table of n rows is {n, n, 0, 0}.
+struct PairSpace { uint32_t rows, cols, row_base, col_base; };
+
 // parent[i] = i for the n rows
 hipError_t launch_cluster_init(uint32_t *parent, uint32_t n, hipStream_t stream);
+// parent[i] = seed[i] for i < n_old (an earlier partition in the form launch_cluster_label writes: seed[i] <= i, which the caller
+// has checked -- (I1) holds from the first union on), parent[i] = i for n_old <= i < n
+hipError_t launch_cluster_seed(uint32_t *parent, const uint32_t *seed, uint32_t n_old, uint32_t n, hipStream_t stream);
 // Every set bit of a.masks (finish_mark_kernel's ballots: bit idx = pair idx of a.counts) joins the clusters of its {row, col}
 // (pair_rc: a.list_rc, or the flat triangle from a.first_row on).  Only a.masks, a.pairs, a.list_rc, a.first_row, a.ncols and
 // a.triangle are read.  Rows and columns must be < n.
 hipError_t launch_cluster_union(const FinishArgs &a, uint32_t *parent, uint32_t n, hipStream_t stream);
+// The same with a base per side: pair {row, col} of the job joins rows sp.row_base + row and sp.col_base + col of parent[], which
+// must hold sp.row_base + sp.rows and sp.col_base + sp.cols rows at least.  A rect job gives row = query, col = reference.
+hipError_t launch_cluster_union(const FinishArgs &a, uint32_t *parent, const PairSpace &sp, hipStream_t stream);
 // label[i] = smallest row of i's cluster, *n_roots = number of clusters.  A launch of its own behind the last union.
 hipError_t launch_cluster_label(uint32_t *parent, uint32_t n, uint32_t *label, unsigned long long *n_roots, hipStream_t stream);
 
@@ -52,13 +63,21 @@ hipError_t launch_cluster_label(uint32_t *parent, uint32_t n, uint32_t *label, u
 // is at or behind `cap` is not written and *overflow is set: the caller regrows, puts *cursor back and appends the job again.
 hipError_t launch_greedy_append(const FinishArgs &a, uint32_t n, uint2 *edges, uint64_t cap, unsigned long long *cursor, uint32_t *overflow,
                                 hipStream_t stream);
+// The same with a base per side (launch_cluster_union): {hi, lo} in the larger table's index space.  Cursor, `cap` and *overflow as above.
+hipError_t launch_greedy_append(const FinishArgs &a, const PairSpace &sp, uint2 *edges, uint64_t cap, unsigned long long *cursor,
+                                uint32_t *overflow, hipStream_t stream);
+// state[i] for i < n_old: REP where seed[i] == i (seed == nullptr: everywhere), else MEMBER -- an earlier result in the form
+// launch_greedy_assign writes; state[i] = UNDECIDED for n_old <= i < n.  The rounds then run over all n rows.
+hipError_t launch_greedy_seed(uint32_t *state, const uint32_t *seed, uint32_t n_old, uint32_t n, hipStream_t stream);
 // `rounds` rounds of the fixpoint over state[n] (all zero before the first round: every row open).  left[r] = rows still open
 // behind round r of this batch (the launcher zeroes left[0 .. rounds)); a round behind one that left none does nothing.  The
 // fixpoint is reached with the first left[r] == 0; at most n rounds are ever needed.
 hipError_t launch_greedy_rounds(const uint2 *edges, uint64_t m, uint32_t *state, uint32_t n, uint32_t *left, uint32_t rounds, hipStream_t stream);
 // Behind the fixpoint: rep[i] = i for a representative, else the smallest representative i has an edge to; *n_reps = representatives.
+// With `first`: rep[] holds rows first .. n - 1 only (rep[i - first], values in the index space of all n rows), from the edges whose
+// hi >= first; *n_reps still counts over all n rows.
 hipError_t launch_greedy_assign(const uint2 *edges, uint64_t m, const uint32_t *state, uint32_t n, uint32_t *rep, unsigned long long *n_reps,
-                                hipStream_t stream);
+                                hipStream_t stream, uint32_t first = 0);
 
 // ---- cluster_forest.hip
 // launch_greedy_append with the pair's counts beside it: {x = larger, y = smaller index, z = numer, w = denom} of a.counts, 16 bytes an

@@ -2389,7 +2389,7 @@ int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kme
 
 // The edge list of one call: grown on demand, the pairs of every block appended behind those of the blocks before it.  E: an edge as
 // Append writes it ({hi, lo} for the greedy rounds, with the pair's counts beside them for the forest)
-template <class E, hipError_t (*Append)(const mg::FinishArgs &, uint32_t, E *, uint64_t, unsigned long long *, uint32_t *, hipStream_t)>
+template <class E, hipError_t (*Append)(const mg::FinishArgs &, const mg::PairSpace &, E *, uint64_t, unsigned long long *, uint32_t *, hipStream_t)>
 struct EdgeList {
     mg_ctx *ctx;
     DevBuf<E> buf;
@@ -2408,14 +2408,14 @@ struct EdgeList {
     }
     // Pass A over f's counts, its marked pairs appended; waits for the block's figures and, if the
     // list was too short for them, regrows it (the pairs of earlier blocks copied over) and appends the block again -- pass A's
-    // ballots are still there
-    int append(mg::FinishArgs f, const PassABufs &b, uint32_t n)
+    // ballots are still there.  sp: where f's pairs stand in the index space of the list (the whole triangle of n rows: {n, n, 0, 0})
+    int append(mg::FinishArgs f, const PassABufs &b, const mg::PairSpace &sp)
     {
         b.bind(f);
         unsigned long long h[3] = {0, 0, 0};
         HIP_TRY(ctx, mg::launch_finish_mark(f, ctl + 1, ctx->stream));
         for (int attempt = 0;; attempt++) {
-            HIP_TRY(ctx, Append(f, n, buf, cap, ctl, reinterpret_cast<uint32_t *>(ctl + 2), ctx->stream));
+            HIP_TRY(ctx, Append(f, sp, buf, cap, ctl, reinterpret_cast<uint32_t *>(ctl + 2), ctx->stream));
             HIP_TRY(ctx, hipMemcpyAsync(h, ctl, 24, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (h[0] <= cap && !h[2]) break;
@@ -2442,6 +2442,48 @@ struct EdgeList {
 };
 using GreedyEdges = EdgeList<uint2, mg::launch_greedy_append>;
 
+// What follows the last append of a greedy call: the fixpoint over E's edges in batches (one wait per batch: the rows each of its
+// rounds left open), the assignment, the copy.  state[] holds n rows; the first n_old of them are seeded from d_seed
+// (launch_greedy_seed; seeded == false: every row open) and rep_out takes the rows from n_old on.
+static int greedy_fixpoint(mg_ctx *ctx, GreedyEdges &E, uint32_t n, uint32_t n_old, bool seeded, const uint32_t *d_seed, uint32_t *rep_out,
+                           bool rep_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    DevBuf<uint32_t> state(ctx), rep(ctx), left(ctx);
+    DevBuf<unsigned long long> d_n(ctx);
+    constexpr uint32_t kBatchMax = 256;
+    if (state.alloc(n) != hipSuccess || left.alloc(kBatchMax) != hipSuccess || d_n.alloc(1) != hipSuccess ||
+        (!rep_on_device && rep.alloc(n - n_old) != hipSuccess))
+        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+    uint32_t *d_rep = rep_on_device ? rep_out : rep.p;
+    if (seeded) HIP_TRY(ctx, mg::launch_greedy_seed(state, d_seed, n_old, n, ctx->stream));
+    else HIP_TRY(ctx, hipMemsetAsync(state, 0, (size_t)n * 4, ctx->stream));
+    std::vector<uint32_t> h(kBatchMax);
+    uint64_t rounds = 0, batches = 0;
+    for (uint32_t batch = 8;; batch = std::min(batch * 2, kBatchMax)) {
+        HIP_TRY(ctx, mg::launch_greedy_rounds(E.buf, E.used, state, n, left, batch, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h.data(), left, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        batches++;
+        uint32_t r = 0;
+        while (r < batch && h[r]) r++;
+        rounds += std::min(r + 1, batch);
+        if (r < batch) break;
+        if (rounds > n) return fail(ctx, MG_ERR_HIP, "cluster: the rounds did not reach their fixpoint");      // (at most n are ever needed)
+    }
+    unsigned long long reps = 0;
+    HIP_TRY(ctx, mg::launch_greedy_assign(E.buf, E.used, state, n, d_rep, d_n, ctx->stream, n_old));
+    HIP_TRY(ctx, hipMemcpyAsync(&reps, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!rep_on_device && n > n_old) HIP_TRY(ctx, hipMemcpyAsync(rep_out, d_rep, (size_t)(n - n_old) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_clusters_out = reps;
+    *n_edges_out = E.n_edges;
+    ctx->greedy_rounds = rounds;
+    ctx->greedy_batches = batches;
+    ctx->greedy_regrows = E.regrows;
+    ctx->greedy_edge_cap = E.cap;
+    return MG_OK;
+}
+
 // The whole triangle of t: cluster_tri's way to the thresholded counts (cut_counts) with GreedyEdges::append as their consumer -- one
 // wait per block --, then the rounds in batches (one wait per batch: the rows each of its rounds left open), then the assignment
 static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
@@ -2459,41 +2501,6 @@ static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, ui
     uint64_t edge_cap = 1ull << 23;                           // 64 MB; the list doubles, or grows to what a block needs, when it is short
     if (const char *o = ctx_opt(ctx, "MASHGPU_GREEDY_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
     GreedyEdges E(ctx);
-    DevBuf<uint32_t> state(ctx), rep(ctx), left(ctx);
-    DevBuf<unsigned long long> d_n(ctx);
-    constexpr uint32_t kBatchMax = 256;
-    // finish: the fixpoint over the edges appended so far, the assignment, the copy
-    auto finish = [&]() -> int {
-        if (state.alloc(n) != hipSuccess || left.alloc(kBatchMax) != hipSuccess || d_n.alloc(1) != hipSuccess || (!rep_on_device && rep.alloc(n) != hipSuccess))
-            return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
-        uint32_t *d_rep = rep_on_device ? rep_out : rep.p;
-        HIP_TRY(ctx, hipMemsetAsync(state, 0, (size_t)n * 4, ctx->stream));
-        std::vector<uint32_t> h(kBatchMax);
-        uint64_t rounds = 0, batches = 0;
-        for (uint32_t batch = 8;; batch = std::min(batch * 2, kBatchMax)) {
-            HIP_TRY(ctx, mg::launch_greedy_rounds(E.buf, E.used, state, n, left, batch, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(h.data(), left, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            batches++;
-            uint32_t r = 0;
-            while (r < batch && h[r]) r++;
-            rounds += std::min(r + 1, batch);
-            if (r < batch) break;
-            if (rounds > n) return fail(ctx, MG_ERR_HIP, "cluster: the rounds did not reach their fixpoint");      // (at most n are ever needed)
-        }
-        unsigned long long reps = 0;
-        HIP_TRY(ctx, mg::launch_greedy_assign(E.buf, E.used, state, n, d_rep, d_n, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(&reps, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (!rep_on_device) HIP_TRY(ctx, hipMemcpyAsync(rep_out, d_rep, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        *n_clusters_out = reps;
-        *n_edges_out = E.n_edges;
-        ctx->greedy_rounds = rounds;
-        ctx->greedy_batches = batches;
-        ctx->greedy_regrows = E.regrows;
-        ctx->greedy_edge_cap = E.cap;
-        return MG_OK;
-    };
     CutBufs bufs(ctx, ctx);
     PassABufs pa(ctx);
     // the list starts no longer than the pairs its route can bring: the candidates, or the whole triangle
@@ -2511,9 +2518,9 @@ static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, ui
                     [&] { pa.release(); },
                     [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
         const int rcb = L ? begin(L->K) : MG_OK;
-        return rcb != MG_OK ? rcb : E.append(f, pa, n);
+        return rcb != MG_OK ? rcb : E.append(f, pa, mg::PairSpace{n, n, 0u, 0u});
     });
-    return rc != MG_OK ? rc : finish();
+    return rc != MG_OK ? rc : greedy_fixpoint(ctx, E, n, 0, false, nullptr, rep_out, rep_on_device, n_clusters_out, n_edges_out);
 }
 
 int mg_cluster_tri_greedy_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
@@ -2542,9 +2549,178 @@ int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches
 }
 
 
+/* ------------------------------------------------- an earlier clustering extended by new rows (include/mashgpu.h: mg_cluster_extend_host) */
+
+// What one of the two jobs of an extending call keeps on the device until the call's last wait: nothing is waited for between the
+// jobs, so the second one takes buffers of its own
+struct ExtendJob {
+    CutBufs bufs;
+    PassABufs pa;
+    explicit ExtendJob(mg_ctx *ctx) : bufs(ctx, ctx), pa(ctx) {}
+};
+
+// The arguments both extending calls share, checked before anything is queued: `seed` is an earlier result over ref's rows
+static int extend_check(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *seed, const Cut &cut, const void *out, uint64_t out_rows,
+                        const uint64_t *n_clusters_out, const uint64_t *n_edges_out, const char *who, const char *seed_name)
+{
+    if (!ref || !qry || !n_clusters_out || !n_edges_out || (!out && out_rows)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
+        return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the tables carry no lengths");
+    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
+    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    if (ref->s != qry->s)
+        return fail(ctx, MG_ERR_INVALID, std::string(who) + ": sketch sizes differ (" + std::to_string(ref->s) + " and " + std::to_string(qry->s) + ")");
+    if (ref->s > 0xFFFFFFFEull) return fail(ctx, MG_ERR_INVALID, "compare: sketch size too large");
+    if (ref->n + qry->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
+    for (uint64_t i = 0; seed && i < ref->n; i++) {
+        if (seed[i] > i)
+            return fail(ctx, MG_ERR_INVALID, std::string(who) + ": " + seed_name + "[" + std::to_string(i) + "] = " + std::to_string(seed[i]) + " is larger than its row");
+        if (seed[seed[i]] != seed[i])
+            return fail(ctx, MG_ERR_INVALID, std::string(who) + ": " + seed_name + "[" + std::to_string(i) + "] = " + std::to_string(seed[i]) +
+                                                 " is not the first row of its cluster (" + seed_name + "[" + std::to_string(seed[i]) + "] = " +
+                                                 std::to_string(seed[seed[i]]) + ")");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return MG_OK;
+}
+
+// The two jobs whose marked pairs are exactly the edges of the concatenated table that touch a new row: the rectangle qry x ref
+// (row = query q -> n + q, col = reference r) and the triangle of qry (both sides n + .).  consume(job, R, space) runs cut_counts.
+template <class Consume>
+static int extend_jobs(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, ExtendJob &rect, ExtendJob &tri, Consume consume)
+{
+    const uint32_t n = (uint32_t)ref->n, m = (uint32_t)qry->n;
+    OutRange R;
+    int rc = out_range(ctx, qry, ref, 0, m, false, &R);
+    if (rc == MG_OK && !R.empty() && R.pairs) rc = consume(rect, R, mg::PairSpace{m, n, n, 0u});
+    if (rc != MG_OK) return rc;
+    rc = out_range(ctx, qry, qry, 0, m, true, &R);
+    if (rc == MG_OK && !R.empty() && R.pairs) rc = consume(tri, R, mg::PairSpace{m, m, n, n});
+    return rc;
+}
+
+// cluster_tri's way, twice over one `parent` seeded with the earlier labels: no wait before the last one
+static int cluster_extend(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_label, const Cut &cut, uint32_t *label_out,
+                          uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    const uint32_t n = (uint32_t)ref->n, total = n + (uint32_t)qry->n;
+    if (!total) return MG_OK;
+    DevBuf<uint32_t> parent(ctx), label(ctx);
+    DevBuf<unsigned long long> d_roots(ctx), d_rect(ctx), d_tri(ctx);          // the clusters; pass A's count per block of either job
+    if (parent.alloc(total) != hipSuccess || label.alloc(total) != hipSuccess || d_roots.alloc(1) != hipSuccess)
+        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+    // the earlier labels travel through `label`, which nobody writes before the label launch
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(label, ref_label, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, mg::launch_cluster_seed(parent, label, n, total, ctx->stream));
+    ExtendJob rect(ctx), tri(ctx);
+    uint64_t nb_rect = 0, nb_tri = 0;
+    int rc = extend_jobs(ctx, ref, qry, rect, tri, [&](ExtendJob &J, const OutRange &R, const mg::PairSpace &sp) -> int {
+        DevBuf<unsigned long long> &d_cnt = &J == &rect ? d_rect : d_tri;
+        uint64_t &nblocks = &J == &rect ? nb_rect : nb_tri;
+        return cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, J.bufs,
+                          [&](uint64_t pairs, uint64_t, uint64_t blocks, bool lists) -> int {
+            if (!J.pa.alloc(pairs, R.s) || d_cnt.alloc(blocks) != hipSuccess) return kAllocFailed;
+            if (lists) return MG_OK;                          // (the flags are cleared once the list's tables stand: below)
+            HIP_TRY(ctx, hipMemsetAsync(J.pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+            return MG_OK;
+        },
+                          [&] { J.pa.release(); },
+                          [&](mg::FinishArgs f, const RowBlock &, const CandLists *L) -> int {
+            if (L) HIP_TRY(ctx, hipMemsetAsync(J.pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+            J.pa.bind(f);
+            HIP_TRY(ctx, mg::launch_finish_mark(f, d_cnt + nblocks++, ctx->stream));
+            HIP_TRY(ctx, mg::launch_cluster_union(f, parent, sp, ctx->stream));
+            return MG_OK;
+        });
+    });
+    if (rc != MG_OK) return rc;
+    // the labels, the roots' number and pass A's counts, behind every union queued so far
+    std::vector<unsigned long long> h(1 + nb_rect + nb_tri);
+    HIP_TRY(ctx, mg::launch_cluster_label(parent, total, label, d_roots, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_roots, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (nb_rect) HIP_TRY(ctx, hipMemcpyAsync(h.data() + 1, d_rect, nb_rect * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (nb_tri) HIP_TRY(ctx, hipMemcpyAsync(h.data() + 1 + nb_rect, d_tri, nb_tri * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(label_out, label, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (both jobs' buffers are released behind this wait)
+    *n_clusters_out = h[0];
+    for (size_t b = 1; b < h.size(); b++) *n_edges_out += h[b];
+    return MG_OK;
+}
+
+// cluster_greedy_tri's way, twice into one edge list (one wait per block, as there), then the fixpoint over the seeded states
+static int cluster_extend_greedy(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_rep, const Cut &cut, uint32_t *rep_out,
+                                 uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    ctx->greedy_rounds = ctx->greedy_batches = ctx->greedy_regrows = ctx->greedy_edge_cap = 0;
+    const uint32_t n = (uint32_t)ref->n, total = n + (uint32_t)qry->n;
+    if (!total) return MG_OK;
+    uint64_t edge_cap = 1ull << 23;                           // (cluster_greedy_tri)
+    if (const char *o = ctx_opt(ctx, "MASHGPU_GREEDY_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));
+    DevBuf<uint32_t> seed(ctx);
+    if (ref_rep && n) {
+        if (seed.alloc(n) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+        HIP_TRY(ctx, hipMemcpyAsync(seed, ref_rep, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    GreedyEdges E(ctx);
+    ExtendJob rect(ctx), tri(ctx);
+    int rc = extend_jobs(ctx, ref, qry, rect, tri, [&](ExtendJob &J, const OutRange &R, const mg::PairSpace &sp) -> int {
+        // the list begins with the first job that brings pairs, no longer than those; the second job's edges make it grow
+        auto begin = [&](uint64_t most_edges) -> int {
+            const int rci = E.buf.p ? MG_OK : E.init(std::min<uint64_t>(edge_cap, most_edges));
+            if (rci != MG_OK) return rci;
+            HIP_TRY(ctx, hipMemsetAsync(J.pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+            return MG_OK;
+        };
+        return cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, J.bufs,
+                          [&](uint64_t pairs, uint64_t, uint64_t, bool lists) -> int {
+            if (!J.pa.alloc(pairs, R.s)) return kAllocFailed;
+            return lists ? MG_OK : begin(R.pairs);
+        },
+                          [&] { J.pa.release(); },
+                          [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
+            const int rcb = L ? begin(L->K) : MG_OK;
+            return rcb != MG_OK ? rcb : E.append(f, J.pa, sp);
+        });
+    });
+    return rc != MG_OK ? rc : greedy_fixpoint(ctx, E, total, n, true, ref_rep ? seed.p : nullptr, rep_out, false, n_clusters_out, n_edges_out);
+}
+
+int mg_cluster_extend_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_label, int kmer_size, double kmer_space,
+                           double max_distance, double max_p_value, uint32_t *label_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    if (ref && ref->n && !ref_label) return fail(ctx, MG_ERR_INVALID, "mg_cluster_extend_host: NULL argument");
+    const int rc = extend_check(ctx, ref, qry, ref_label, cut, label_out_host, ref && qry ? ref->n + qry->n : 1, n_clusters_out, n_edges_out,
+                                "mg_cluster_extend_host", "ref_label");
+    if (rc != MG_OK) return rc;
+    *n_clusters_out = *n_edges_out = 0;
+    return cluster_extend(ctx, ref, qry, ref_label, cut, label_out_host, n_clusters_out, n_edges_out);
+}
+
+int mg_cluster_extend_greedy_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_rep, int kmer_size, double kmer_space,
+                                  double max_distance, double max_p_value, uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    const int rc = extend_check(ctx, ref, qry, ref_rep, cut, rep_out_host, qry ? qry->n : 1, n_clusters_out, n_edges_out,
+                                "mg_cluster_extend_greedy_host", "ref_rep");
+    if (rc != MG_OK) return rc;
+    *n_clusters_out = *n_edges_out = 0;
+    return cluster_extend_greedy(ctx, ref, qry, ref_rep, cut, rep_out_host, n_clusters_out, n_edges_out);
+}
+
+
 /* ------------------------------------------------- the minimum spanning forest of the thresholded triangle (cluster_forest.hip) */
 
-using ForestEdges = EdgeList<uint4, mg::launch_forest_append>;
+static hipError_t forest_append(const mg::FinishArgs &f, const mg::PairSpace &sp, uint4 *edges, uint64_t cap, unsigned long long *cursor,
+                                uint32_t *overflow, hipStream_t stream)
+{
+    return mg::launch_forest_append(f, sp.rows, edges, cap, cursor, overflow, stream);      // (whole triangles only: no bases)
+}
+using ForestEdges = EdgeList<uint4, forest_append>;
 
 // The whole triangle of t: cluster_greedy_tri's way to the edge list (cut_counts with ForestEdges::append as the consumer, one wait per
 // block), then ONE batch -- the rounds, the labels, the sort, the denominators -- and one wait for it, then the distance rows of exactly
@@ -2584,7 +2760,7 @@ static int cluster_forest_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, mg
                     [&] { pa.release(); },
                     [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
         const int rcb = L ? begin(L->K) : MG_OK;
-        return rcb != MG_OK ? rcb : E.append(f, pa, n);
+        return rcb != MG_OK ? rcb : E.append(f, pa, mg::PairSpace{n, n, 0u, 0u});
     });
     if (rc != MG_OK) return rc;
     const uint32_t rounds_queued = mg::forest_rounds(n);

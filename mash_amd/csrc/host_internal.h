@@ -107,7 +107,7 @@ struct mg_ctx {
     // mg_ctx_set_option: tuning and test knobs of this context (name -> value); a knob that is not set here is looked
     // up in the environment under the same name
     std::map<std::string, std::string> options;
-    // mg_cluster_greedy_stats: what the last mg_cluster_tri_greedy_* call of this context needed
+    // mg_cluster_greedy_stats: what the last mg_cluster_tri_greedy_* or mg_cluster_extend_greedy_host call of this context needed
     uint64_t greedy_rounds = 0, greedy_batches = 0, greedy_regrows = 0, greedy_edge_cap = 0;
     // mg_cluster_forest_stats: the same for the last mg_cluster_tri_forest_host call
     uint64_t forest_rounds = 0, forest_regrows = 0, forest_edge_cap = 0;

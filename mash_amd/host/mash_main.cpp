@@ -911,14 +911,15 @@ int report_error(Gpu &gpu)
 }
 
 // dense table upload
-// the same table on EVERY device of the communicator (host -> GPU 0 -> RCCL broadcast)
-mg_dtable *upload_all(Gpu &gpu, const SketchSet &set, uint64_t s, vector<uint64_t> *lengths_out = nullptr, bool by_rows = false)
+// the same table on EVERY device of the communicator (host -> GPU 0 -> RCCL broadcast); rows: only those sketches, in that order
+mg_dtable *upload_all(Gpu &gpu, const SketchSet &set, uint64_t s, vector<uint64_t> *lengths_out = nullptr, bool by_rows = false,
+                      const vector<uint32_t> *rows = nullptr)
 {
-    const uint64_t n = set.refs.size();
+    const uint64_t n = rows ? rows->size() : set.refs.size();
     vector<uint64_t> h(std::max<uint64_t>(n * s, 1), MG_HASH_PAD), len(std::max<uint64_t>(n, 1));
     vector<uint32_t> nh(std::max<uint64_t>(n, 1));
     for (uint64_t i = 0; i < n; i++) {
-        const Ref &r = set.refs[i];
+        const Ref &r = set.refs[rows ? (*rows)[i] : i];
         const uint64_t k = std::min<uint64_t>(r.hashes.size(), s);
         nh[i] = (uint32_t)k;
         len[i] = r.length;
@@ -1769,6 +1770,8 @@ int cmd_triangle(int argc, const char **argv)
 // order, a sketch opens a cluster iff no earlier representative is within the threshold, else it joins the first one that is.
 // Lines and numbering are the same (the label is the representative); the host route runs that walk here.
 // -T: the minimum spanning forest of the same pairs instead (cluster_forest below): edge-list lines, not cluster lines.
+// -A <earlier output>: the clusters of the first L inputs are read from an earlier run's stdout and only the pairs that touch a
+// later input are compared (cluster_extend below; include/mashgpu.h: mg_cluster_extend_host).
 
 // `mash cluster -T`: one `triangle -E` line per edge of the minimum spanning forest of the pairs within -d / -v, best first.  The
 // forest is found on the device and its rows - clusters records come back (mg_cluster_tri_forest_host); MASH_AMD_HOST_FINISH=1 takes
@@ -1814,6 +1817,125 @@ int cluster_forest(TriRun &r)
     return 0;
 }
 
+// `mash cluster -A`: what an earlier run printed for the first L inputs -- per line its ID and its label, the first line that
+// carries its cluster number (the cluster's first member, with -R its representative: a representative precedes its members)
+struct Earlier {
+    vector<string> id;
+    vector<uint32_t> label;
+};
+
+// Reads the lines `<number>\t<size>\t<ID>` (the ID is everything behind the second tab; the size is not used).  false: an ERROR
+// line has been printed.  Nothing here needs a device.
+bool read_earlier(const string &path, Earlier &e)
+{
+    std::ifstream in(path);
+    if (!in) {
+        cerr << "ERROR: Could not open " << path << " for reading." << endl;
+        return false;
+    }
+    std::map<uint64_t, uint32_t> first;      // cluster number -> the first line that carries it
+    string line;
+    while (std::getline(in, line)) {
+        const uint64_t at = e.id.size() + 1;
+        const size_t t1 = line.find('\t'), t2 = t1 == string::npos ? t1 : line.find('\t', t1 + 1);
+        if (t2 == string::npos) {
+            cerr << "ERROR: Line " << at << " of " << path << " is not a line of `mash cluster` (number, size and ID between tabs)." << endl;
+            return false;
+        }
+        uint64_t number = 0;
+        bool good = t1 > 0 && t1 <= 18;
+        for (size_t k = 0; good && k < t1; k++) {
+            good = line[k] >= '0' && line[k] <= '9';
+            number = number * 10 + (uint64_t)(line[k] - '0');
+        }
+        if (!good || number == 0) {
+            cerr << "ERROR: Line " << at << " of " << path << " does not begin with a cluster number (a positive integer)." << endl;
+            return false;
+        }
+        e.label.push_back(first.emplace(number, (uint32_t)e.id.size()).first->second);
+        e.id.push_back(line.substr(t2 + 1));
+    }
+    if (!in.eof()) {                          // (a directory, a device that fails)
+        cerr << "ERROR: Could not read " << path << "." << endl;
+        return false;
+    }
+    return true;
+}
+
+// `mash cluster -A`: lab[i] for all n inputs from the earlier labels of the first L and the edges that touch a later input.  Plain:
+// the first L sketches are one table, the rest a second one (mg_cluster_extend_host).  -R: only the earlier representatives are
+// uploaded beside the new sketches -- edges to earlier members decide nothing -- and the indices are mapped back
+// (mg_cluster_extend_greedy_host with ref_rep == NULL).  MASH_AMD_HOST_FINISH=1 takes the edges of the host calls of `dist -d` and
+// `triangle -E -d` over the same two tables and does the unions, or the walk, here.
+int cluster_extend(Gpu &gpu, const SketchSet &set, const Earlier &old, bool greedy, double d_max, double p_max, StageClock &clk, vector<uint32_t> &lab)
+{
+    const uint64_t n = set.refs.size(), L = old.id.size(), m = n - L;
+    vector<uint32_t> ref_rows, qry_rows;     // the inputs behind the rows of the two tables
+    for (uint64_t i = 0; i < L; i++)
+        if (!greedy || old.label[i] == i) ref_rows.push_back((uint32_t)i);
+    for (uint64_t i = L; i < n; i++) qry_rows.push_back((uint32_t)i);
+    const uint64_t nref = ref_rows.size();
+    auto input_of = [&](uint32_t x) { return x < nref ? ref_rows[x] : (uint32_t)(L + (x - nref)); };      // a row of ref + qry
+    vector<uint64_t> len_ref, len_qry;
+    DTable dr(upload_all(gpu, set, set.p.sketch_size, &len_ref, false, &ref_rows)), dq(upload_all(gpu, set, set.p.sketch_size, &len_qry, false, &qry_rows));
+    mg_table *tr = mg_dtable_local(dr.get(), 0), *tq = mg_dtable_local(dq.get(), 0);      // (several devices selected: the first one's replicas)
+    const double kspace = set.kmer_space();
+    const int kmer = set.p.kmer;
+    clk.lap("upload (earlier, new)");
+    std::copy(old.label.begin(), old.label.end(), lab.begin());
+    if (!host_finish_wanted()) {
+        uint64_t n_clusters = 0, n_edges = 0;
+        if (greedy) {
+            vector<uint32_t> rep(std::max<uint64_t>(m, 1));
+            if (mg_cluster_extend_greedy_host(gpu.ctx, tr, tq, nullptr, kmer, kspace, d_max, p_max, rep.data(), &n_clusters, &n_edges) != MG_OK)
+                return report_error(gpu);
+            for (uint64_t q = 0; q < m; q++) lab[L + q] = input_of(rep[q]);
+            clk.lap("compare+mark+append (new x representatives, new x new)+rounds+assign+copy");
+        } else {
+            if (mg_cluster_extend_host(gpu.ctx, tr, tq, old.label.data(), kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges) != MG_OK)
+                return report_error(gpu);
+            clk.lap("seed+compare+mark+union (new x old, new x new)+label+copy");
+        }
+        return 0;
+    }
+    for (uint64_t i = L; i < n; i++) lab[i] = (uint32_t)i;
+    auto find = [&](uint32_t x) { while (lab[x] != x) { lab[x] = lab[lab[x]]; x = lab[x]; } return x; };
+    vector<vector<uint32_t>> smaller(greedy ? m : 0);          // -R: per new sketch its neighbours with a smaller index, as inputs
+    auto take = [&](uint32_t hi, uint32_t lo) {                 // an edge between inputs, hi a new one
+        if (greedy) { smaller[hi - L].push_back(lo); return; }
+        const uint32_t a = find(hi), b = find(lo);
+        if (a != b) lab[std::max(a, b)] = std::min(a, b);
+    };
+    vector<mg_edge> edges;
+    mg_pair pr;
+    if (nref)
+        for (Blocks b(0, m, kDistFilteredPairs, nref); b.next();) {
+            if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                    return mg_compare_rect_filter_host(gpu.ctx, tr, tq, b.r0, b.r1, kmer, d_max, o, cap, cnt); }))
+                return 1;
+            for (const mg_edge &e : edges)
+                if (finish_edge(e, len_ref[e.col], len_qry[e.row], kmer, kspace, p_max, pr)) take((uint32_t)(L + e.row), ref_rows[e.col]);
+        }
+    for (Blocks b(1, m, kTriFilteredPairs); b.next();) {
+        if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                return mg_compare_tri_filter_host(gpu.ctx, tq, b.r0, b.r1, kmer, d_max, o, cap, cnt); }))
+            return 1;
+        for (const mg_edge &e : edges)
+            if (finish_edge(e, len_qry[e.row], len_qry[e.col], kmer, kspace, p_max, pr))
+                take((uint32_t)(L + std::max(e.row, e.col)), (uint32_t)(L + std::min(e.row, e.col)));
+    }
+    if (greedy) {
+        // the walk goes on in input order: lab[j] == j says that j, decided before i, is a representative
+        for (uint64_t i = L; i < n; i++)
+            for (const uint32_t j : smaller[i - L])
+                if (lab[j] == j && (lab[i] == i || j < lab[i])) lab[i] = j;
+    } else {
+        for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
+    }
+    clk.lap(greedy ? "compare+filter+copy (new x representatives, new x new)+walk" : "compare+filter+copy (new x old, new x new)+union");
+    return 0;
+}
+
 int cmd_cluster(int argc, const char **argv)
 {
     Cmd c;
@@ -1823,6 +1945,7 @@ int cmd_cluster(int argc, const char **argv)
     c.add("comment", Opt::Boolean, "C");
     c.add("representatives", Opt::Boolean, "R");
     c.add("tree", Opt::Boolean, "T");
+    c.add("assign", Opt::File, "A");
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "0.05", 0., 1.);
     c.use_sketch_options();
@@ -1842,13 +1965,23 @@ int cmd_cluster(int argc, const char **argv)
                 "  -T        The minimum spanning forest of those pairs instead of clusters: one `mash triangle -E` line\n"
                 "            per forest edge, best first by shared-hashes as an exact fraction, equal fractions in the\n"
                 "            order of `mash triangle -E`.  The lines down to any fraction are the forest, and give the\n"
-                "            single-linkage clusters, of that stricter threshold.  Not with -R.\n\n";
+                "            single-linkage clusters, of that stricter threshold.  Not with -R.\n"
+                "  -A <file> Extend an earlier clustering: <file> is the output of an earlier `mash cluster` (or `mash\n"
+                "            cluster -R`, then give -R again) over the FIRST inputs, one line each; the IDs must match.  Only\n"
+                "            pairs with one of the later inputs are compared.  All inputs are listed; if <file> was made\n"
+                "            with the same -R, -d and -v, the output is that of the run without -A, and it can be given\n"
+                "            to the next -A.  The mode and thresholds behind <file> are not checked.  Not with -T.\n\n";
         return 0;
     }
     const bool comment = c.o("comment").active, greedy = c.o("representatives").active, forest = c.o("tree").active;
+    const bool extend = c.o("assign").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
     if (forest && greedy) {
         cerr << "ERROR: -" << c.o("tree").id << " and -" << c.o("representatives").id << " cannot be given together." << endl;
+        return 1;
+    }
+    if (forest && extend) {
+        cerr << "ERROR: -" << c.o("tree").id << " and -" << c.o("assign").id << " cannot be given together." << endl;
         return 1;
     }
     if (d_max >= 1.0 && p_max >= 1.0) {
@@ -1858,11 +1991,26 @@ int cmd_cluster(int argc, const char **argv)
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // as `mash triangle` (CommandTriangle.cpp:74-77)
+    Earlier old;
+    if (extend && !read_earlier(c.o("assign").arg, old)) return 1;           // (before a device is opened)
     Gpu gpu;
     SketchSet set;
     init_from_files(gpu, set, input_files(c), p, 1);
     const KmerWarning w = scan_kmer_warning(set);
     const uint64_t n = set.refs.size();
+    if (extend) {
+        if (old.id.size() > n) {
+            cerr << "ERROR: " << c.o("assign").arg << " has " << old.id.size() << " lines, but there are only " << n << " input sequences." << endl;
+            return 1;
+        }
+        for (uint64_t i = 0; i < old.id.size(); i++) {
+            const string &id = comment ? set.refs[i].comment : set.refs[i].name;
+            if (id == old.id[i]) continue;
+            cerr << "ERROR: Line " << (i + 1) << " of " << c.o("assign").arg << " is about \"" << old.id[i] << "\", but input " << (i + 1) << " is \"" << id
+                 << "\": the earlier inputs must come first, in the same order." << endl;
+            return 1;
+        }
+    }
     if (n == 0) return 0;
     if (forest) {
         TriRun run(gpu, set, comment, true, 0, d_max, p_max);
@@ -1871,12 +2019,14 @@ int cmd_cluster(int argc, const char **argv)
         return finish_run(set, w, p.reads);
     }
     vector<uint64_t> lengths;
-    DTable dt(upload_all(gpu, set, set.p.sketch_size, &lengths));
-    mg_table *t = mg_dtable_local(dt.get(), 0);                  // (several devices selected: the first one's replica)
+    DTable dt(extend ? nullptr : upload_all(gpu, set, set.p.sketch_size, &lengths));      // (-A uploads two tables of its own)
+    mg_table *t = extend ? nullptr : mg_dtable_local(dt.get(), 0);                        // (several devices selected: the first one's replica)
     const double kspace = set.kmer_space();
     StageClock clk;
     vector<uint32_t> lab(n);
-    if (!host_finish_wanted()) {
+    if (extend) {
+        if (cluster_extend(gpu, set, old, greedy, d_max, p_max, clk, lab)) return 1;
+    } else if (!host_finish_wanted()) {
         uint64_t n_clusters = 0, n_edges = 0;
         const int rc = greedy ? mg_cluster_tri_greedy_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
                               : mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges);
@@ -2466,7 +2616,7 @@ int main(int argc, const char **argv)
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
         "  dist      Estimate the distance of query sequences to references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n"
-        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
+        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, extend an earlier clustering by new sequences (-A), or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"
