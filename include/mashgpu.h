@@ -457,6 +457,27 @@ int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, dou
                               uint64_t *n_edges_out);
 int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out,
                             uint64_t *edge_capacity_out);
+/* The same representatives, every other row filed under its NEAREST one, ON THE DEVICE (cluster_greedy.hip) -- `mash cluster -B`,
+ * CD-HIT's -g 1.  Edges, representatives, n_clusters and n_edges are those of mg_cluster_tri_greedy_host; only rep[] of a member
+ * differs:
+ *   rep[i]  : i for a representative, else, among ALL representatives j (j < i or j > i) with an edge {i, j}, the one whose edge
+ *             has the larger shared fraction numer/denom -- compared exactly, numer_a * denom_b against numer_b * denom_a in 64-bit
+ *             integers, denom == 0 counting as 0/1 (the order of mg_cluster_tri_forest_host's edges); equal fractions, also under
+ *             different denominators, go to the smaller j.
+ * So every member has an edge to its representative, no two representatives share an edge, the number of clusters is that of
+ * mg_cluster_tri_greedy_host, and a member may have a smaller index than its representative.  rep[] is a function of the edge
+ * set and its counts alone, bit for bit: not of route, blocking, MASHGPU_GREEDY_EDGE_CAP or execution order.
+ * Limits: the whole table only, at most 2^31 - 1 rows; a sketch size of 2^21 or more returns MG_ERR_UNSUPPORTED (the 64-bit weight
+ * key orders denominators below 2^21 exactly); the edges are kept on the device as 16 bytes each while the call runs.  There is
+ * no extending form: a new representative can be nearer to an old member than its old representative, and that pair is not
+ * among the pairs an extending call compares.  Errors, MASHGPU_GREEDY_EDGE_CAP, MASHGPU_CLUSTER_BLOCK_PAIRS, MASHGPU_RESULTS_MATRIX
+ * and mg_cluster_greedy_stats: as for mg_cluster_tri_greedy_host. */
+int mg_cluster_tri_nearest_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                                double max_p_value, uint32_t *rep_out_host /* [rows] */, uint64_t *n_clusters_out,
+                                uint64_t *n_edges_out);
+int mg_cluster_tri_nearest_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                               double max_p_value, uint32_t *rep_out_dev /* [rows] */, uint64_t *n_clusters_out,
+                               uint64_t *n_edges_out);
 /* An earlier clustering of `ref` (n rows) extended by the rows of `qry` (m rows), ON THE DEVICE -- `mash cluster -A`.  `cat` is
  * the table whose rows are ref's followed by qry's: new row q has index n + q.  Only the pairs that touch a new row are compared:
  *   new edge   : a pair {n + q, r} that mg_compare_rect_results_host(ctx, ref, qry, 0, m, kmer_size, kmer_space, max_distance,

@@ -33,6 +33,7 @@ EXPORTS = [
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host", "mg_compare_tri_topk_host",
     "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
+    "mg_cluster_tri_nearest_host", "mg_cluster_tri_nearest_dev",
     "mg_cluster_extend_host", "mg_cluster_extend_greedy_host",
     "mg_cluster_tri_forest_host", "mg_cluster_forest_stats", "mg_cluster_forest_rounds",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
@@ -363,6 +364,8 @@ def load_library():
     lib.mg_cluster_tri_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_greedy_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_greedy_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_tri_nearest_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_tri_nearest_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_greedy_stats.argtypes = [vp, vp, vp, vp, vp]
     lib.mg_cluster_extend_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_extend_greedy_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
@@ -1029,8 +1032,23 @@ class MashGpu:
         self._check(self.lib.mg_cluster_tri_greedy_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, rep_ptr, C.byref(nc), C.byref(ne)))
         return int(nc.value), int(ne.value)
 
+    def cluster_tri_nearest_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0):
+        """cluster_tri_greedy_host's representatives, every other row under its NEAREST one: (rep u32[rows] = the row itself for a
+        representative, else the representative -- of smaller or larger index -- whose edge has the larger numer/denom, exactly,
+        equal fractions to the smaller representative; clusters, edges) (mg_cluster_tri_nearest_host)"""
+        rep = np.zeros(table.rows, dtype=np.uint32)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_nearest_host(self.ctx, table.handle, k, kmer_space, max_d, max_p, rep.ctypes.data, C.byref(nc), C.byref(ne)))
+        return rep, int(nc.value), int(ne.value)
+
+    def cluster_tri_nearest_dev(self, table, k, kmer_space, rep_ptr, max_d=-1.0, max_p=-1.0):
+        """cluster_tri_nearest_host with rep left on the device at rep_ptr (u32[rows]): (clusters, edges)"""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_nearest_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, rep_ptr, C.byref(nc), C.byref(ne)))
+        return int(nc.value), int(ne.value)
+
     def cluster_greedy_stats(self):
-        """what this context's last cluster_tri_greedy_* or cluster_extend_greedy_host call needed: {rounds, batches, regrows, edge_capacity} (mg_cluster_greedy_stats)"""
+        """what this context's last cluster_tri_greedy_*, cluster_tri_nearest_* or cluster_extend_greedy_host call needed: {rounds, batches, regrows, edge_capacity} (mg_cluster_greedy_stats)"""
         v = [C.c_uint64(0) for _ in range(4)]
         self._check(self.lib.mg_cluster_greedy_stats(self.ctx, *[C.byref(x) for x in v]))
         return dict(zip(("rounds", "batches", "regrows", "edge_capacity"), (int(x.value) for x in v)))

@@ -40,7 +40,36 @@
 // decisions on the concatenated table, (G3)'s "a word read as MEMBER is MEMBER" and (G4)'s induction start from them, and the
 // edges from an open row to a seeded MEMBER decide nothing -- which is why a caller may leave the members out of the table.
 // Every edge of such a call has an open row as hi; the assignment writes rep[] for those rows only (`first`).
+//
+// NEAREST representative (launch_nearest_assign, `mash cluster -B`): the same representatives, but a member joins, among ALL the
+// representatives it has an edge to, the one whose edge is best in the order of forest_key.h -- the larger shared fraction by
+// exact cross-multiplication, equal fractions (also under different denominators) to the smaller representative.  The list is
+// cluster_forest.hip's, {hi, lo, numer, denom}; the rounds read its first two words (cg_ends) and are otherwise the same kernel.
+// Behind the fixpoint, each in a launch of its own and over the whole list:
+//   pass 1 (cn_key_kernel): an edge with one end REP and the other MEMBER: atomicMax(&best_key[member], forest_key(numer, denom))
+//   pass 2 (cn_rep_kernel): the same edges whose key == best_key[member]:   atomicMin(&rep[member], representative)
+// Invariants:
+//   (N1) state[] is final (G1) and was written by earlier launches: plain loads, and "an edge between a REP and a MEMBER" means the
+//        same to both passes.  best_key[] is final when pass 2 reads it, for the same reason.
+//   (N2) The representative can be EITHER end of the edge: a member below a representative is `lo` and the representative `hi`
+//        (cg_assign_kernel only ever looks at `lo`).  Both passes go through cn_ends, which names the member and the
+//        representative whichever way round they stand.  An edge between two members decides nothing; no edge joins two
+//        representatives (the walk).
+//   (N3) best_key[] starts at 0, which IS a key: an edge may carry numer == 0 (only the p-value filter on) and be a member's only
+//        edge.  That is harmless because pass 2 looks at edges only, never at "no edge yet": every member has an edge to a
+//        representative (G4), so best_key[member] is the maximum over a set that is not empty, 0 included, and the edge that
+//        carries it passes pass 2's test.  rep[member] starts at ~0 (cg_rep_init_kernel), above every row.
+//   (N4) Padding entries hi == lo (a pair outside the table) are skipped by cn_ends as by every other reader.
+//   (N5) The key is the fraction's order exactly for denominators below FOREST_DENOM_LIMIT (forest_key.h): equal fractions have
+//        equal keys whatever their denominators, 0/0 is 0/1.  The host refuses larger sketch sizes.
+// Why no order of execution can change the result: the only racing accesses are one atomicMax per word in pass 1 and one
+// atomicMin per word in pass 2, each over a fixed set of offers, and max and min do not depend on the order of their operands.
+// The relaxed look in front of the atomic only skips an offer that cannot win: a stale value is an older one, smaller for
+// best_key, larger for rep (cluster_forest.hip, F2).  So rep[] is a function of the edge set and its counts alone.
+// Contention is low (a member has a handful of representatives within the threshold, spread over the list), so the offers are
+// per lane: no wave-level reduction.
 #include "cluster_internal.h"
+#include "forest_key.h"
 
 namespace mg {
 
@@ -109,12 +138,17 @@ __global__ __launch_bounds__(CG_NT) void cg_seed_kernel(uint32_t *state, const u
 
 // `go`: the number of rows the round before left open (nullptr: the first round of a batch, the host has looked); a round
 // queued behind the fixpoint does nothing
-__global__ __launch_bounds__(CG_NT) void cg_round_edges_kernel(const uint2 *edges, unsigned long long m, uint32_t *state, const uint32_t *go)
+// E: uint2 {hi, lo}, or uint4 {hi, lo, numer, denom} of which the rounds read the first two words
+__device__ __forceinline__ uint2 cg_ends(const uint2 *edges, uint64_t e) { return edges[e]; }
+__device__ __forceinline__ uint2 cg_ends(const uint4 *edges, uint64_t e) { return *reinterpret_cast<const uint2 *>(edges + e); }
+
+template <class E>
+__global__ __launch_bounds__(CG_NT) void cg_round_edges_kernel(const E *edges, unsigned long long m, uint32_t *state, const uint32_t *go)
 {
     if (go && *go == 0) return;                                // (written by an earlier launch; uniform over the grid)
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += stride) {
-        const uint2 x = edges[e];
+        const uint2 x = cg_ends(edges, e);
         if (x.x <= x.y) continue;
         const uint32_t sh = cg_load(state + x.x);
         if (sh >= CG_MEMBER) continue;
@@ -165,6 +199,45 @@ __global__ __launch_bounds__(CG_NT) void cg_assign_kernel(const uint2 *edges, un
     }
 }
 
+// ---- the nearest representative (N1 .. N5 at the head of the file)
+
+__device__ __forceinline__ unsigned long long cn_load(unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the edge joins a REP and a MEMBER, whichever way round: `member` and `rep` are its ends
+__device__ __forceinline__ bool cn_ends(const uint4 &x, const uint32_t *state, uint32_t &member, uint32_t &rep)
+{
+    if (x.x <= x.y) return false;                              // (padding)
+    const uint32_t sh = state[x.x], sl = state[x.y];
+    if (sh == CG_MEMBER && sl == CG_REP) { member = x.x; rep = x.y; return true; }
+    if (sh == CG_REP && sl == CG_MEMBER) { member = x.y; rep = x.x; return true; }
+    return false;
+}
+
+__global__ __launch_bounds__(CG_NT) void cn_key_kernel(const uint4 *edges, unsigned long long m, const uint32_t *state, unsigned long long *best_key)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += stride) {
+        const uint4 x = edges[e];
+        uint32_t member, rep;
+        if (!cn_ends(x, state, member, rep)) continue;
+        const unsigned long long key = forest_key(x.z, x.w);
+        if (key > cn_load(best_key + member)) atomicMax(best_key + member, key);
+    }
+}
+
+__global__ __launch_bounds__(CG_NT) void cn_rep_kernel(const uint4 *edges, unsigned long long m, const uint32_t *state, const unsigned long long *best_key,
+                                                      uint32_t *rep_of)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += stride) {
+        const uint4 x = edges[e];
+        uint32_t member, rep;
+        if (!cn_ends(x, state, member, rep)) continue;
+        if (forest_key(x.z, x.w) != best_key[member]) continue;                   // (best_key: pass 1's, an earlier launch)
+        if (rep < cg_load(rep_of + member)) atomicMin(rep_of + member, rep);
+    }
+}
+
 static uint32_t cg_blocks(uint64_t items, uint32_t cap)
 {
     const uint64_t b = (items + CG_NT - 1) / CG_NT;
@@ -194,17 +267,28 @@ hipError_t launch_greedy_seed(uint32_t *state, const uint32_t *seed, uint32_t n_
     return hipGetLastError();
 }
 
-hipError_t launch_greedy_rounds(const uint2 *edges, uint64_t m, uint32_t *state, uint32_t n, uint32_t *left, uint32_t rounds, hipStream_t stream)
+template <class E>
+static hipError_t cg_rounds(const E *edges, uint64_t m, uint32_t *state, uint32_t n, uint32_t *left, uint32_t rounds, hipStream_t stream)
 {
     if (n == 0 || rounds == 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(left, 0, (size_t)rounds * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     for (uint32_t r = 0; r < rounds; r++) {
         const uint32_t *go = r ? left + (r - 1) : nullptr;
-        if (m) hipLaunchKernelGGL(cg_round_edges_kernel, dim3(cg_blocks(m, 2048)), dim3(CG_NT), 0, stream, edges, (unsigned long long)m, state, go);
+        if (m) hipLaunchKernelGGL(cg_round_edges_kernel<E>, dim3(cg_blocks(m, 2048)), dim3(CG_NT), 0, stream, edges, (unsigned long long)m, state, go);
         hipLaunchKernelGGL(cg_round_rows_kernel, dim3(cg_blocks(n, 2048)), dim3(CG_NT), 0, stream, state, n, go, left + r);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_greedy_rounds(const uint2 *edges, uint64_t m, uint32_t *state, uint32_t n, uint32_t *left, uint32_t rounds, hipStream_t stream)
+{
+    return cg_rounds(edges, m, state, n, left, rounds, stream);
+}
+
+hipError_t launch_greedy_rounds(const uint4 *edges, uint64_t m, uint32_t *state, uint32_t n, uint32_t *left, uint32_t rounds, hipStream_t stream)
+{
+    return cg_rounds(edges, m, state, n, left, rounds, stream);
 }
 
 hipError_t launch_greedy_assign(const uint2 *edges, uint64_t m, const uint32_t *state, uint32_t n, uint32_t *rep, unsigned long long *n_reps,
@@ -214,6 +298,20 @@ hipError_t launch_greedy_assign(const uint2 *edges, uint64_t m, const uint32_t *
     if (e != hipSuccess || n == 0) return e;
     hipLaunchKernelGGL(cg_rep_init_kernel, dim3(cg_blocks(n, 2048)), dim3(CG_NT), 0, stream, state, n, first, rep, n_reps);
     if (m && first < n) hipLaunchKernelGGL(cg_assign_kernel, dim3(cg_blocks(m, 2048)), dim3(CG_NT), 0, stream, edges, (unsigned long long)m, state, first, rep);
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest_assign(const uint4 *edges, uint64_t m, const uint32_t *state, uint32_t n, unsigned long long *best_key, uint32_t *rep,
+                                 unsigned long long *n_reps, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(n_reps, 0, sizeof(unsigned long long), stream);
+    if (e != hipSuccess || n == 0) return e;
+    if ((e = hipMemsetAsync(best_key, 0, (size_t)n * sizeof(unsigned long long), stream)) != hipSuccess) return e;      // (N3)
+    hipLaunchKernelGGL(cg_rep_init_kernel, dim3(cg_blocks(n, 2048)), dim3(CG_NT), 0, stream, state, n, 0u, rep, n_reps);
+    if (m) {
+        hipLaunchKernelGGL(cn_key_kernel, dim3(cg_blocks(m, 2048)), dim3(CG_NT), 0, stream, edges, (unsigned long long)m, state, best_key);
+        hipLaunchKernelGGL(cn_rep_kernel, dim3(cg_blocks(m, 2048)), dim3(CG_NT), 0, stream, edges, (unsigned long long)m, state, best_key, rep);
+    }
     return hipGetLastError();
 }
 

@@ -78,6 +78,13 @@ hipError_t launch_greedy_rounds(const uint2 *edges, uint64_t m, uint32_t *state,
 // hi >= first; *n_reps still counts over all n rows.
 hipError_t launch_greedy_assign(const uint2 *edges, uint64_t m, const uint32_t *state, uint32_t n, uint32_t *rep, unsigned long long *n_reps,
                                 hipStream_t stream, uint32_t first = 0);
+// The rounds over a list with counts (launch_forest_append's {hi, lo, numer, denom}): the same fixpoint, the counts are not read.
+hipError_t launch_greedy_rounds(const uint4 *edges, uint64_t m, uint32_t *state, uint32_t n, uint32_t *left, uint32_t rounds, hipStream_t stream);
+// Behind the fixpoint over that list: rep[i] = i for a representative, else the representative -- of smaller or larger index -- whose
+// edge to i is best in the order of forest_key.h (the larger numer/denom exactly; equal fractions: the smaller representative);
+// *n_reps = representatives.  best_key[n] is scratch (cleared here).  Denominators must be below FOREST_DENOM_LIMIT.
+hipError_t launch_nearest_assign(const uint4 *edges, uint64_t m, const uint32_t *state, uint32_t n, unsigned long long *best_key, uint32_t *rep,
+                                 unsigned long long *n_reps, hipStream_t stream);
 
 // ---- cluster_forest.hip
 // launch_greedy_append with the pair's counts beside it: {x = larger, y = smaller index, z = numer, w = denom} of a.counts, 16 bytes an

@@ -7,6 +7,7 @@ namespace mg { void index_dump_clocks(); }
 #include "sort_bits.h"
 #include "topk_internal.h"
 #include "knn_internal.h"
+#include <type_traits>
 
 /* ------------------------------------------------------------------ comparing */
 
@@ -2360,16 +2361,18 @@ static int cluster_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t 
 
 static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
                               uint64_t *n_edges_out);
+static int cluster_nearest_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
+                               uint64_t *n_edges_out);
 
 static int cluster_entry(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out,
-                         uint64_t *n_edges_out, const char *who, bool greedy = false)
+                         uint64_t *n_edges_out, const char *who, bool greedy = false, bool nearest = false)
 {
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!t || !n_clusters_out || !n_edges_out || (!label_out && t->n)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
     if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
     if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
-    return (greedy ? cluster_greedy_tri : cluster_tri)(ctx, t, cut, label_out, label_on_device, n_clusters_out, n_edges_out);
+    return (nearest ? cluster_nearest_tri : greedy ? cluster_greedy_tri : cluster_tri)(ctx, t, cut, label_out, label_on_device, n_clusters_out, n_edges_out);
 }
 
 int mg_cluster_tri_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
@@ -2442,17 +2445,29 @@ struct EdgeList {
 };
 using GreedyEdges = EdgeList<uint2, mg::launch_greedy_append>;
 
+// the list with counts (cluster_forest.hip's append): the forest's, and the greedy rounds' when members join their NEAREST representative
+static hipError_t forest_append(const mg::FinishArgs &f, const mg::PairSpace &sp, uint4 *edges, uint64_t cap, unsigned long long *cursor,
+                                uint32_t *overflow, hipStream_t stream)
+{
+    return mg::launch_forest_append(f, sp.rows, edges, cap, cursor, overflow, stream);      // (whole triangles only: no bases)
+}
+using ForestEdges = EdgeList<uint4, forest_append>;
+
 // What follows the last append of a greedy call: the fixpoint over E's edges in batches (one wait per batch: the rows each of its
 // rounds left open), the assignment, the copy.  state[] holds n rows; the first n_old of them are seeded from d_seed
 // (launch_greedy_seed; seeded == false: every row open) and rep_out takes the rows from n_old on.
-static int greedy_fixpoint(mg_ctx *ctx, GreedyEdges &E, uint32_t n, uint32_t n_old, bool seeded, const uint32_t *d_seed, uint32_t *rep_out,
+// Edges == ForestEdges: the list carries the pairs' counts and the assignment is the nearest representative's (launch_nearest_assign:
+// two more launches in the last batch, no further wait); whole tables only (n_old == 0).
+template <class Edges>
+static int greedy_fixpoint(mg_ctx *ctx, Edges &E, uint32_t n, uint32_t n_old, bool seeded, const uint32_t *d_seed, uint32_t *rep_out,
                            bool rep_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
 {
+    constexpr bool kNearest = std::is_same<Edges, ForestEdges>::value;
     DevBuf<uint32_t> state(ctx), rep(ctx), left(ctx);
-    DevBuf<unsigned long long> d_n(ctx);
+    DevBuf<unsigned long long> d_n(ctx), best_key(ctx);
     constexpr uint32_t kBatchMax = 256;
     if (state.alloc(n) != hipSuccess || left.alloc(kBatchMax) != hipSuccess || d_n.alloc(1) != hipSuccess ||
-        (!rep_on_device && rep.alloc(n - n_old) != hipSuccess))
+        (!rep_on_device && rep.alloc(n - n_old) != hipSuccess) || (kNearest && best_key.alloc(n) != hipSuccess))
         return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
     uint32_t *d_rep = rep_on_device ? rep_out : rep.p;
     if (seeded) HIP_TRY(ctx, mg::launch_greedy_seed(state, d_seed, n_old, n, ctx->stream));
@@ -2471,7 +2486,8 @@ static int greedy_fixpoint(mg_ctx *ctx, GreedyEdges &E, uint32_t n, uint32_t n_o
         if (rounds > n) return fail(ctx, MG_ERR_HIP, "cluster: the rounds did not reach their fixpoint");      // (at most n are ever needed)
     }
     unsigned long long reps = 0;
-    HIP_TRY(ctx, mg::launch_greedy_assign(E.buf, E.used, state, n, d_rep, d_n, ctx->stream, n_old));
+    if constexpr (kNearest) HIP_TRY(ctx, mg::launch_nearest_assign(E.buf, E.used, state, n, best_key, d_rep, d_n, ctx->stream));
+    else HIP_TRY(ctx, mg::launch_greedy_assign(E.buf, E.used, state, n, d_rep, d_n, ctx->stream, n_old));
     HIP_TRY(ctx, hipMemcpyAsync(&reps, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
     if (!rep_on_device && n > n_old) HIP_TRY(ctx, hipMemcpyAsync(rep_out, d_rep, (size_t)(n - n_old) * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2485,9 +2501,12 @@ static int greedy_fixpoint(mg_ctx *ctx, GreedyEdges &E, uint32_t n, uint32_t n_o
 }
 
 // The whole triangle of t: cluster_tri's way to the thresholded counts (cut_counts) with GreedyEdges::append as their consumer -- one
-// wait per block --, then the rounds in batches (one wait per batch: the rows each of its rounds left open), then the assignment
-static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
-                              uint64_t *n_edges_out)
+// wait per block --, then the rounds in batches (one wait per batch: the rows each of its rounds left open), then the assignment.
+// Edges: GreedyEdges (the first representative), or ForestEdges (the nearest one: 16 bytes an edge instead of 8, nothing else differs
+// before the assignment)
+template <class Edges>
+static int cluster_greedy_tri_of(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
+                                 uint64_t *n_edges_out)
 {
     *n_clusters_out = 0;
     *n_edges_out = 0;
@@ -2497,10 +2516,12 @@ static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, ui
     if (rc != MG_OK || R.empty()) return rc;
     if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
     if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
+    if (std::is_same<Edges, ForestEdges>::value && R.s >= mg::FOREST_DENOM_LIMIT)
+        return fail(ctx, MG_ERR_UNSUPPORTED, "cluster nearest: sketch size 2^21 or more (the weight key orders denominators below 2^21 exactly)");
     const uint32_t n = (uint32_t)t->n;
-    uint64_t edge_cap = 1ull << 23;                           // 64 MB; the list doubles, or grows to what a block needs, when it is short
+    uint64_t edge_cap = 1ull << 23;                           // 64 MB (128 with counts); the list doubles, or grows to what a block needs, when it is short
     if (const char *o = ctx_opt(ctx, "MASHGPU_GREEDY_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
-    GreedyEdges E(ctx);
+    Edges E(ctx);
     CutBufs bufs(ctx, ctx);
     PassABufs pa(ctx);
     // the list starts no longer than the pairs its route can bring: the candidates, or the whole triangle
@@ -2523,6 +2544,18 @@ static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, ui
     return rc != MG_OK ? rc : greedy_fixpoint(ctx, E, n, 0, false, nullptr, rep_out, rep_on_device, n_clusters_out, n_edges_out);
 }
 
+static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
+                              uint64_t *n_edges_out)
+{
+    return cluster_greedy_tri_of<GreedyEdges>(ctx, t, cut, rep_out, rep_on_device, n_clusters_out, n_edges_out);
+}
+
+static int cluster_nearest_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
+                               uint64_t *n_edges_out)
+{
+    return cluster_greedy_tri_of<ForestEdges>(ctx, t, cut, rep_out, rep_on_device, n_clusters_out, n_edges_out);
+}
+
 int mg_cluster_tri_greedy_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
                                uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
 {
@@ -2535,6 +2568,20 @@ int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, dou
 {
     return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_dev, true, n_clusters_out, n_edges_out,
                          "mg_cluster_tri_greedy_dev", true);
+}
+
+int mg_cluster_tri_nearest_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                                uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_host, false, n_clusters_out, n_edges_out,
+                         "mg_cluster_tri_nearest_host", true, true);
+}
+
+int mg_cluster_tri_nearest_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                               uint32_t *rep_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_dev, true, n_clusters_out, n_edges_out,
+                         "mg_cluster_tri_nearest_dev", true, true);
 }
 
 int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out, uint64_t *edge_capacity_out)
@@ -2714,13 +2761,6 @@ int mg_cluster_extend_greedy_host(mg_ctx *ctx, const mg_table *ref, const mg_tab
 
 
 /* ------------------------------------------------- the minimum spanning forest of the thresholded triangle (cluster_forest.hip) */
-
-static hipError_t forest_append(const mg::FinishArgs &f, const mg::PairSpace &sp, uint4 *edges, uint64_t cap, unsigned long long *cursor,
-                                uint32_t *overflow, hipStream_t stream)
-{
-    return mg::launch_forest_append(f, sp.rows, edges, cap, cursor, overflow, stream);      // (whole triangles only: no bases)
-}
-using ForestEdges = EdgeList<uint4, forest_append>;
 
 // The whole triangle of t: cluster_greedy_tri's way to the edge list (cut_counts with ForestEdges::append as the consumer, one wait per
 // block), then ONE batch -- the rounds, the labels, the sort, the denominators -- and one wait for it, then the distance rows of exactly

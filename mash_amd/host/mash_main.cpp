@@ -1769,6 +1769,8 @@ int cmd_triangle(int argc, const char **argv)
 // -R: greedy representative clusters of the same pairs instead (mg_cluster_tri_greedy_host): walking the sketches in input
 // order, a sketch opens a cluster iff no earlier representative is within the threshold, else it joins the first one that is.
 // Lines and numbering are the same (the label is the representative); the host route runs that walk here.
+// -B: -R's representatives, every other sketch under its NEAREST one (mg_cluster_tri_nearest_host): the representative, earlier or
+// later in the input, with which it shares the larger fraction of hashes, exactly (mg::forest_before); a fourth field names it.
 // -T: the minimum spanning forest of the same pairs instead (cluster_forest below): edge-list lines, not cluster lines.
 // -A <earlier output>: the clusters of the first L inputs are read from an earlier run's stdout and only the pairs that touch a
 // later input are compared (cluster_extend below; include/mashgpu.h: mg_cluster_extend_host).
@@ -1944,6 +1946,7 @@ int cmd_cluster(int argc, const char **argv)
     c.add("list", Opt::Boolean, "l");
     c.add("comment", Opt::Boolean, "C");
     c.add("representatives", Opt::Boolean, "R");
+    c.add("best", Opt::Boolean, "B");
     c.add("tree", Opt::Boolean, "T");
     c.add("assign", Opt::File, "A");
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
@@ -1962,6 +1965,13 @@ int cmd_cluster(int argc, const char **argv)
                 "            becomes a representative if no earlier representative has an edge to it, and joins the\n"
                 "            first representative that has one otherwise.  No two representatives share an edge and\n"
                 "            every member has an edge to its representative.\n"
+                "  -B        The representatives of -R (implied), but every other sketch joins its nearest representative:\n"
+                "            among all representatives it has an edge to, earlier or later in the input, the one with the\n"
+                "            larger shared-hashes as an exact fraction; equal fractions go to the earlier representative.\n"
+                "            Output gets a fourth field, [cluster-number, cluster-size, ID, representative-ID]: a member\n"
+                "            may precede its representative.  Clusters are numbered by their representatives' order.  Not\n"
+                "            with -T.  Not with -A: a new representative can be nearer to an earlier member than the one it\n"
+                "            was filed under, and that pair is not among those -A compares.\n"
                 "  -T        The minimum spanning forest of those pairs instead of clusters: one `mash triangle -E` line\n"
                 "            per forest edge, best first by shared-hashes as an exact fraction, equal fractions in the\n"
                 "            order of `mash triangle -E`.  The lines down to any fraction are the forest, and give the\n"
@@ -1973,9 +1983,17 @@ int cmd_cluster(int argc, const char **argv)
                 "            to the next -A.  The mode and thresholds behind <file> are not checked.  Not with -T.\n\n";
         return 0;
     }
-    const bool comment = c.o("comment").active, greedy = c.o("representatives").active, forest = c.o("tree").active;
-    const bool extend = c.o("assign").active;
+    const bool comment = c.o("comment").active, nearest = c.o("best").active, greedy = c.o("representatives").active || nearest;
+    const bool forest = c.o("tree").active, extend = c.o("assign").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
+    if (nearest && forest) {
+        cerr << "ERROR: -" << c.o("best").id << " and -" << c.o("tree").id << " cannot be given together." << endl;
+        return 1;
+    }
+    if (nearest && extend) {
+        cerr << "ERROR: -" << c.o("best").id << " and -" << c.o("assign").id << " cannot be given together (a new representative can be nearer to an earlier member)." << endl;
+        return 1;
+    }
     if (forest && greedy) {
         cerr << "ERROR: -" << c.o("tree").id << " and -" << c.o("representatives").id << " cannot be given together." << endl;
         return 1;
@@ -2028,15 +2046,17 @@ int cmd_cluster(int argc, const char **argv)
         if (cluster_extend(gpu, set, old, greedy, d_max, p_max, clk, lab)) return 1;
     } else if (!host_finish_wanted()) {
         uint64_t n_clusters = 0, n_edges = 0;
-        const int rc = greedy ? mg_cluster_tri_greedy_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
-                              : mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges);
+        const int rc = nearest  ? mg_cluster_tri_nearest_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
+                       : greedy ? mg_cluster_tri_greedy_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
+                                : mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges);
         if (rc != MG_OK) return report_error(gpu);
-        clk.lap(greedy ? "compare+mark+append+rounds+assign+copy" : "compare+mark+union+label+copy");
+        clk.lap(nearest ? "compare+mark+append+rounds+nearest+copy" : greedy ? "compare+mark+append+rounds+assign+copy" : "compare+mark+union+label+copy");
     } else {
         for (uint64_t i = 0; i < n; i++) lab[i] = (uint32_t)i;
         auto find = [&](uint32_t x) { while (lab[x] != x) { lab[x] = lab[lab[x]]; x = lab[x]; } return x; };
         vector<mg_edge> edges;
         vector<vector<uint32_t>> smaller(greedy ? n : 0);      // -R: per sketch its neighbours with a smaller index
+        vector<mg_edge> kept;                                  // -B: every edge with its counts
         for (Blocks b(1, n, kTriFilteredPairs); b.next();) {
             if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
                     return mg_compare_tri_filter_host(gpu.ctx, t, b.r0, b.r1, set.p.kmer, d_max, o, cap, cnt); }))
@@ -2046,6 +2066,7 @@ int cmd_cluster(int argc, const char **argv)
                 if (!finish_edge(e, lengths[e.row], lengths[e.col], set.p.kmer, kspace, p_max, pr)) continue;
                 if (greedy) {
                     smaller[std::max(e.row, e.col)].push_back(std::min(e.row, e.col));
+                    if (nearest) kept.push_back(e);
                     continue;
                 }
                 const uint32_t a = find(e.row), b2 = find(e.col);
@@ -2057,10 +2078,26 @@ int cmd_cluster(int argc, const char **argv)
             for (uint64_t i = 0; i < n; i++)
                 for (const uint32_t j : smaller[i])
                     if (lab[j] == j && (lab[i] == i || j < lab[i])) lab[i] = j;
+            if (nearest) {
+                // the walk has named the representatives; a member now takes the best of ALL its edges to one, either end of the
+                // pair: mg::forest_before with the representative in the row pair's place (equal fractions: the smaller one)
+                vector<uint8_t> is_rep(n);
+                vector<const mg_edge *> best(n, nullptr);
+                for (uint64_t i = 0; i < n; i++) is_rep[i] = lab[i] == i;
+                for (const mg_edge &e : kept) {
+                    if (is_rep[e.row] == is_rep[e.col]) continue;
+                    const uint32_t member = is_rep[e.row] ? e.col : e.row, r = is_rep[e.row] ? e.row : e.col;
+                    const mg_edge *b2 = best[member];
+                    if (!b2 || mg::forest_before(e.numer, e.denom, r, b2->numer, b2->denom, lab[member])) {
+                        best[member] = &e;
+                        lab[member] = r;
+                    }
+                }
+            }
         } else {
             for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
         }
-        clk.lap(greedy ? "compare+filter+copy+walk" : "compare+filter+copy+union");
+        clk.lap(nearest ? "compare+filter+copy+walk+nearest" : greedy ? "compare+filter+copy+walk" : "compare+filter+copy+union");
     }
     // label = the cluster's first member: numbers in order of first appearance are numbers by ascending label
     vector<uint32_t> number(n, 0), size(n, 0);
@@ -2072,6 +2109,7 @@ int cmd_cluster(int argc, const char **argv)
     FastOut out;
     for (uint64_t i = 0; i < n; i++) {
         out << number[lab[i]] << '\t' << size[lab[i]] << '\t' << (comment ? set.refs[i].comment : set.refs[i].name);
+        if (nearest) out << '\t' << (comment ? set.refs[lab[i]].comment : set.refs[lab[i]].name);
         out.eol();
     }
     clk.lap("format+write");
@@ -2616,7 +2654,7 @@ int main(int argc, const char **argv)
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
         "  dist      Estimate the distance of query sequences to references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n"
-        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, extend an earlier clustering by new sequences (-A), or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
+        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), extend an earlier clustering by new sequences (-A), or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"
