@@ -140,6 +140,8 @@ struct SparseIndexBuild {
     mg::IxPlan early_plan;                                  // the tiles' plan, if it could be made before the clustered copy ...
     DevBuf<unsigned char> d_lb;                             // ... whose kernel then left the rows' window offsets here
     bool lb_made = false;
+    DevBuf<unsigned char> d_tcnt;                           // the blocks' bucket counts (the plan's cnt scratch) ...
+    bool cnt_made = false;                                  // ... made with the window offsets, from the same read of the table (index_offsets_counts)
     bool cnt_stale = false;                                 // d_cnt still holds the counts in the table's order
 
     // ---- find_copies
@@ -170,12 +172,28 @@ struct SparseIndexBuild {
 
     SparseIndexBuild(mg_ctx *c, const mg_table *tab, uint32_t sketch_size, bool clustered_variant, mg_table::Sparse *index, uint32_t split_row)
         : ctx(c), t(tab), s(sketch_size), clustered(clustered_variant), split(split_row), sp(index), n(tab->n), dc_cls(c), d_link(c), dc_last(c), d_dig(c), d_dig_sorted(c),
-          k_a(c), k_b(c), d_cnt(c), d_rows_sorted(c), d_flags(c), d_nflag(c), r_a(c), r_b(c), l_a(c), l_b(c), d_inv(c), d_lab(c), d_tmp_dup(c), d_tmp_cl(c), d_lb(c),
+          k_a(c), k_b(c), d_cnt(c), d_rows_sorted(c), d_flags(c), d_nflag(c), r_a(c), r_b(c), l_a(c), l_b(c), d_inv(c), d_lab(c), d_tmp_dup(c), d_tmp_cl(c), d_lb(c), d_tcnt(c),
           d_groups(c), d_grp_of(c), d_lead_rows(c), lead(c), temp(c), gs_of(c), key64_a(c), key64_b(c), d_stat(c), d_slots(c)
     {}
 
     int unusable(const char *why) { sp->usable = false; sp->why = why; stop = true; return MG_OK; }
 
+
+    // Whether the early call makes the blocks' bucket counts with the window offsets (index_offsets_counts): where the counters
+    // fit a workgroup's LDS, unless MASHGPU_IX_COUNTS=tiles asks for K0 + K1 (=fused: the rule itself; for A/B runs and tests).
+    // Its scratch and the statistics' flags are then allocated here, the flags zeroed in front of the kernel.
+    bool counts_with_offsets()
+    {
+        const char *o = ctx_opt(ctx, "MASHGPU_IX_COUNTS");
+        if ((o && strcmp(o, "tiles") == 0) || !mg::index_offsets_counts_fits(early_plan.g)) return false;
+        if (d_tcnt.alloc(early_plan.cnt_bytes) != hipSuccess || d_stat.alloc(1) != hipSuccess ||
+            hipMemsetAsync(d_stat, 0, sizeof(Stat), ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            d_tcnt.free();
+            return false;
+        }
+        return cnt_made = true;
+    }
 
     // the device's counts in the index's order: only if somebody asks (copy suspects, no clustering to be had)
     hipError_t counts_to_device()
@@ -212,16 +230,16 @@ struct SparseIndexBuild {
         sp->dgroups_host.clear();
     }
 
-    struct TileScratch {                                    // index_build.hip's scratch besides the window offsets (IxPlan's sizes)
-        DevBuf<unsigned char> tcnt, start, big, pk, tc;
-        explicit TileScratch(mg_ctx *c) : tcnt(c), start(c), big(c), pk(c), tc(c) {}
+    struct TileScratch {                                    // index_build.hip's scratch besides the window offsets and the blocks' counts (IxPlan's sizes)
+        DevBuf<unsigned char> start, big, pk, tc;
+        explicit TileScratch(mg_ctx *c) : start(c), big(c), pk(c), tc(c) {}
     };
 
     // the ONE call of index_build.hip: its stages by bit mask (index_build.h), the leaders' lists once the candidates are laid out
     hipError_t tiles(const TileScratch &w, int stages)
     {
         const mg::IxLeaders lv = lead.view(d_lead_rows);
-        return mg::index_build_mapped(plan, H, rowmap, sp->off, d_lb, w.tcnt, w.start, w.big, w.pk, w.tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
+        return mg::index_build_mapped(plan, H, rowmap, sp->off, d_lb, d_tcnt, w.start, w.big, w.pk, w.tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
                                sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf, lead_ready ? &lv : nullptr,
                                ctx->stream, stages);
     }
@@ -443,6 +461,7 @@ int SparseIndexBuild::order_rows()
                     early_plan = mg::index_plan((uint32_t)n, (uint32_t)E_all, s, sp->rs, t->s, maxv, dens0, ix_verify);
                     if (early_plan.ok && d_lb.alloc(early_plan.lb_bytes) == hipSuccess) {
                         if (copy_now) HIP_TRY(ctx, mg::index_gather_rows(early_plan, t->hashes, sp->inv, d_cnt, sp->phashes, d_lb, ctx->stream));
+                        else if (counts_with_offsets()) HIP_TRY(ctx, mg::index_offsets_counts(early_plan, t->hashes, sp->inv, d_cnt, d_lb, d_tcnt, d_stat.p->ixf, ctx->stream));
                         else HIP_TRY(ctx, mg::index_window_offsets(early_plan, t->hashes, sp->inv, d_cnt, d_lb, ctx->stream));
                         lb_made = true;
                     } else {
@@ -600,12 +619,12 @@ int SparseIndexBuild::lay_out()
     else if (tiles_hopeless) plan.why = "a clade of more rows than a bucket's sort takes";
     // the tiles' plan (index_build.hip; MASHGPU_SPARSE_INDEX=sort: none).  The window offsets the clustered copy left are
     // those of this plan, or K0 makes them again.
-    if (lb_made && !(plan.ok && memcmp(&plan.g, &early_plan.g, sizeof plan.g) == 0)) lb_made = false;
+    if (lb_made && !(plan.ok && memcmp(&plan.g, &early_plan.g, sizeof plan.g) == 0)) lb_made = cnt_made = false;
     // transient buffers (members: back to the pool when the build object goes, in stream order) and the retained ones
     temp_bytes = std::max(std::max(mg::sparse_order_temp_bytes((uint32_t)n), mg::sparse_order_slice_temp_bytes((uint32_t)n)),
                           mg::sparse_offsets_temp_bytes((uint32_t)n));
     want_order = !ctx_opt(ctx, "MASHGPU_SPARSE_NO_ORDER");
-    bool ok = temp.alloc(std::max<size_t>(temp_bytes, 16)) == hipSuccess && gs_of.alloc(E) == hipSuccess && d_stat.alloc(1) == hipSuccess &&
+    bool ok = temp.alloc(std::max<size_t>(temp_bytes, 16)) == hipSuccess && gs_of.alloc(E) == hipSuccess && (d_stat.p || d_stat.alloc(1) == hipSuccess) &&
               d_slots.alloc(std::max(mg::sparse_stat_scratch_bytes(), mg::index_stat_scratch_bytes())) == hipSuccess &&
               (!want_order || (key64_a.alloc(n) == hipSuccess && key64_b.alloc(n) == hipSuccess));
     // retained buffers
@@ -676,14 +695,15 @@ void SparseIndexBuild::prepare_candidates()
 hipError_t SparseIndexBuild::tile_passes()
 {
     TileScratch w(ctx);
-    if (!((lb_made || d_lb.alloc(plan.lb_bytes) == hipSuccess) && w.tcnt.alloc(plan.cnt_bytes) == hipSuccess && w.start.alloc(plan.start_bytes) == hipSuccess &&
+    if (!((lb_made || d_lb.alloc(plan.lb_bytes) == hipSuccess) && (cnt_made || d_tcnt.alloc(plan.cnt_bytes) == hipSuccess) && w.start.alloc(plan.start_bytes) == hipSuccess &&
           w.big.alloc(plan.big_bytes) == hipSuccess && w.pk.alloc(plan.pk_bytes) == hipSuccess && w.tc.alloc(plan.tc_bytes) == hipSuccess)) {
         (void)hipGetLastError();                            // (no memory for the tiles' scratch: the sort)
         return hipSuccess;
     }
-    hipError_t e = hipMemsetAsync(d_stat, 0, sizeof(Stat), ctx->stream);
+    // (counts made ahead: the statistics were zeroed in front of their kernel, which may have raised a flag since)
+    hipError_t e = cnt_made ? hipSuccess : hipMemsetAsync(d_stat, 0, sizeof(Stat), ctx->stream);
     // the partition (K0 - K3) goes first: the host lays out the candidates for dense groups while it runs
-    if (e == hipSuccess) e = tiles(w, lb_made ? 1 | 8 : 1);
+    if (e == hipSuccess) e = tiles(w, cnt_made ? 1 | 8 | 16 : lb_made ? 1 | 8 : 1);
     // (test knob: what a ticket served out of lane order would leave behind -- the sorts' order check has to refuse the table)
     DevBuf<uint32_t> d_swapped(ctx);
     if (e == hipSuccess && ctx_opt(ctx, "MASHGPU_IX_DEBUG_SWAP") && d_swapped.alloc(1) == hipSuccess) {
@@ -730,6 +750,8 @@ hipError_t SparseIndexBuild::tile_passes()
         fprintf(stderr, "compare sparse: index by tiles: shift %u, %u buckets (%u per window, %u windows), fullest %u, %u beyond the LDS (%u values streamed)%s\n",
                 plan.g.shift, plan.g.Bp, plan.g.BW, plan.g.NW, h_stat.ixf[mg::IXF_MAXBUCKET], h_stat.ixf[mg::IXF_NBIG], h_stat.ixf[mg::IXF_NSTREAMED],
                 h_stat.ixf[mg::IXF_DEGENERATE] ? " -- clumped values: sorted instead" : "");
+    if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+        fprintf(stderr, "compare sparse: block counts %s\n", cnt_made ? "made with the window offsets (one read of the table)" : "by the tiles (K1)");
     return e;
 }
 

@@ -10,6 +10,8 @@
 //   buckets   bucket(v) = v >> shift, about 1 300 - 2 500 entries each (room for 6 144: shared values make the fill uneven); a WINDOW is 2^k consecutive buckets;
 //   K0        per row the position at which every window starts (rows ascend: a row's entries of one window are contiguous);
 //   K1 + K2   entries per (block of 512 rows, bucket) -> where every bucket and every block's share of it starts;
+//   K0 + K1   in ONE pass over the table where 16-bit counters of all buckets fit a workgroup's LDS (index_offsets_counts: a
+//             workgroup per block of rows streams the rows as K0 does and counts every entry in LDS);
 //   K3        a tile = (block of rows, window): the rows' segments are read, sorted by bucket in LDS (stable: by row, then
 //             position) and written as ONE contiguous piece per bucket -- a single pass replaces the radix passes, because a
 //             tile's entries fall into a few hundred buckets only.  An entry travels as one 64-bit word: its value's bits
@@ -91,12 +93,22 @@ hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const 
 // K0 ahead of the build, through the map: the window offsets of the index's rows into lb, the rows' entry counts taken from
 // cnt_table[rowmap[a]] (the TABLE's order -- the index's offsets need not exist yet).  The build then takes stage bit 8.
 hipError_t index_window_offsets(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *cnt_table, void *lb, hipStream_t stream);
+// K0 and K1 ahead of the build from ONE read of the table: the window offsets into lb as index_window_offsets leaves them, and
+// the blocks' bucket counts into cnt (the plan's cnt scratch) as K1 leaves them -- a workgroup per block of rows holds the
+// counts of all Bp buckets in LDS as 16-bit counters.  Only where they fit (index_offsets_counts_fits: 2 Bp bytes and the
+// scan's scratch within the 160 KB of a CU; otherwise hipErrorInvalidValue and the caller takes index_window_offsets).  A
+// counter that overflows raises flags[IXF_DEGENERATE] (flags: zeroed by the caller BEFORE this call and not again before the
+// build); cnt is right even then.  The build then takes stage bits 8 | 16.
+bool index_offsets_counts_fits(const IxGeom &g);
+hipError_t index_offsets_counts(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *cnt_table, void *lb, void *cnt,
+                                uint32_t *flags, hipStream_t stream);
 // The copy of the table in another order of its rows (out[a] = row inv[a], whole rows) that also leaves the window offsets of
 // the copy's rows in lb (K0 inside the copy); cnt_table: entry counts in the table's order.  index_build on `out` then
 // takes stage bit 8.
 hipError_t index_gather_rows(const IxPlan &plan, const uint64_t *hashes, const uint32_t *inv, const uint32_t *cnt_table, uint64_t *out, void *lb,
                              hipStream_t stream);
-// stages (bits): 8 = lb is made already (index_window_offsets, index_gather_rows), 1 = the partition (K0 - K3; needs neither the statistics' memory nor the leaders'), 2 = the bucket sorts (K4, K4b:
+// stages (bits): 8 = lb is made already (index_window_offsets, index_gather_rows), 16 = lb AND the blocks' counts are made already (index_offsets_counts: neither K0
+// nor K1 runs), 1 =the partition (K0 - K3; needs neither the statistics' memory nor the leaders'), 2 = the bucket sorts (K4, K4b:
 // values, rows, groups, statistics, leaders are final behind them), 4 = the images (K5).  A caller prepares the leader search
 // while stage 1 runs, and queues its copy of the statistics between stages 2 and 4.
 

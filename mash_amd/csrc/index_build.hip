@@ -236,6 +236,121 @@ __global__ __launch_bounds__(IX_NT) void ix_tile_count_kernel(IxGeom g, const ui
     if (tid < g.BW) cnt[(uint64_t)blk * g.Bp + (uint64_t)w * g.BW + tid] = s_hist[tid];
 }
 
+// ------------------------------------------------------------------------------------------------
+// K0 + K1 from ONE read of the table (index_offsets_counts): a workgroup per block of rows keeps the block's counts of ALL
+// buckets in LDS -- 16-bit counters, two to a word, as K4 packs its own -- while its waves stream the block's rows as K0 does:
+// whole rows, 64 consecutive entries per load.  K1 read the same values a second time in 64-byte pieces a row stride apart,
+// only to count them.  Runs where the counters fit a workgroup's LDS (index_offsets_counts_fits); otherwise K0 + K1.
+constexpr uint32_t IXOC_NT = 1024;              // 16 waves take the block's rows in turn
+constexpr uint32_t IXOC_UN = 16;                // loads of 64 entries a wave issues before it uses the first (a row of s = 1000: all of it)
+constexpr uint32_t IXOC_SCRATCH = 64;           // the scan's partial sums (ix_block_scan_sum)
+constexpr uint32_t IXOC_LDS_MAX = 160u * 1024u; // what one workgroup may take: the LDS of a CU
+static_assert(IXOC_LDS_MAX <= 160u * 1024u, "a CU of gfx950 has 160 KB of LDS: the counters of one workgroup must fit it");
+static_assert(IX_RB % (IXOC_NT / 64u) == 0, "every wave takes the same number of rows of a full block");
+
+__host__ __device__ inline uint32_t ixoc_words(uint32_t Bp) { return (Bp + 1u) >> 1; }
+__host__ __device__ inline uint64_t ixoc_lds_bytes(uint32_t Bp) { return (uint64_t)ixoc_words(Bp) * 4u + IXOC_SCRATCH; }
+
+// The rows [row0, row0 + nrows) streamed by the workgroup's waves, every entry counted into s_w; returns the entries of the
+// rows this WAVE took.  MODE 0: both counters of a word, 16 bits each, and the rows' window offsets written (lb, exactly K0's
+// statements); MODE 1 / 2: only the even / odd buckets, a whole word each (the recount behind an overflow), nothing written.
+// A row's table row and entry count are asked for one and two rows ahead, so no load of values waits for another load.
+template <uint32_t MODE>
+__device__ __forceinline__ uint32_t ixoc_stream_rows(const IxGeom &g, const uint64_t *__restrict__ H, const uint32_t *__restrict__ rowmap,
+                                                     const uint32_t *__restrict__ cnt_table, uint16_t *__restrict__ lb, uint32_t *s_w, uint32_t row0,
+                                                     uint32_t nrows)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const uint32_t wsh = g.shift + g.bw_log;
+    uint32_t entries = 0;
+    if (wave >= nrows) return 0;                          // (the wave as a whole)
+    auto table_row = [&](uint32_t r) -> uint32_t { return rowmap ? rowmap[row0 + r] : row0 + r; };
+    uint32_t trow = table_row(wave);
+    uint32_t trow_n = table_row(wave + nw < nrows ? wave + nw : wave);
+    uint32_t cnt = cnt_table[trow];
+    for (uint32_t r = wave; r < nrows; r += nw) {        // uniform in the wave
+        const uint32_t cnt_n = cnt_table[trow_n];
+        const uint32_t trow_nn = table_row(r + 2u * nw < nrows ? r + 2u * nw : r);
+        const uint64_t *src = H + (uint64_t)trow * g.stride;
+        uint16_t *out = lb + (uint64_t)(row0 + r) * (g.NW + 1u);
+        entries += cnt;
+        int wlast = -1;                                   // the window of the entry before the chunk (none: -1)
+        for (uint32_t p0 = 0; p0 < cnt; p0 += 64u * IXOC_UN) {      // uniform in the wave
+            uint64_t v[IXOC_UN];
+#pragma unroll
+            for (uint32_t u = 0; u < IXOC_UN; u++) {
+                const uint32_t p = p0 + 64u * u + lane;
+                v[u] = src[p < cnt ? p : 0u];
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < IXOC_UN; u++) {
+                const uint32_t c0 = p0 + 64u * u, p = c0 + lane;
+                const int w = (int)(uint32_t)(v[u] >> wsh);
+                // the neighbour's window from a shuffle, lane 0's from the chunk before; the chunk's last entry's for the next
+                int wp = __shfl_up(w, 1u);
+                if (lane == 0) wp = wlast;
+                const int wl = __shfl(w, cnt - 1u - c0 < 64u ? cnt - 1u - c0 : 63u);
+                if (c0 < cnt) wlast = wl;
+                if (p < cnt) {
+                    if (MODE == 0)
+                        for (int x = wp + 1; x <= w; x++) out[x] = (uint16_t)p;
+                    const uint32_t b = (uint32_t)(v[u] >> g.shift);
+                    // (a value beyond the plan's largest has no counter: left out, and the sum behind the rows misses it)
+                    if (b < g.Bp) {
+                        if (MODE == 0) atomicAdd(&s_w[b >> 1], 1u << (16u * (b & 1u)));
+                        else if ((b & 1u) == MODE - 1u) atomicAdd(&s_w[b >> 1], 1u);
+                    }
+                }
+            }
+        }
+        if (MODE == 0)
+            for (uint32_t x = (uint32_t)(wlast + 1) + lane; x <= g.NW; x += 64u) out[x] = (uint16_t)cnt;
+        trow = trow_n;
+        trow_n = trow_nn;
+        cnt = cnt_n;
+    }
+    return entries;
+}
+
+// lb as K0 leaves it, cnt[blk][bucket] as K1 leaves it (u32, the whole row of Bp counters).  A 16-bit counter that overflows
+// carries into its neighbour: the halves then sum to less than the block's entries (every overflow takes 65 535 or 65 536 off
+// the sum, none adds), the workgroup raises flags[IXF_DEGENERATE] -- such a table is the general sort's -- and counts again,
+// the even and the odd buckets in turn with a whole word each, so that what K2 / K3 are given is right in any case.
+__global__ __launch_bounds__(IXOC_NT) void ix_offsets_counts_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint32_t *__restrict__ rowmap,
+                                                                    const uint32_t *__restrict__ cnt_table, uint16_t *__restrict__ lb,
+                                                                    uint32_t *__restrict__ cnt, uint32_t *flags)
+{
+    MG_DYN_SHARED(uint32_t, s_w);
+    const uint32_t nwords = ixoc_words(g.Bp);
+    uint32_t *s_part = s_w + nwords;
+    const uint32_t tid = threadIdx.x, blk = blockIdx.x;
+    const uint32_t row0 = blk * IX_RB, nrows = g.n - row0 < IX_RB ? g.n - row0 : IX_RB;
+    uint32_t *o = cnt + (uint64_t)blk * g.Bp;
+    for (uint32_t x = tid; x < nwords; x += IXOC_NT) s_w[x] = 0;
+    __syncthreads();
+    const uint32_t mine = ixoc_stream_rows<0>(g, H, rowmap, cnt_table, lb, s_w, row0, nrows);
+    __syncthreads();
+    uint32_t sum = 0;
+    for (uint32_t x = tid; x < nwords; x += IXOC_NT) sum += (s_w[x] & 0xFFFFu) + (s_w[x] >> 16);
+    uint32_t counted = 0, entries = 0;
+    (void)ix_block_scan_sum(sum, s_part, counted);
+    (void)ix_block_scan_sum((tid & 63u) == 0 ? mine : 0u, s_part, entries);
+    if (counted == entries) {                            // uniform
+        for (uint32_t b = tid; b < g.Bp; b += IXOC_NT) o[b] = (s_w[b >> 1] >> (16u * (b & 1u))) & 0xFFFFu;
+        return;
+    }
+    if (tid == 0) flags[IXF_DEGENERATE] = 1u;
+    for (uint32_t half = 0; half < 2u; half++) {
+        __syncthreads();
+        for (uint32_t x = tid; x < nwords; x += IXOC_NT) s_w[x] = 0;
+        __syncthreads();
+        if (half == 0) (void)ixoc_stream_rows<1>(g, H, rowmap, cnt_table, lb, s_w, row0, nrows);
+        else (void)ixoc_stream_rows<2>(g, H, rowmap, cnt_table, lb, s_w, row0, nrows);
+        __syncthreads();
+        for (uint32_t b = half + 2u * tid; b < g.Bp; b += 2u * IXOC_NT) o[b] = s_w[b >> 1];
+    }
+}
+
 // K2a: per bucket the blocks' counts become exclusive prefixes over the blocks; tot[bucket] = the bucket's entries
 __global__ __launch_bounds__(256) void ix_col_scan_kernel(IxGeom g, uint32_t *cnt, uint32_t *tot)
 {
@@ -1361,6 +1476,20 @@ hipError_t index_window_offsets(const IxPlan &plan, const uint64_t *hashes, cons
     return hipGetLastError();
 }
 
+bool index_offsets_counts_fits(const IxGeom &g) { return ixoc_lds_bytes(g.Bp) <= IXOC_LDS_MAX; }
+
+hipError_t index_offsets_counts(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *cnt_table, void *lb_v, void *cnt_v,
+                                uint32_t *flags, hipStream_t stream)
+{
+    if (!plan.ok || !index_offsets_counts_fits(plan.g)) return hipErrorInvalidValue;
+    const uint32_t lds = (uint32_t)ixoc_lds_bytes(plan.g.Bp);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ix_offsets_counts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ix_offsets_counts_kernel, dim3(plan.g.nblk), dim3(IXOC_NT), lds, stream, plan.g, hashes, rowmap, cnt_table, static_cast<uint16_t *>(lb_v),
+                       static_cast<uint32_t *>(cnt_v), flags);
+    return hipGetLastError();
+}
+
 hipError_t index_build(const IxPlan &plan, const uint64_t *hashes, const uint32_t *off, void *lb_v, void *cnt_v, void *start_v, void *big_v, void *pk_v, void *tc_v,
                        uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of, uint32_t *code_img, uint32_t *pos_img,
                        void *stat_scratch, unsigned long long *incidences, uint32_t *max_group, uint32_t *groups, uint32_t *flags,
@@ -1387,9 +1516,9 @@ hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const 
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(ix_tile_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)IXL_BYTES);
         if (e != hipSuccess) return e;
         const uint32_t tiles = 8u * ((g.nseq + 7u) / 8u);
-        if (!(stages & 8)) hipLaunchKernelGGL(ix_window_offsets_kernel, dim3((g.n + 3u) / 4u), dim3(256), 0, stream, g, hashes, rowmap, off,
-                                              (const uint32_t *)nullptr, lb);
-        hipLaunchKernelGGL(ix_tile_count_kernel, dim3(tiles), dim3(IX_NT), 0, stream, g, hashes, rowmap, (const uint16_t *)lb, cnt);
+        if (!(stages & (8 | 16))) hipLaunchKernelGGL(ix_window_offsets_kernel, dim3((g.n + 3u) / 4u), dim3(256), 0, stream, g, hashes, rowmap, off,
+                                                     (const uint32_t *)nullptr, lb);
+        if (!(stages & 16)) hipLaunchKernelGGL(ix_tile_count_kernel, dim3(tiles), dim3(IX_NT), 0, stream, g, hashes, rowmap, (const uint16_t *)lb, cnt);
         hipLaunchKernelGGL(ix_col_scan_kernel, dim3((g.Bp + 255u) / 256u), dim3(256), 0, stream, g, cnt, start);
         hipLaunchKernelGGL(ix_bucket_scan_kernel, dim3(1), dim3(1024), 0, stream, g, start, flags, static_cast<uint32_t *>(big_v));
         e = hipGetLastError();
