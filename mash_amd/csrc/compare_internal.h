@@ -164,7 +164,7 @@ hipError_t launch_sparse_merge(const SparseArgs &a, uint64_t expect, uint32_t cu
 bool sparse_merge_rows_supported(uint32_t rs_row);
 size_t sparse_scan_temp_bytes(uint32_t nrows);
 hipError_t launch_sparse_merge_rows(const SparseArgs &a, uint64_t expect, uint32_t *chunks, void *temp, size_t temp_bytes,
-                                    hipStream_t stream);
+                                    hipStream_t stream, bool *windowed_out = nullptr);
 hipError_t launch_sparse_scatter(const SparseArgs &a, uint64_t expect, uint32_t cus, hipStream_t stream);
 size_t sparse_gather_temp_bytes(uint32_t nrows);
 hipError_t launch_sparse_gather_rows(const SparseArgs &a, uint32_t *cnt_by_row, uint32_t *row_base, void *temp, size_t temp_bytes, uint32_t row_add,
@@ -181,7 +181,7 @@ hipError_t launch_sparse_fill_chunks(uint2 *out, uint64_t pairs, uint32_t numer,
 hipError_t launch_sparse_fill_value(uint2 *out, uint64_t pairs, uint32_t numer, uint32_t denom, uint32_t blocks_per_cu, uint32_t cus,
                                     hipStream_t stream);
 hipError_t launch_sparse_merge_pack(const SparseArgs &a, uint64_t expect, uint32_t *chunks, void *temp, size_t temp_bytes, bool *used,
-                                    hipStream_t stream);
+                                    hipStream_t stream, uint32_t *pack_min_out = nullptr);
 hipError_t launch_sparse_fill_short(uint2 *out, const uint32_t *short_rows, const uint32_t *short_rcnt, uint32_t nshort_rows,
                                     const uint32_t *short_cols, const uint32_t *short_ccnt, uint32_t nshort_cols,
                                     uint32_t row_begin, uint32_t ncols, uint32_t triangle, uint64_t out_base, uint32_t s,

@@ -26,20 +26,33 @@
 //
 // The sort of the index is rocPRIM's stable radix sort (value keys, entry ids as payload); every
 // other step is a kernel below.
-#include <hip/hip_runtime.h>
+//
+// (Locate, discover, the merge kernels, scatter, class pairs and the fill of short pairs also compile for tools/hipemu --
+//  MG_HIP_EMU: work-items as fibers on the CPU, tests/test_sparse_emu.py; the index build by radix sort, the lists of a
+//  thresholded job and the streaming fills -- whatever needs rocPRIM sorts or stores of the hardware -- are left out of that
+//  build, and the two scans of the merge launchers are std::partial_sum there.)
 #include <stdint.h>
 
 #include <cstdlib>
 #include <cstring>
+
+#include "compare_internal.h"
+#ifdef MG_HIP_EMU
+#include <numeric>
+#define SP_DYN_U32(name, align) MG_DYN_SHARED(uint32_t, name)
+#else
+#include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
-
-#include "compare_internal.h"
+#define SP_DYN_U32(name, align) extern __shared__ align uint32_t name[]
+#endif
 #include "copy_gate.h"
 
 namespace mg {
+
+#ifndef MG_HIP_EMU
 
 // ------------------------------------------------------------------------------------------------
 // index build
@@ -227,12 +240,15 @@ hipError_t launch_sparse_offsets(const uint32_t *cnt, const uint32_t *inv, uint3
     return hipGetLastError();
 }
 
+#endif  // !MG_HIP_EMU
+
 __global__ __launch_bounds__(256) void sp_fill_u32_kernel(uint32_t *p, uint64_t count, uint32_t v)
 {
     const uint64_t stride = (uint64_t)gridDim.x * 256u;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < count; i += stride) p[i] = v;
 }
 
+#ifndef MG_HIP_EMU
 // ---- identical rows: collections hold many copies of one sketch (isolates of an outbreak, re-submitted
 // genomes).  Copies form a CLASS represented by its first row: only representatives enter the index,
 // discovery marks classes and expands them to rows when it lists candidates, and a pair inside a
@@ -433,9 +449,12 @@ hipError_t launch_sparse_order_slice(const uint32_t *order, uint32_t n, uint32_t
     return rocprim::select(temp, temp_bytes, order, out, count_out, (size_t)n, sp_in_range{rb, re}, stream);
 }
 
+#endif  // !MG_HIP_EMU
+
 // row stride of a code image: s rounded up to a chunk of four, plus one chunk the loop may load behind the row
 uint32_t sparse_img_stride(uint32_t s) { return ((s + 3u) & ~3u) + 4u; }
 
+#ifndef MG_HIP_EMU
 struct sp_max_u32 {
     __device__ uint32_t operator()(const uint32_t &a, const uint32_t &b) const { return a > b ? a : b; }
 };
@@ -652,6 +671,8 @@ hipError_t sparse_build_index(const uint64_t *hashes, uint64_t stride, const uin
     return hipGetLastError();
 }
 
+#endif  // !MG_HIP_EMU
+
 // ------------------------------------------------------------------------------------------------
 // rect: locate the queries' values in the reference table's index
 
@@ -713,7 +734,7 @@ __device__ __forceinline__ uint32_t sp_class_span(const SparseArgs &a, uint32_t 
 template <bool COUNT_ONLY, bool DEDUP>
 __global__ __launch_bounds__(256) void sp_discover_kernel(SparseArgs a)
 {
-    extern __shared__ uint32_t bm[];
+    SP_DYN_U32(bm, );
     __shared__ uint32_t s_w[4];
     __shared__ unsigned long long s_base;
     __shared__ unsigned long long s_inc[4];
@@ -937,7 +958,7 @@ __global__ __launch_bounds__(256) void sp_chunks_kernel(const uint32_t *seg_cnt,
 template <bool RECT>
 __global__ __launch_bounds__(SPM_NT) void sp_merge_rows_kernel(SparseArgs a)
 {
-    extern __shared__ __align__(16) uint32_t lds[];
+    SP_DYN_U32(lds, __align__(16));
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t nrows = a.row_end - a.row_begin;
     const uint32_t item = blockIdx.x;
@@ -1048,7 +1069,7 @@ __global__ __launch_bounds__(SPM_NT) void sp_merge_rows_kernel(SparseArgs a)
 template <bool RECT>
 __global__ __launch_bounds__(SPM_NT) void sp_merge_rows_win_kernel(SparseArgs a)
 {
-    extern __shared__ __align__(16) uint32_t lds[];
+    SP_DYN_U32(lds, __align__(16));
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t nrows = a.row_end - a.row_begin;
     const uint32_t item = blockIdx.x;
@@ -1189,7 +1210,7 @@ template <bool RECT, uint32_t SPM_PACK_MIN>
 __global__ __launch_bounds__(SPM_NT) void sp_merge_pack_kernel(SparseArgs a)
 {
     constexpr uint32_t SPM_PACK_ROWS = (SPM_NT + SPM_PACK_MIN - 1u) / SPM_PACK_MIN + 1u;
-    extern __shared__ __align__(16) uint32_t lds[];
+    SP_DYN_U32(lds, __align__(16));
     __shared__ uint32_t pslot[SPM_PACK_ROWS];
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t nrows = a.row_end - a.row_begin;
@@ -1317,9 +1338,10 @@ __global__ __launch_bounds__(SPM_NT) void sp_merge_pack_kernel(SparseArgs a)
 }
 
 // chunks / chunk_inc / temp as for launch_sparse_merge_rows; false in *used: the job is not one for this kernel (rows
-// longer than the LDS window, too much LDS) and the caller takes launch_sparse_merge_rows
+// longer than the LDS window, too much LDS) and the caller takes launch_sparse_merge_rows; *pack_min_out (nullable): the
+// units per row of the instantiation that was launched
 hipError_t launch_sparse_merge_pack(const SparseArgs &a, uint64_t expect, uint32_t *chunks, void *temp, size_t temp_bytes, bool *used,
-                                    hipStream_t stream)
+                                    hipStream_t stream, uint32_t *pack_min_out)
 {
     *used = false;
     const uint32_t nrows = a.row_end - a.row_begin;
@@ -1334,8 +1356,13 @@ hipError_t launch_sparse_merge_pack(const SparseArgs &a, uint64_t expect, uint32
     hipLaunchKernelGGL(sp_pack_costs_kernel, dim3((nrows + 255u) / 256u), dim3(256), 0, stream, a.seg_cnt, nrows, pack_min, chunks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+#ifdef MG_HIP_EMU
+    (void)temp; (void)temp_bytes;
+    std::partial_sum(chunks, chunks + nrows, a.chunk_inc);
+#else
     e = rocprim::inclusive_scan(temp, temp_bytes, (const uint32_t *)chunks, a.chunk_inc, (size_t)nrows, rocprim::plus<uint32_t>(), stream);
     if (e != hipSuccess) return e;
+#endif
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e2 != hipSuccess) return e2;
@@ -1343,12 +1370,13 @@ hipError_t launch_sparse_merge_pack(const SparseArgs &a, uint64_t expect, uint32
         return hipGetLastError();
     };
     *used = true;
+    if (pack_min_out) *pack_min_out = pack_min;
     if (pack_min == 32) return a.triangle ? go(sp_merge_pack_kernel<false, 32>) : go(sp_merge_pack_kernel<true, 32>);
     if (pack_min == 43) return a.triangle ? go(sp_merge_pack_kernel<false, 43>) : go(sp_merge_pack_kernel<true, 43>);
     return a.triangle ? go(sp_merge_pack_kernel<false, 64>) : go(sp_merge_pack_kernel<true, 64>);
 }
 
-
+#ifndef MG_HIP_EMU
 // candidates in REFERENCE order (rows ascending; a row's segment is already in column order): the rows'
 // counts (by row), then, after an exclusive scan, every segment copied to its row's place
 __global__ __launch_bounds__(256) void sp_row_counts_kernel(SparseArgs a, uint32_t *cnt_by_row)
@@ -1470,6 +1498,8 @@ size_t sparse_gather_temp_bytes(uint32_t nrows)
     return b;
 }
 
+#endif  // !MG_HIP_EMU
+
 // results of the candidates -> their output slots (after the fill)
 __global__ __launch_bounds__(256) void sp_scatter_kernel(SparseArgs a)
 {
@@ -1530,6 +1560,7 @@ hipError_t launch_sparse_class_pairs(uint2 *out, const uint32_t *cls_rows, const
 // ------------------------------------------------------------------------------------------------
 // fill: {0, denom} for every pair
 
+#ifndef MG_HIP_EMU
 typedef uint32_t sp_u32x4 __attribute__((ext_vector_type(4)));
 
 // every wave writes 4 KB of consecutive addresses per round (four 16-byte nontemporal stores 1 KB apart; 6.7 ms for the 40 GB of
@@ -1613,6 +1644,8 @@ hipError_t launch_sparse_fill_value(uint2 *out, uint64_t pairs, uint32_t numer, 
     hipLaunchKernelGGL(sp_fill_value_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, out, pairs, numer, denom);
     return hipGetLastError();
 }
+
+#endif  // !MG_HIP_EMU
 
 // pairs of two SHORT sketches (|A| + |B| < s): denom = |A| + |B|.  One workgroup per short row of
 // the row side, threads over the short rows of the column side (both lists ascending).
@@ -1699,24 +1732,35 @@ size_t sparse_merge_rows_lds(uint32_t rs_row)
 bool sparse_merge_rows_supported(uint32_t rs_row) { return sparse_merge_rows_lds(rs_row) <= 160 * 1024 - 256; }
 size_t sparse_scan_temp_bytes(uint32_t nrows)
 {
+#ifdef MG_HIP_EMU
+    (void)nrows;
+    return 16;
+#else
     size_t b = 0;
     rocprim::inclusive_scan(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)nrows, rocprim::plus<uint32_t>(),
                             (hipStream_t) nullptr);
     return b;
+#endif
 }
 
 // Row-blocked merge of the candidates the discover launch listed: work items from the rows' segment
-// sizes (scan), then one workgroup per item.  `expect`: the candidate count of the counting pass.
+// sizes (scan), then one workgroup per item.  `expect`: the candidate count of the counting pass.  *windowed_out
+// (nullable): whether the windowed kernel was the one launched.
 hipError_t launch_sparse_merge_rows(const SparseArgs &a, uint64_t expect, uint32_t *chunks, void *temp, size_t temp_bytes,
-                                    hipStream_t stream)
+                                    hipStream_t stream, bool *windowed_out)
 {
     const uint32_t nrows = a.row_end - a.row_begin;
     if (expect == 0 || nrows == 0) return hipSuccess;
     hipLaunchKernelGGL(sp_chunks_kernel, dim3((nrows + 255u) / 256u), dim3(256), 0, stream, a.seg_cnt, nrows, chunks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+#ifdef MG_HIP_EMU
+    (void)temp; (void)temp_bytes;
+    std::partial_sum(chunks, chunks + nrows, a.chunk_inc);
+#else
     e = rocprim::inclusive_scan(temp, temp_bytes, (const uint32_t *)chunks, a.chunk_inc, (size_t)nrows, rocprim::plus<uint32_t>(), stream);
     if (e != hipSuccess) return e;
+#endif
     const uint64_t items = expect / SPM_NT + nrows;              // upper bound: one partial item per row
     if (items >= (1ull << 31)) return hipErrorInvalidValue;
     const size_t smem = sparse_merge_rows_lds(a.rs_row);
@@ -1728,6 +1772,7 @@ hipError_t launch_sparse_merge_rows(const SparseArgs &a, uint64_t expect, uint32
     };
     // rows that fit the LDS window whole take the kernel without window logic
     const bool whole = a.rs_row <= SPM_AWIN + 8u && !getenv("MASHGPU_SPARSE_MERGE_WINDOWS");
+    if (windowed_out) *windowed_out = !whole;
     if (a.triangle) return whole ? go(sp_merge_rows_kernel<false>) : go(sp_merge_rows_win_kernel<false>);
     return whole ? go(sp_merge_rows_kernel<true>) : go(sp_merge_rows_win_kernel<true>);
 }

@@ -1249,12 +1249,20 @@ int SparseJobRun::merge_and_scatter()
     // fill their own items and gain nothing from staging their neighbours (measured: 27.8 -> 33.4 ms on the clade table)
     bool pack = by_rows && plan->cand < 64ull * nrows;
     if (const char *ev = ctx_opt(ctx, "MASHGPU_SPARSE_MERGE_PACK")) pack = by_rows && atoi(ev) != 0;
-    if (pack) e = mg::launch_sparse_merge_pack(a, plan->cand, ix->chunks, ix->scan_temp, ix->scan_temp_bytes, &packed, ctx->stream);
+    uint32_t pack_min = 0;
+    bool windowed = false;
+    if (pack) e = mg::launch_sparse_merge_pack(a, plan->cand, ix->chunks, ix->scan_temp, ix->scan_temp_bytes, &packed, ctx->stream, &pack_min);
     if (!packed && e == hipSuccess)
-        e = by_rows ? mg::launch_sparse_merge_rows(a, plan->cand, ix->chunks, ix->scan_temp, ix->scan_temp_bytes, ctx->stream)
+        e = by_rows ? mg::launch_sparse_merge_rows(a, plan->cand, ix->chunks, ix->scan_temp, ix->scan_temp_bytes, ctx->stream, &windowed)
                     : mg::launch_sparse_merge(a, plan->cand, (uint32_t)ctx->cu_count, ctx->stream);
     clk_end(CK_MERGE);
     prof_end(ctx, ctx->prof_merge);
+    if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG")) {
+        char form[16];
+        if (packed) snprintf(form, sizeof form, "pack %u", pack_min);
+        else snprintf(form, sizeof form, "%s", !by_rows ? "lanes" : windowed ? "rows windowed" : "rows");
+        fprintf(stderr, "compare merge: %s, %llu candidates%s\n", form, (unsigned long long)plan->cand, job ? " (for lists)" : "");
+    }
     if (e != hipSuccess) return fail(ctx, MG_ERR_HIP, std::string("compare (merge): ") + hipGetErrorString(e));
     if (job) job->args = a;
     if (!job) {

@@ -212,7 +212,7 @@ def test_model_rect_equals_oracle(oracle, s):
 
 @pytest.mark.parametrize("pack_min", [32, 43, 64])
 def test_pack_mapping_of_candidates_to_lanes(pack_min):
-    """The work distribution of sp_merge_pack_kernel (compare_sparse_x.hip) in numpy: candidates of all rows as one line
+    """The work distribution of sp_merge_pack_kernel (compare_sparse.hip) in numpy: candidates of all rows as one line
     of units (a row with candidates takes max(candidates, pack_min) units), item t = units [128 t, 128 t + 128).  Every
     lane finds its row from the rows of the item's probe units (0, pack_min, 2 pack_min, ..., 127) alone -- at most
     one row boundary lies between two probes -- and every candidate of every row is some lane's, exactly once."""

@@ -304,6 +304,8 @@ static inline uint64_t __ballot(int pred)
     hipemu::wave_sync();
     return m;
 }
+// the value lane `l` holds (l uniform over the wave, every lane of the wave takes part -- as __shfl above)
+static inline int __builtin_amdgcn_readlane(int v, int l) { return __shfl(v, (unsigned)l); }
 static inline int __popcll(uint64_t x) { return __builtin_popcountll(x); }
 static inline int __popc(uint32_t x) { return __builtin_popcount(x); }
 
