@@ -576,7 +576,7 @@ void sketch_reads(Gpu &gpu, SketchSet &set, const vector<string> &files, mg_sket
         mp.target_cov = set.p.target_cov;
         mp.bloom_bytes = set.p.bloom_bytes;
         // (MASH_AMD_SHARED_READS=1: one session for all reads-mode files of a run, emptied by mg_reads_reset between
-        //  them -- its device buffers are then allocated once; opt-in until it has run on the GPU)
+        //  them -- its device buffers are then allocated once)
         if (shared_reads && *shared_reads) rs = *shared_reads;
         else if (mg_reads_begin(gpu.ctx, &mp, &rs) != MG_OK) { cerr << "ERROR: " << mg_last_error(gpu.ctx) << endl; exit(1); }
         b.bases.reserve(std::min<size_t>(reads_chunk, 64u << 20) + (1u << 16));

@@ -750,3 +750,228 @@ SCREEN_CASES = ("flood", "flood_wide", "flood_forward", "flood_translated", "sho
 
 def screen_case(name):
     return globals()["screen_case_" + name]()
+
+
+# ---------------------------------------------------------------------------------------------- sketch kernels against the oracle
+#
+# tests/test_sketch_instances_gpu.py runs the sketch kernels (sketch.hip) at every instantiation, tile seam and merge level on the
+# inputs built here; tests/test_sketch_cases_oracle.py asserts on the CPU that the inputs reach what they are built for.  The judge
+# is oracle.sketch_records / oracle.sketch_reads, every comparison exact.
+#
+# The constants below RESTATE the engine's plan (plan_sketch_work, host_sketch.cpp; sketch_geometry, sketch.hip).  They are compared
+# with nothing at run time: they are the tests' claim about the code, and a change of the plan is made in both places on purpose.
+
+SKETCH_TILE = {256: 256 * 60, 1024: 1024 * 28}            # k-mer starts per tile: NT lanes of sk_L(NT) starts (kmer_stream.h)
+SKETCH_MIN_CHUNK_TILES = 4                                # a chunk (one workgroup) is at least four tiles ...
+SKETCH_TARGET_ITEMS = 2048                                # ... and a batch is cut into about this many
+SKETCH_MERGE_GROUP = 32                                   # above 2 * 32 chunks a sketch is merged in groups of 32, then the groups
+SKETCH_SEGMENT = {256: 256 * 4 * 2, 1024: 1024 * 4 * 1}   # candidates one segment may append: NT * 4 * sk_seg_dw(NT)
+SKETCH_PER_LANE = 16                                      # the candidate buffer holds at most 16 hashes per lane (SK_E)
+SKETCH_ONE_TILE = {"MASHGPU_SKETCH_MIN_CHUNK": "15360", "MASHGPU_SKETCH_ITEMS": "100000"}     # chunks of one tile (15 360 is rounded up)
+SKETCH_ENV = ("MASHGPU_SKETCH_MIN_CHUNK", "MASHGPU_SKETCH_ITEMS", "MASHGPU_SKETCH_NO_SEED", "MASHGPU_SKETCH_SEED_FACTOR")
+# MODE 0: canonical DNA, 1: forward-only DNA, 2: a table alphabet, forward-only
+SKETCH_MODES = ({}, {"noncanonical": True}, {"alphabet": SCREEN_PROTEIN, "noncanonical": True})
+_PROTEIN_LETTERS = np.frombuffer(SCREEN_PROTEIN.encode(), dtype=np.uint8)
+
+
+def sketch_geometry(s):
+    """(NT, capacity of the candidate buffer) the LDS selector takes for sketch size s, None where s goes to range counting in HBM:
+    the capacity is the power of two that holds s and one segment, at most 16 hashes per lane"""
+    for nt in (256, 1024):
+        cap = 2
+        while cap < s + SKETCH_SEGMENT[nt]:
+            cap <<= 1
+        if cap <= SKETCH_PER_LANE * nt:
+            return nt, cap
+    return None
+
+
+def sketch_plan(lengths, k, nt, env=None):
+    """plan_sketch_work restated: per sketch of the batch None (no k-mer) or {"chunks", "groups": slots per first-level merge ([]:
+    one level), "last": k-mer starts of the last chunk}; env: the two knobs of the plan as the environment gives them"""
+    env = env or {}
+    tile = SKETCH_TILE[nt]
+    total = sum(l - k + 1 for l in lengths if l >= k)
+    items = max(int(env.get("MASHGPU_SKETCH_ITEMS", SKETCH_TARGET_ITEMS)), 1)
+    chunk = max(-(-total // items), int(env.get("MASHGPU_SKETCH_MIN_CHUNK", SKETCH_MIN_CHUNK_TILES * tile)))
+    chunk = -(-chunk // tile) * tile
+    out = []
+    for l in lengths:
+        if l < k:
+            out.append(None)
+            continue
+        npos = l - k + 1
+        nch = -(-npos // chunk)
+        g = SKETCH_MERGE_GROUP
+        groups = [min(g, nch - i) for i in range(0, nch, g)] if nch > 2 * g else []
+        out.append({"chunks": nch, "groups": groups, "last": npos - (nch - 1) * chunk})
+    return out
+
+
+def sketch_batch(blobs):
+    """(bases u8[], off u64[n + 1]) of a batch as mg_sketch_host takes it: one blob (records joined with the separator) per sketch"""
+    off = np.zeros(len(blobs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+    return np.frombuffer(b"".join(blobs), dtype=np.uint8), off
+
+
+def sketch_expected(oracle, kw, bases, off):
+    """the oracle's (hashes, counts) of every sketch of a batch: bytes [off[i], off[i + 1]) alone, cut into records at the separators"""
+    p = oracle.params(**kw)
+    raw = bases.tobytes()
+    out = []
+    for i in range(len(off) - 1):
+        h, c, _, _, _ = oracle.sketch_records(raw[int(off[i]): int(off[i + 1])].split(RECORD_SEP), p)
+        out.append((h, c))
+    return out
+
+
+def _rand_protein(rng, n):
+    return _PROTEIN_LETTERS[rng.integers(0, 20, n)].tobytes()
+
+
+# ---- 1. the wide selector (NT = 1024) at every k and mode
+
+SKETCH_WIDE_SIZES = (2049, 4097, 12288)                    # the first s of NT = 1024, the first of capacity 16 384, the last of the selector
+
+
+def sketch_case_wide(k):
+    """{"s", "dna": sketches for MODE 0 and 1, "protein": sketches for MODE 2}; sketch 0 of each is one long record with two seams of
+    the 28 672 tile (70 kbp) resp. one (40 000 residues where s = 12 288, which 12 000 residues cannot fill), the others adversarial"""
+    from workloads import synth
+    rng = np.random.default_rng(8100 + k)
+    s = SKETCH_WIDE_SIZES[k % 3]
+    dna = [[synth._rand_dna(rng, 70000)], synth.adversarial_dna_records(rng, 1), synth.adversarial_dna_records(rng, 2)]
+    protein = [[_rand_protein(rng, 40000 if s == 12288 else 12000)], synth.random_protein_records(rng, 1)]
+    return {"s": s, "dna": dna, "protein": protein}
+
+
+# ---- 2. the boundaries of sketch_geometry
+
+SKETCH_GEOMETRY_SIZES = {2048: (256, 4096), 2049: (1024, 8192), 4096: (1024, 8192), 4097: (1024, 16384), 12288: (1024, 16384), 12289: None}
+
+
+def sketch_case_geometry():
+    """{"dna": (kw, sketches), "protein": (kw, sketches)}: one record of 150 kbp at k = 21 canonical, one of 40 000 residues at k = 9"""
+    from workloads import synth
+    rng = np.random.default_rng(8200)
+    return {"dna": ({"k": 21}, [[synth._rand_dna(rng, 150000)]]),
+            "protein": (dict(SKETCH_MODES[2], k=9), [[_rand_protein(rng, 40000)]])}
+
+
+# ---- 3. the event kernel (reads mode with -c / -b) at every k and mode
+
+SKETCH_EVENT_READS, SKETCH_EVENT_COV, SKETCH_EVENT_BLOOM = 800, 3.0, 700
+
+
+def sketch_case_events(k, mode):
+    """800 reads of 40 .. 119 symbols cut out of a 3 000-symbol source (DNA: half of them reverse complements), every tenth with an
+    invalid symbol"""
+    from workloads import synth
+    rng = np.random.default_rng(8300 + 3 * k + mode)
+    src = _rand_protein(rng, 3000) if mode == 2 else synth._rand_dna(rng, 3000)
+    reads = []
+    for i in range(SKETCH_EVENT_READS):
+        l = int(rng.integers(40, 120))
+        st = int(rng.integers(0, 3000 - l))
+        r = bytearray(src[st:st + l])
+        if i % 10 == 9:
+            r[int(rng.integers(0, l))] = ord("X" if mode == 2 else "N")
+        r = bytes(r)
+        reads.append(_revcomp(r) if mode != 2 and rng.random() < 0.5 else r)
+    return reads
+
+
+# ---- 4. an invalid byte and a record separator at every offset around a tile seam
+
+SKETCH_SEAM_KS = (1, 4, 5, 16, 17, 21, 32)
+SKETCH_SEAM_SIZES = (300, 3000)                            # NT = 256 and NT = 1024
+SKETCH_SEAM_MODES = (5, 21)                                # the k-mer sizes that also run MODE 1 and MODE 2
+
+
+def sketch_case_seams(k, s, mode=0):
+    """(kw, bases, off, where): for every d in [-k, k] one sketch whose byte TILE + d is invalid (MODE 0: N; MODE 1 with preserve_case:
+    a lower-case base; MODE 2: X) and one whose byte TILE + d is the record separator -- two records split there.  Every sketch is
+    two tiles and 1 001 bytes long, an odd length of 9 mod 16, so that consecutive sketches begin at every alignment of the 16-byte
+    loads; the sweep is repeated until the batch has 16 sketches.  where: (offset of the byte within its sketch, the byte) per sketch"""
+    from workloads import synth
+    nt, _ = sketch_geometry(s)
+    tile = SKETCH_TILE[nt]
+    rng = np.random.default_rng(8400 + 10 * k + mode + s)
+    kw = dict(SKETCH_MODES[mode], k=k, s=s)
+    if mode == 1:
+        kw["preserve_case"] = True
+    blobs, where = [], []
+    while len(blobs) < 16:
+        for d in range(-k, k + 1):
+            for sep in (False, True):
+                n = 2 * tile + 1001
+                b = bytearray(_rand_protein(rng, n) if mode == 2 else synth._rand_dna(rng, n))
+                at = tile + d
+                b[at] = RECORD_SEP[0] if sep else (ord("N"), b[at] + 32, ord("X"))[mode]
+                blobs.append(bytes(b))
+                where.append((at, b[at]))
+    bases, off = sketch_batch(blobs)
+    return kw, bases, off, where
+
+
+# ---- 5. slices of one genome: sketches that touch without a separator
+
+SKETCH_SLICE_KS = (5, 16, 21, 32)
+
+
+def sketch_slice_lengths(k, tile):
+    return [0, k - 1, k, k + 1, 15, 16, 17, tile - 1, tile, tile + 1, tile + k - 2, tile + k - 1, tile + k,
+            SKETCH_MIN_CHUNK_TILES * tile + k - 1,          # the largest sketch of one chunk
+            SKETCH_MIN_CHUNK_TILES * tile + k]              # two chunks, the second of one k-mer start
+
+
+def sketch_case_slices(k, s):
+    """(kw, bases, off): one buffer of ACGT (about 400 kbp at the 28 672 tile) with three N in it, cut by off[] alone into slices of
+    sketch_slice_lengths: a k-mer across a cut belongs to no sketch"""
+    from workloads import synth
+    nt, _ = sketch_geometry(s)
+    lengths = sketch_slice_lengths(k, SKETCH_TILE[nt])
+    off = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lengths, dtype=np.uint64)
+    bases = synth.synthetic_genome(50 + k, int(off[-1])).copy()
+    for i in (8, 12, 14):                                   # inside the slices of T, T + k and 4 T + k bytes
+        bases[int(off[i]) + lengths[i] // 3] = ord("N")
+    return {"k": k, "s": s}, bases, off
+
+
+# ---- 6. the two-level merge
+
+SKETCH_MERGE_CASES = {256: {"k": 21, "s": 1000}, 1024: {"k": 21, "s": 3000}}
+
+
+def sketch_case_merge(nt):
+    """(kw, bases, off, names) for chunks of one tile (SKETCH_ONE_TILE): sketches of exactly 64 chunks (one level), of 65 (groups of
+    32, 32 and 1; the last chunk is one k-mer start), of 72 (a ragged last group), 72 chunks of a 700-base unit repeated (seeded,
+    short, run again through both levels) and an ordinary one of 60 kbp"""
+    from workloads import synth
+    kw = dict(SKETCH_MERGE_CASES[nt])
+    k, tile = kw["k"], SKETCH_TILE[nt]
+    rng = np.random.default_rng(8600 + nt)
+    unit = synth._rand_dna(rng, 700)
+    blobs = {"c64": synth._rand_dna(rng, 64 * tile + k - 1), "c65": synth._rand_dna(rng, 64 * tile + k),
+             "c72": synth._rand_dna(rng, 71 * tile + 5000 + k - 1), "repeat": (unit * (72 * tile // 700 + 1))[: 72 * tile],
+             "plain": synth._rand_dna(rng, 60000)}
+    bases, off = sketch_batch(list(blobs.values()))
+    return kw, bases, off, list(blobs)
+
+
+def sketch_case_merge_reads(nt=256):
+    """(kw, reads): the 72-chunk genome of sketch_case_merge as reads of 5 000 bases that begin every 2 500: every base but the
+    first and the last 2 500 is covered twice (min_copies = 2).  (In the order of the genome: the oracle's set of hashes seen once
+    stays small, it is a sorted array.)"""
+    kw, bases, off, names = sketch_case_merge(nt)
+    i = names.index("c72")
+    g = bases[int(off[i]): int(off[i + 1])].tobytes()
+    return dict(kw, min_copies=2), [g[o:o + 5000] for o in range(0, len(g) - 2500, 2500)]
+
+
+def sketch_case_genome():
+    """(kw, record): a lone genome of 5 Mbp at the default plan, k = 21, s = 1 000 -- what `mash sketch` of one bacterial genome is"""
+    from workloads import synth
+    return {"k": 21, "s": 1000}, synth.synthetic_genome(77, 5_000_000).tobytes()

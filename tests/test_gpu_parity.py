@@ -231,9 +231,8 @@ def test_sketch_target_coverage_early_stop(eng, oracle, k, s, m):
     oh, oc, _, _, _ = oracle.sketch_reads(reads, oracle.params(k=k, s=s, min_copies=m))
     assert np.array_equal(h0, oh) and np.array_equal(c0, oc)
     for per in ((len(reads) + 6) // 7, 211):
-        # (MASHGPU_TEST_READS_RESET=1: the second time through a session that has seen another read set and was emptied by
-        #  mg_reads_reset -- no trace of it; opt-in until that call has run on the GPU)
-        first = reads[::-1][:500] if per == 211 and os.environ.get("MASHGPU_TEST_READS_RESET") else None
+        # (the second time through a session that has seen another read set and was emptied by mg_reads_reset -- no trace of it)
+        first = reads[::-1][:500] if per == 211 else None
         ch, cc, cu, fed = eng.sketch_reads_chunked(reads, eng.params(k=k, s=s, min_copies=m), per, first=first)
         assert fed == (len(reads) + per - 1) // per and cu == long_enough, (k, s, m, per)
         assert np.array_equal(ch, h0) and np.array_equal(cc, c0), (k, s, m, per)
