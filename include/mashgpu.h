@@ -478,6 +478,33 @@ int mg_cluster_tri_nearest_host(mg_ctx *ctx, const mg_table *t, int kmer_size, d
 int mg_cluster_tri_nearest_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
                                double max_p_value, uint32_t *rep_out_dev /* [rows] */, uint64_t *n_clusters_out,
                                uint64_t *n_edges_out);
+/* The single-linkage clusters of mg_cluster_tri_host with each cluster's MEDOID, scored ON THE DEVICE (cluster_medoid.hip) -- `mash
+ * cluster -M`.  Everything is exact, no float takes part, and nothing depends on execution order, route or blocking.  With the
+ * edges of mg_cluster_tri_host (the pairs mg_compare_tri_results_host returns under the same max_distance / max_p_value) and
+ * their counts numer/denom (column 5 of `mash triangle -E`):
+ *   weight(e)  : floor(numer * 2^32 / max(denom, 1)) as a 64-bit integer -- at most 2^32, because numer <= denom; 0/0 counts as 0/1,
+ *                as the order of mg_cluster_tri_forest_host's edges has it;
+ *   score[i]   : the sum of weight(e) over all edges with an end at i.  The other end is always in i's cluster; a pair of the
+ *                cluster that is not an edge contributes 0.  With fewer than 2^31 rows score < 2^63, and integer addition commutes:
+ *                the sum is a function of the edge set alone;
+ *   label[i], n_clusters, n_edges : exactly mg_cluster_tri_host's;
+ *   medoid[i]  : among the rows of i's cluster, the one with the largest score; equal scores go to the smallest row.  A row
+ *                without an edge is its own medoid, with score 0.
+ * Where all sketches are full (denom = s everywhere) the medoid is the member with the largest mean Jaccard estimate to the rest
+ * of its cluster; the 2^32 fixed point only makes mixed denominators summable in integers.
+ * score_out may be NULL.  Errors and limits are those of mg_cluster_tri_host: the whole table only, one device, at most 2^31 - 1
+ * rows; both filters disabled: MG_ERR_INVALID; a table without lengths: MG_ERR_INVALID; a table of 0 or 1 rows: MG_OK.  Only rows x
+ * 8 (with the scores: 16) bytes cross PCIe; _dev leaves the three arrays on the device.  MASHGPU_CLUSTER_BLOCK_PAIRS and
+ * MASHGPU_RESULTS_MATRIX as for mg_cluster_tri_host; the context option MASHGPU_MEDOID_PLAIN sends two atomic adds per edge to
+ * memory instead of combining a row's weights in the wave first (an A/B knob: the results are the same bits).
+ * There is no extending form: the weights of the edges between two old rows are not among the pairs mg_cluster_extend_host
+ * compares, so an old row's score cannot be had from the new pairs. */
+int mg_cluster_tri_medoid_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                               double max_p_value, uint32_t *label_out_host /* [rows] */, uint32_t *medoid_out_host /* [rows] */,
+                               uint64_t *score_out_host /* [rows] or NULL */, uint64_t *n_clusters_out, uint64_t *n_edges_out);
+int mg_cluster_tri_medoid_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                              double max_p_value, uint32_t *label_out_dev /* [rows] */, uint32_t *medoid_out_dev /* [rows] */,
+                              uint64_t *score_out_dev /* [rows] or NULL */, uint64_t *n_clusters_out, uint64_t *n_edges_out);
 /* An earlier clustering of `ref` (n rows) extended by the rows of `qry` (m rows), ON THE DEVICE -- `mash cluster -A`.  `cat` is
  * the table whose rows are ref's followed by qry's: new row q has index n + q.  Only the pairs that touch a new row are compared:
  *   new edge   : a pair {n + q, r} that mg_compare_rect_results_host(ctx, ref, qry, 0, m, kmer_size, kmer_space, max_distance,

@@ -33,7 +33,7 @@ EXPORTS = [
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host", "mg_compare_tri_topk_host",
     "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
-    "mg_cluster_tri_nearest_host", "mg_cluster_tri_nearest_dev",
+    "mg_cluster_tri_nearest_host", "mg_cluster_tri_nearest_dev", "mg_cluster_tri_medoid_host", "mg_cluster_tri_medoid_dev",
     "mg_cluster_extend_host", "mg_cluster_extend_greedy_host",
     "mg_cluster_tri_forest_host", "mg_cluster_forest_stats", "mg_cluster_forest_rounds",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
@@ -366,6 +366,8 @@ def load_library():
     lib.mg_cluster_tri_greedy_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_nearest_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_nearest_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_tri_medoid_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp, vp, vp]
+    lib.mg_cluster_tri_medoid_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp, vp, vp]
     lib.mg_cluster_greedy_stats.argtypes = [vp, vp, vp, vp, vp]
     lib.mg_cluster_extend_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_extend_greedy_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
@@ -1045,6 +1047,26 @@ class MashGpu:
         """cluster_tri_nearest_host with rep left on the device at rep_ptr (u32[rows]): (clusters, edges)"""
         nc, ne = C.c_uint64(0), C.c_uint64(0)
         self._check(self.lib.mg_cluster_tri_nearest_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, rep_ptr, C.byref(nc), C.byref(ne)))
+        return int(nc.value), int(ne.value)
+
+    def cluster_tri_medoid_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0, scores=True):
+        """cluster_tri_host's clusters with their medoids: (label u32[rows], medoid u32[rows] = the row of the cluster whose edges'
+        weights floor(numer * 2^32 / max(denom, 1)) sum to the most, equal sums to the smallest row, score u64[rows] = that sum per
+        row (None with scores=False), clusters, edges) (mg_cluster_tri_medoid_host)"""
+        label = np.zeros(table.rows, dtype=np.uint32)
+        medoid = np.zeros(table.rows, dtype=np.uint32)
+        score = np.zeros(table.rows, dtype=np.uint64) if scores else None
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_medoid_host(self.ctx, table.handle, k, kmer_space, max_d, max_p, label.ctypes.data, medoid.ctypes.data,
+                                                        score.ctypes.data if scores else None, C.byref(nc), C.byref(ne)))
+        return label, medoid, score, int(nc.value), int(ne.value)
+
+    def cluster_tri_medoid_dev(self, table, k, kmer_space, label_ptr, medoid_ptr, score_ptr=None, max_d=-1.0, max_p=-1.0):
+        """cluster_tri_medoid_host with the arrays left on the device at label_ptr, medoid_ptr (u32[rows]) and score_ptr (u64[rows],
+        may be None): (clusters, edges)"""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_medoid_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, label_ptr, medoid_ptr, score_ptr,
+                                                       C.byref(nc), C.byref(ne)))
         return int(nc.value), int(ne.value)
 
     def cluster_greedy_stats(self):

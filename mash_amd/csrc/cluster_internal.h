@@ -1,6 +1,7 @@
 // cluster_internal.h — launch interface between host_compare.cpp and cluster.hip (single-linkage clusters of a thresholded triangle),
-// cluster_greedy.hip (greedy representative clusters of the same graph) and cluster_forest.hip (its minimum spanning forest), and the
-// lock-free union-find that cluster.hip and cluster_forest.hip share.
+// cluster_medoid.hip (the same clusters with their medoids), cluster_greedy.hip (greedy representative clusters of the same graph) and
+// cluster_forest.hip (its minimum spanning forest), and the lock-free union-find that cluster.hip, cluster_medoid.hip and
+// cluster_forest.hip share.
 #pragma once
 #include "finish_internal.h"          // (under MG_HIP_EMU that header brings tools/hipemu: tests/test_cluster_emu.py)
 #include <stdint.h>
@@ -56,6 +57,20 @@ hipError_t launch_cluster_union(const FinishArgs &a, uint32_t *parent, uint32_t 
 hipError_t launch_cluster_union(const FinishArgs &a, uint32_t *parent, const PairSpace &sp, hipStream_t stream);
 // label[i] = smallest row of i's cluster, *n_roots = number of clusters.  A launch of its own behind the last union.
 hipError_t launch_cluster_label(uint32_t *parent, uint32_t n, uint32_t *label, unsigned long long *n_roots, hipStream_t stream);
+
+// ---- cluster_medoid.hip
+// launch_cluster_union (the form with a PairSpace) that also scores: every set bit inside sp joins the clusters of its {row, col} AND
+// adds medoid_weight(a.counts[idx]) (forest_key.h) to score[row] and score[col], 64-bit adds.  score[] holds what parent[] holds and
+// lives across the blocks of a call; the caller clears it once, before the first block.  a.counts is read besides what
+// launch_cluster_union reads, at set bits only.  Bits that are clear, behind a.pairs or outside sp add nothing.  plain: two atomics
+// per edge; otherwise the lanes of a word that hold the same row -- in any order, adjacent or not -- combine in the wave first.  Both
+// leave the same bits.
+hipError_t launch_medoid_union(const FinishArgs &a, uint32_t *parent, unsigned long long *score, const PairSpace &sp, hipStream_t stream,
+                               bool plain = false);
+// Behind launch_cluster_label, on the same stream: medoid[i] = among the rows of label[i]'s cluster the one with the largest score,
+// equal scores to the smallest row (a row without an edge: itself).  best[n] and pick[n] are scratch, cleared here.
+hipError_t launch_medoid_pick(const uint32_t *label, const unsigned long long *score, uint32_t n, unsigned long long *best, uint32_t *pick,
+                              uint32_t *medoid, hipStream_t stream);
 
 // ---- cluster_greedy.hip
 // Every set bit of a.masks (as launch_cluster_union reads them) is appended as {x = larger, y = smaller index} at

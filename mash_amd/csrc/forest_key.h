@@ -28,6 +28,14 @@ MG_FOREST_HD unsigned long long forest_key(uint32_t numer, uint32_t denom)
     return ((unsigned long long)numer << 42) / (denom ? denom : 1u);
 }
 
+// THE WEIGHT of an edge in a row's centrality score (`mash cluster -M`, cluster_medoid.hip): floor(numer * 2^32 / max(denom, 1)), at most
+// 2^32 because numer <= denom; 0/0 counts as 0/1 as above.  A fixed point only so that fractions under different denominators can be
+// summed in integers: fewer than 2^31 edges at a row keep the sum below 2^63.
+MG_FOREST_HD unsigned long long medoid_weight(uint32_t numer, uint32_t denom)
+{
+    return ((unsigned long long)numer << 32) / (denom ? denom : 1u);
+}
+
 // the row pair as one word: ascending {row, col} is ascending rc
 MG_FOREST_HD unsigned long long forest_rc(uint32_t row, uint32_t col) { return (unsigned long long)row << 32 | col; }
 

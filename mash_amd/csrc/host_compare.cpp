@@ -2396,6 +2396,103 @@ int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kme
 }
 
 
+/* ------------------------------------------------- the same clusters with their medoids (cluster_medoid.hip) */
+
+// cluster_tri with a score beside the union: `parent` and `score` live across the blocks, score is cleared once before the first
+// of them, every block's set bits unite and add their weights in one launch (launch_medoid_union), then the labels and, behind them
+// on the same stream, the pick.  One wait, at the end.  score_out may be NULL.  MASHGPU_MEDOID_PLAIN: two atomics per edge (the A/B
+// of tools/cluster_medoid_bench.py; the bits are the same).
+static int cluster_medoid_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, uint32_t *medoid_out, uint64_t *score_out,
+                              bool on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    *n_clusters_out = 0;
+    *n_edges_out = 0;
+    OutRange R;
+    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
+    if (rc != MG_OK || R.empty()) return rc;
+    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
+    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
+    const uint32_t n = (uint32_t)t->n;
+    const bool plain = ctx_opt(ctx, "MASHGPU_MEDOID_PLAIN") != nullptr;
+    DevBuf<uint32_t> parent(ctx), label(ctx), medoid(ctx), pick(ctx);
+    DevBuf<unsigned long long> score(ctx), best(ctx);
+    DevBuf<unsigned long long> d_n(ctx);                      // [0]: the clusters, [1 + b]: pass A's count of block b (the list: block 0)
+    HIP_TRY(ctx, parent.alloc(n));
+    HIP_TRY(ctx, pick.alloc(n));
+    HIP_TRY(ctx, best.alloc(n));
+    if (!on_device) {
+        HIP_TRY(ctx, label.alloc(n));
+        HIP_TRY(ctx, medoid.alloc(n));
+    }
+    if (!on_device || !score_out) HIP_TRY(ctx, score.alloc(n));
+    uint32_t *d_label = on_device ? label_out : label.p, *d_medoid = on_device ? medoid_out : medoid.p;
+    unsigned long long *d_score = on_device && score_out ? (unsigned long long *)score_out : score.p;
+    HIP_TRY(ctx, mg::launch_cluster_init(parent, n, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_score, 0, (size_t)n * 8, ctx->stream));
+    CutBufs bufs(ctx, ctx);
+    PassABufs pa(ctx);
+    uint64_t nblocks = 0;
+    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
+                    [&](uint64_t pairs, uint64_t, uint64_t blocks, bool lists) -> int {
+        if (!pa.alloc(pairs, R.s) || d_n.alloc(1 + blocks) != hipSuccess) return kAllocFailed;
+        if (lists) return MG_OK;                              // (the flags are cleared once the list's tables stand: below)
+        HIP_TRY(ctx, hipMemsetAsync(d_n, 0, (1 + blocks) * 8, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+        return MG_OK;
+    },
+                    [&] { pa.release(); },
+                    [&](mg::FinishArgs f, const RowBlock &, const CandLists *L) -> int {
+        if (L) HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
+        pa.bind(f);
+        HIP_TRY(ctx, mg::launch_finish_mark(f, d_n + ++nblocks, ctx->stream));
+        HIP_TRY(ctx, mg::launch_medoid_union(f, parent, d_score, mg::PairSpace{n, n, 0u, 0u}, ctx->stream, plain));
+        return MG_OK;
+    });
+    if (rc != MG_OK) return rc;
+    if (!nblocks) HIP_TRY(ctx, d_n.alloc(1));                 // (one row, or no candidates)
+    std::vector<unsigned long long> h(1 + nblocks);
+    HIP_TRY(ctx, mg::launch_cluster_label(parent, n, d_label, d_n, ctx->stream));
+    HIP_TRY(ctx, mg::launch_medoid_pick(d_label, d_score, n, best, pick, d_medoid, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_n, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!on_device) {
+        HIP_TRY(ctx, hipMemcpyAsync(label_out, d_label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(medoid_out, d_medoid, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (score_out) HIP_TRY(ctx, hipMemcpyAsync(score_out, d_score, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (bufs and pa are released behind this wait)
+    *n_clusters_out = h[0];
+    for (uint64_t b = 0; b < nblocks; b++) *n_edges_out += h[1 + b];
+    return MG_OK;
+}
+
+static int cluster_medoid_entry(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, uint32_t *medoid_out, uint64_t *score_out,
+                                bool on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out, const char *who)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!t || !n_clusters_out || !n_edges_out || ((!label_out || !medoid_out) && t->n)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
+    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
+    return cluster_medoid_tri(ctx, t, cut, label_out, medoid_out, score_out, on_device, n_clusters_out, n_edges_out);
+}
+
+int mg_cluster_tri_medoid_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                               uint32_t *label_out_host, uint32_t *medoid_out_host, uint64_t *score_out_host, uint64_t *n_clusters_out,
+                               uint64_t *n_edges_out)
+{
+    return cluster_medoid_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_host, medoid_out_host, score_out_host, false,
+                                n_clusters_out, n_edges_out, "mg_cluster_tri_medoid_host");
+}
+
+int mg_cluster_tri_medoid_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                              uint32_t *label_out_dev, uint32_t *medoid_out_dev, uint64_t *score_out_dev, uint64_t *n_clusters_out,
+                              uint64_t *n_edges_out)
+{
+    return cluster_medoid_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_dev, medoid_out_dev, score_out_dev, true,
+                                n_clusters_out, n_edges_out, "mg_cluster_tri_medoid_dev");
+}
+
+
 /* ------------------------------------------------- greedy representative clusters of the thresholded triangle (cluster_greedy.hip) */
 
 // The edge list of one call: grown on demand, the pairs of every block appended behind those of the blocks before it.  E: an edge as

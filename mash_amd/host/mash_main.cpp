@@ -1771,6 +1771,9 @@ int cmd_triangle(int argc, const char **argv)
 // Lines and numbering are the same (the label is the representative); the host route runs that walk here.
 // -B: -R's representatives, every other sketch under its NEAREST one (mg_cluster_tri_nearest_host): the representative, earlier or
 // later in the input, with which it shares the larger fraction of hashes, exactly (mg::forest_before); a fourth field names it.
+// -M: the single-linkage clusters, each line with a fourth field naming the cluster's MEDOID (mg_cluster_tri_medoid_host): the member
+// whose edges' weights floor(numer * 2^32 / max(denom, 1)) sum to the most, equal sums to the earlier member.  Numbers, sizes and
+// the first three fields are those of the run without -M.  The host route sums and picks here, from the edges it fetches anyway.
 // -T: the minimum spanning forest of the same pairs instead (cluster_forest below): edge-list lines, not cluster lines.
 // -A <earlier output>: the clusters of the first L inputs are read from an earlier run's stdout and only the pairs that touch a
 // later input are compared (cluster_extend below; include/mashgpu.h: mg_cluster_extend_host).
@@ -1949,6 +1952,7 @@ int cmd_cluster(int argc, const char **argv)
     c.add("best", Opt::Boolean, "B");
     c.add("tree", Opt::Boolean, "T");
     c.add("assign", Opt::File, "A");
+    c.add("medoid", Opt::Boolean, "M");
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "0.05", 0., 1.);
     c.use_sketch_options();
@@ -1980,12 +1984,27 @@ int cmd_cluster(int argc, const char **argv)
                 "            cluster -R`, then give -R again) over the FIRST inputs, one line each; the IDs must match.  Only\n"
                 "            pairs with one of the later inputs are compared.  All inputs are listed; if <file> was made\n"
                 "            with the same -R, -d and -v, the output is that of the run without -A, and it can be given\n"
-                "            to the next -A.  The mode and thresholds behind <file> are not checked.  Not with -T.\n\n";
+                "            to the next -A.  The mode and thresholds behind <file> are not checked.  Not with -T.\n"
+                "  -M        The single-linkage clusters with each cluster's medoid: output gets a fourth field,\n"
+                "            [cluster-number, cluster-size, ID, medoid-ID]; the first three fields are those of the run\n"
+                "            without -M.  An edge weighs floor(shared * 2^32 / max(denominator, 1)) with shared/denominator\n"
+                "            the shared-hashes of its `mash triangle -E` line, a sketch's score is the sum over its edges (a\n"
+                "            pair of the cluster that is no edge counts 0), and the medoid is the member with the largest\n"
+                "            score, equal scores to the earlier member: with full sketches, the member with the largest mean\n"
+                "            Jaccard estimate to the rest of its cluster.  Exact integers throughout.  Not with -R, -B, -T\n"
+                "            or -A (the weights between earlier inputs are not among the pairs -A compares).\n\n";
         return 0;
     }
     const bool comment = c.o("comment").active, nearest = c.o("best").active, greedy = c.o("representatives").active || nearest;
     const bool forest = c.o("tree").active, extend = c.o("assign").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
+    const bool medoid = c.o("medoid").active;
+    for (const char *other : {"representatives", "best", "tree", "assign"}) {
+        if (!medoid || !c.o(other).active) continue;
+        cerr << "ERROR: -" << c.o("medoid").id << " and -" << c.o(other).id << " cannot be given together"
+             << (string(other) == "assign" ? " (the weights between earlier inputs are not among the pairs -A compares)." : ".") << endl;
+        return 1;
+    }
     if (nearest && forest) {
         cerr << "ERROR: -" << c.o("best").id << " and -" << c.o("tree").id << " cannot be given together." << endl;
         return 1;
@@ -2041,9 +2060,14 @@ int cmd_cluster(int argc, const char **argv)
     mg_table *t = extend ? nullptr : mg_dtable_local(dt.get(), 0);                        // (several devices selected: the first one's replica)
     const double kspace = set.kmer_space();
     StageClock clk;
-    vector<uint32_t> lab(n);
+    vector<uint32_t> lab(n), med(medoid ? n : 0);
     if (extend) {
         if (cluster_extend(gpu, set, old, greedy, d_max, p_max, clk, lab)) return 1;
+    } else if (medoid && !host_finish_wanted()) {
+        uint64_t n_clusters = 0, n_edges = 0;
+        if (mg_cluster_tri_medoid_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), med.data(), nullptr, &n_clusters, &n_edges) != MG_OK)
+            return report_error(gpu);
+        clk.lap("compare+mark+union+score+label+pick+copy");
     } else if (!host_finish_wanted()) {
         uint64_t n_clusters = 0, n_edges = 0;
         const int rc = nearest  ? mg_cluster_tri_nearest_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
@@ -2057,6 +2081,7 @@ int cmd_cluster(int argc, const char **argv)
         vector<mg_edge> edges;
         vector<vector<uint32_t>> smaller(greedy ? n : 0);      // -R: per sketch its neighbours with a smaller index
         vector<mg_edge> kept;                                  // -B: every edge with its counts
+        vector<uint64_t> score(medoid ? n : 0);                // -M: per sketch the sum of its edges' weights
         for (Blocks b(1, n, kTriFilteredPairs); b.next();) {
             if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
                     return mg_compare_tri_filter_host(gpu.ctx, t, b.r0, b.r1, set.p.kmer, d_max, o, cap, cnt); }))
@@ -2071,6 +2096,11 @@ int cmd_cluster(int argc, const char **argv)
                 }
                 const uint32_t a = find(e.row), b2 = find(e.col);
                 if (a != b2) lab[std::max(a, b2)] = std::min(a, b2);
+                if (medoid) {
+                    const uint64_t wt = mg::medoid_weight(e.numer, e.denom);
+                    score[e.row] += wt;
+                    score[e.col] += wt;
+                }
             }
         }
         if (greedy) {
@@ -2096,8 +2126,16 @@ int cmd_cluster(int argc, const char **argv)
             }
         } else {
             for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
+            if (medoid) {
+                // per cluster the largest score, met first at its smallest row: the walk is in index order and only a larger score moves it
+                vector<uint32_t> top(n);
+                for (uint64_t i = 0; i < n; i++) top[i] = (uint32_t)i;
+                for (uint64_t i = 0; i < n; i++)
+                    if (score[i] > score[top[lab[i]]]) top[lab[i]] = (uint32_t)i;
+                for (uint64_t i = 0; i < n; i++) med[i] = top[lab[i]];
+            }
         }
-        clk.lap(nearest ? "compare+filter+copy+walk+nearest" : greedy ? "compare+filter+copy+walk" : "compare+filter+copy+union");
+        clk.lap(medoid ? "compare+filter+copy+union+score+pick" : nearest ? "compare+filter+copy+walk+nearest" : greedy ? "compare+filter+copy+walk" : "compare+filter+copy+union");
     }
     // label = the cluster's first member: numbers in order of first appearance are numbers by ascending label
     vector<uint32_t> number(n, 0), size(n, 0);
@@ -2110,6 +2148,7 @@ int cmd_cluster(int argc, const char **argv)
     for (uint64_t i = 0; i < n; i++) {
         out << number[lab[i]] << '\t' << size[lab[i]] << '\t' << (comment ? set.refs[i].comment : set.refs[i].name);
         if (nearest) out << '\t' << (comment ? set.refs[lab[i]].comment : set.refs[lab[i]].name);
+        if (medoid) out << '\t' << (comment ? set.refs[med[i]].comment : set.refs[med[i]].name);
         out.eol();
     }
     clk.lap("format+write");
@@ -2654,7 +2693,7 @@ int main(int argc, const char **argv)
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
         "  dist      Estimate the distance of query sequences to references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n"
-        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), extend an earlier clustering by new sequences (-A), or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
+        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), name each single-linkage cluster's medoid (-M), extend an earlier clustering by new sequences (-A), or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"
