@@ -1,4 +1,4 @@
-// cluster_internal.h — launch interface between host_compare.cpp and cluster.hip (single-linkage clusters of a thresholded triangle),
+// cluster_internal.h — launch interface between host_cluster.cpp and cluster.hip (single-linkage clusters of a thresholded triangle),
 // cluster_medoid.hip (the same clusters with their medoids), cluster_greedy.hip (greedy representative clusters of the same graph) and
 // cluster_forest.hip (its minimum spanning forest), and the lock-free union-find that cluster.hip, cluster_medoid.hip and
 // cluster_forest.hip share.

@@ -1,5 +1,5 @@
 // host_compare.cpp -- the compare entry points: tile engine, inverted-index engine, finishing, thresholded and list outputs
-#include "host_internal.h"
+#include "cut_internal.h"
 #include "index_build.h"
 #ifdef IX_PHASE_CLOCKS
 namespace mg { void index_dump_clocks(); }
@@ -1496,18 +1496,8 @@ int mg_compare_rect_dev(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, u
 
 /* ------------------------------------------------- host outputs: range set-up, row blocks */
 
-// What every host-output call starts from: [rb, re) clamped to the rows, the view a triangle of one table is served from
-// (tri_view: the first re rows are all such a call looks at), s, and the pairs of the range.
-struct OutRange {
-    const mg_table *rows, *cols;
-    uint64_t rb, re, pairs;
-    uint32_t s;
-    bool triangle;
-    bool empty() const { return rb >= re; }
-};
-
-static int out_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle, OutRange *o,
-                     uint64_t max_s = 0xFFFFFFFEull)
+int out_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re, bool triangle, OutRange *o,
+              uint64_t max_s)
 {
     *o = {rows, cols, rb, std::min(re, rows->n), 0, 0, triangle};
     if (o->empty()) return MG_OK;
@@ -1520,8 +1510,6 @@ static int out_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, ui
     return MG_OK;
 }
 
-// rows [r, r2): `pairs` pairs, `before` pairs of the range ahead of them
-struct RowBlock { uint64_t r, r2, pairs, before; };
 
 // The range in blocks of whole rows of at most max_pairs pairs (a block always takes its first row); *largest: the pairs of the
 // largest block, which the caller's device buffers hold
@@ -1544,13 +1532,6 @@ static std::vector<RowBlock> row_blocks(const OutRange &R, uint64_t max_pairs, u
     }
     return v;
 }
-
-// How a caller has its matrix cut: row blocks of at most `pairs` pairs -- or of what the option `knob` says (the tests' way to many
-// blocks): below `pairs`, or up to `ceiling` where a caller sets one -- and the caller's name in the allocation error
-struct Blocks { uint64_t pairs; const char *knob, *who; uint64_t ceiling = 0; };
-
-// what a caller's allocation callback answers when the device has no room: its driver words the error
-static const int kAllocFailed = -1001;
 
 // The matrix of R, row block by row block, through `counts` (the caller's: its owner decides where a block's memory comes from, and
 // the caller decides how long it lives): the counts of the largest block and -- alloc(largest pairs, most rows of a block, blocks) --
@@ -1811,25 +1792,7 @@ int mg_compare_rect_filter_host(mg_ctx *ctx, const mg_table *ref, const mg_table
 
 static_assert(sizeof(mg_pair) == sizeof(mg::FinishPair) && sizeof(mg_result) == sizeof(mg::FinishEdge), "ABI structs");
 
-// What a finish is given: k and the k-mer space of the distance and p-value formulas, and the two thresholds.  A threshold
-// is on when it lies in [0, 1): one of 1 or more lets every pair through, a negative one means none was asked for.
-struct Cut {
-    int k;
-    double kspace, max_d, max_p;
-    bool d_on() const { return max_d >= 0.0 && max_d < 1.0; }
-    bool filtered() const { return d_on() || (max_p >= 0.0 && max_p < 1.0); }
-};
-
-// What the device finish needs besides the counts: the distance table (host libm, one row per
-// denominator flagged in `seen`, row s always) and the integer form of the distance filter.
-struct FinishTables {
-    DevBuf<uint32_t> d_start, d_min;
-    DevBuf<double> d_lut;
-    bool complete = true;                   // false: some flagged denominator did not fit the budget (device yields NaN)
-    explicit FinishTables(mg_ctx *c) : d_start(c), d_min(c), d_lut(c) {}
-};
-
-static int build_finish_tables(mg_ctx *ctx, uint32_t s, const Cut &cut, const std::vector<uint32_t> &seen, FinishTables &ft)
+int build_finish_tables(mg_ctx *ctx, uint32_t s, const Cut &cut, const std::vector<uint32_t> &seen, FinishTables &ft)
 {
     const int k = cut.k;
     const uint64_t budget = 1ull << 26;                       // doubles (512 MiB): every denominator up to s = 11 583
@@ -1860,8 +1823,8 @@ static int build_finish_tables(mg_ctx *ctx, uint32_t s, const Cut &cut, const st
 
 // The FinishArgs fields every device finish fills: `pairs` counts from row first_row on, the tables' lengths, the distance
 // table and filters of `ft`
-static mg::FinishArgs finish_args(const mg_table *rows, const mg_table *cols, uint32_t s, bool triangle, const void *counts, uint64_t pairs,
-                                  uint64_t first_row, const FinishTables &ft, const Cut &cut)
+mg::FinishArgs finish_args(const mg_table *rows, const mg_table *cols, uint32_t s, bool triangle, const void *counts, uint64_t pairs,
+                           uint64_t first_row, const FinishTables &ft, const Cut &cut)
 {
     mg::FinishArgs a{};
     a.counts = reinterpret_cast<const uint2 *>(counts);
@@ -2025,16 +1988,6 @@ static int job_lists(mg_ctx *ctx, const SparseJob &job, uint32_t nrows, uint32_t
     return MG_OK;
 }
 
-struct CandLists {
-    uint64_t K = 0;
-    DevBuf<uint2> rc, cnt;
-    DevBuf<uint32_t> byrow, base;
-    DevBuf<unsigned char> temp;
-    size_t tb = 0;
-    explicit CandLists(mg_ctx *c) : rc(c), cnt(c), byrow(c), base(c), temp(c) {}
-    void release() { rc.free(); cnt.free(); byrow.free(); base.free(); temp.free(); }
-};
-
 // The inverted-index engine's job over R as lists (job_lists) instead of a matrix.  *ok false: no lists -- the engine is forced
 // off or leaves the job to the matrix (copies of rows, empty rows, nearly every pair related), or the lists do not fit: 2^32
 // entries and more, or scratch the device cannot give.  That is no error: the caller's own fallback does the job.
@@ -2063,47 +2016,10 @@ static int cand_lists(mg_ctx *ctx, const OutRange &R, CandLists &L, bool *ok, Ex
     return job_lists(ctx, job, nrows, R.triangle ? 0u : (uint32_t)R.rb, R.s, L.byrow, L.base, L.temp, L.tb, L.rc, L.cnt);
 }
 
-// Pass A of a finish (finish_mark_kernel) over up to `pairs` entries: its ballots and segments, the denominators it flags
-struct PassABufs {
-    DevBuf<unsigned long long> masks, seg_off;
-    DevBuf<uint32_t> seg_count, seen;
-    explicit PassABufs(mg_ctx *owner) : masks(owner), seg_off(owner), seg_count(owner), seen(owner) {}
-    bool alloc(uint64_t pairs, uint32_t s)
-    {
-        return masks.alloc(mg::finish_mask_words(pairs)) == hipSuccess && seg_count.alloc(mg::finish_segments(pairs)) == hipSuccess &&
-               seg_off.alloc(mg::finish_segments(pairs)) == hipSuccess && seen.alloc((uint64_t)s + 1) == hipSuccess;
-    }
-    void release() { masks.free(); seg_off.free(); seg_count.free(); seen.free(); }
-    void bind(mg::FinishArgs &f) const
-    {
-        f.masks = masks;
-        f.seg_count = seg_count;
-        f.seg_off = seg_off;
-        f.denom_seen = seen;
-    }
-};
-
-// What a thresholded call keeps on the device for as long as it runs, whichever route serves it: the candidate lists, the finish
-// tables of pass A, the counts of a matrix block (their owner is the caller's choice)
-struct CutBufs {
-    CandLists L;
-    FinishTables fa;
-    DevBuf<mg_counts> counts;
-    CutBufs(mg_ctx *ctx, mg_ctx *counts_owner) : L(ctx), fa(ctx), counts(counts_owner) {}
-};
-
-// The counts of R for a consumer that thresholds them (survivors, unions, edges, the nearest k), by one of two routes:
-//  * lists, if asked for and the index engine gives them (cand_lists): a filter is on, so only pairs that share a hash can pass
-//    (numer = 0 means distance 1 and p-value 1), and those are the engine's candidates -- no matrix is filled, no 8 B per pair read
-//    back.  use() is called once, f over the list (f.list_rc) and L the lists, b the whole range -- or not at all: no candidates.
-//  * the matrix in row blocks (matrix_blocks) otherwise: use() is called per block, L == nullptr.
-// f carries pass A's tables (no extra denominator row), built once: behind the first compare, for building waits.
-// alloc(pairs, rows, blocks, lists) allocates the consumer's buffers for the list or the largest block and answers as matrix_blocks'
-// callback does; on the lists route anything but MG_OK only means no lists.  Lists that fall through leave nothing behind on the
-// device -- the fallback is there for the device that is short of memory --: give_back() frees what alloc(.., true) took.
-template <class Alloc, class GiveBack, class Use>
-static int cut_counts(mg_ctx *ctx, const OutRange &R, const Cut &cut, bool try_lists, const Blocks &how, CutBufs &B, Alloc alloc, GiveBack give_back,
-                      Use use)
+// The counts of R for a consumer that thresholds them (cut_internal.h says what the callbacks are given), by one of two routes: the
+// lists (cand_lists), or the matrix in row blocks (matrix_blocks: alloc answers as its callback does)
+int cut_counts(mg_ctx *ctx, const OutRange &R, const Cut &cut, bool try_lists, const Blocks &how, CutBufs &B, const CutAlloc &alloc,
+               const std::function<void()> &give_back, const CutUse &use)
 {
     if (!R.pairs) return MG_OK;
     int rc = MG_OK;
@@ -2127,7 +2043,7 @@ static int cut_counts(mg_ctx *ctx, const OutRange &R, const Cut &cut, bool try_l
 }
 
 // a denominator beyond the distance table's budget left NaN distances (FinishTables::complete): those are computed here
-static void patch_nan_distances(mg_result *r, uint64_t n, int k)
+void patch_nan_distances(mg_result *r, uint64_t n, int k)
 {
     for (uint64_t i = 0; i < n; i++)
         if (r[i].distance != r[i].distance) r[i].distance = mg::mash_distance(r[i].numer, r[i].denom, k);
@@ -2310,687 +2226,6 @@ int mg_compare_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_tabl
     if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
         return fail(ctx, MG_ERR_INVALID, "mg_compare_rect_results_host: the tables carry no lengths");
     return compare_results(ctx, qry, ref, q_begin, q_end, false, Cut{kmer_size, kmer_space, max_distance, max_p_value}, out_host, capacity, count_out);
-}
-
-
-/* ------------------------------------------------- single-linkage clusters of the thresholded triangle (cluster.hip) */
-
-// The whole triangle of t: pass A over its thresholded counts (cut_counts) -- the candidate list, or block after block of the matrix --
-// and the union of every pair it marks into `parent`, which lives across the blocks; then one label launch.  No pass B, no distance
-// table, no record, and no wait before finish's: pass A's counts stay on the device until then.
-static int cluster_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out,
-                       uint64_t *n_edges_out)
-{
-    *n_clusters_out = 0;
-    *n_edges_out = 0;
-    OutRange R;
-    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
-    if (rc != MG_OK || R.empty()) return rc;
-    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
-    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
-    const uint32_t n = (uint32_t)t->n;
-    DevBuf<uint32_t> parent(ctx), label(ctx);
-    DevBuf<unsigned long long> d_n(ctx);                      // [0]: the clusters, [1 + b]: pass A's count of block b (the list: block 0)
-    HIP_TRY(ctx, parent.alloc(n));
-    if (!label_on_device) HIP_TRY(ctx, label.alloc(n));
-    uint32_t *d_label = label_on_device ? label_out : label.p;
-    HIP_TRY(ctx, mg::launch_cluster_init(parent, n, ctx->stream));
-    CutBufs bufs(ctx, ctx);
-    PassABufs pa(ctx);
-    uint64_t nblocks = 0;
-    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
-                    [&](uint64_t pairs, uint64_t, uint64_t blocks, bool lists) -> int {
-        if (!pa.alloc(pairs, R.s) || d_n.alloc(1 + blocks) != hipSuccess) return kAllocFailed;
-        if (lists) return MG_OK;                              // (the flags are cleared once the list's tables stand: below)
-        HIP_TRY(ctx, hipMemsetAsync(d_n, 0, (1 + blocks) * 8, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-        return MG_OK;
-    },
-                    [&] { pa.release(); },
-                    [&](mg::FinishArgs f, const RowBlock &, const CandLists *L) -> int {
-        if (L) HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-        pa.bind(f);
-        HIP_TRY(ctx, mg::launch_finish_mark(f, d_n + ++nblocks, ctx->stream));
-        HIP_TRY(ctx, mg::launch_cluster_union(f, parent, n, ctx->stream));
-        return MG_OK;
-    });
-    if (rc != MG_OK) return rc;
-    if (!nblocks) HIP_TRY(ctx, d_n.alloc(1));                 // (one row, or no candidates)
-    // the labels, the roots' number and pass A's counts, behind every union queued so far
-    std::vector<unsigned long long> h(1 + nblocks);
-    HIP_TRY(ctx, mg::launch_cluster_label(parent, n, d_label, d_n, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_n, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (!label_on_device) HIP_TRY(ctx, hipMemcpyAsync(label_out, d_label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (bufs and pa are released behind this wait)
-    *n_clusters_out = h[0];
-    for (uint64_t b = 0; b < nblocks; b++) *n_edges_out += h[1 + b];
-    return MG_OK;
-}
-
-static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
-                              uint64_t *n_edges_out);
-static int cluster_nearest_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
-                               uint64_t *n_edges_out);
-
-static int cluster_entry(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, bool label_on_device, uint64_t *n_clusters_out,
-                         uint64_t *n_edges_out, const char *who, bool greedy = false, bool nearest = false)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!t || !n_clusters_out || !n_edges_out || (!label_out && t->n)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
-    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
-    return (nearest ? cluster_nearest_tri : greedy ? cluster_greedy_tri : cluster_tri)(ctx, t, cut, label_out, label_on_device, n_clusters_out, n_edges_out);
-}
-
-int mg_cluster_tri_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                        uint32_t *label_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_host, false, n_clusters_out, n_edges_out, "mg_cluster_tri_host");
-}
-
-int mg_cluster_tri_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                       uint32_t *label_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_dev, true, n_clusters_out, n_edges_out, "mg_cluster_tri_dev");
-}
-
-
-/* ------------------------------------------------- the same clusters with their medoids (cluster_medoid.hip) */
-
-// cluster_tri with a score beside the union: `parent` and `score` live across the blocks, score is cleared once before the first
-// of them, every block's set bits unite and add their weights in one launch (launch_medoid_union), then the labels and, behind them
-// on the same stream, the pick.  One wait, at the end.  score_out may be NULL.  MASHGPU_MEDOID_PLAIN: two atomics per edge (the A/B
-// of tools/cluster_medoid_bench.py; the bits are the same).
-static int cluster_medoid_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, uint32_t *medoid_out, uint64_t *score_out,
-                              bool on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    *n_clusters_out = 0;
-    *n_edges_out = 0;
-    OutRange R;
-    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
-    if (rc != MG_OK || R.empty()) return rc;
-    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
-    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
-    const uint32_t n = (uint32_t)t->n;
-    const bool plain = ctx_opt(ctx, "MASHGPU_MEDOID_PLAIN") != nullptr;
-    DevBuf<uint32_t> parent(ctx), label(ctx), medoid(ctx), pick(ctx);
-    DevBuf<unsigned long long> score(ctx), best(ctx);
-    DevBuf<unsigned long long> d_n(ctx);                      // [0]: the clusters, [1 + b]: pass A's count of block b (the list: block 0)
-    HIP_TRY(ctx, parent.alloc(n));
-    HIP_TRY(ctx, pick.alloc(n));
-    HIP_TRY(ctx, best.alloc(n));
-    if (!on_device) {
-        HIP_TRY(ctx, label.alloc(n));
-        HIP_TRY(ctx, medoid.alloc(n));
-    }
-    if (!on_device || !score_out) HIP_TRY(ctx, score.alloc(n));
-    uint32_t *d_label = on_device ? label_out : label.p, *d_medoid = on_device ? medoid_out : medoid.p;
-    unsigned long long *d_score = on_device && score_out ? (unsigned long long *)score_out : score.p;
-    HIP_TRY(ctx, mg::launch_cluster_init(parent, n, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(d_score, 0, (size_t)n * 8, ctx->stream));
-    CutBufs bufs(ctx, ctx);
-    PassABufs pa(ctx);
-    uint64_t nblocks = 0;
-    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
-                    [&](uint64_t pairs, uint64_t, uint64_t blocks, bool lists) -> int {
-        if (!pa.alloc(pairs, R.s) || d_n.alloc(1 + blocks) != hipSuccess) return kAllocFailed;
-        if (lists) return MG_OK;                              // (the flags are cleared once the list's tables stand: below)
-        HIP_TRY(ctx, hipMemsetAsync(d_n, 0, (1 + blocks) * 8, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-        return MG_OK;
-    },
-                    [&] { pa.release(); },
-                    [&](mg::FinishArgs f, const RowBlock &, const CandLists *L) -> int {
-        if (L) HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-        pa.bind(f);
-        HIP_TRY(ctx, mg::launch_finish_mark(f, d_n + ++nblocks, ctx->stream));
-        HIP_TRY(ctx, mg::launch_medoid_union(f, parent, d_score, mg::PairSpace{n, n, 0u, 0u}, ctx->stream, plain));
-        return MG_OK;
-    });
-    if (rc != MG_OK) return rc;
-    if (!nblocks) HIP_TRY(ctx, d_n.alloc(1));                 // (one row, or no candidates)
-    std::vector<unsigned long long> h(1 + nblocks);
-    HIP_TRY(ctx, mg::launch_cluster_label(parent, n, d_label, d_n, ctx->stream));
-    HIP_TRY(ctx, mg::launch_medoid_pick(d_label, d_score, n, best, pick, d_medoid, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_n, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (!on_device) {
-        HIP_TRY(ctx, hipMemcpyAsync(label_out, d_label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(medoid_out, d_medoid, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (score_out) HIP_TRY(ctx, hipMemcpyAsync(score_out, d_score, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (bufs and pa are released behind this wait)
-    *n_clusters_out = h[0];
-    for (uint64_t b = 0; b < nblocks; b++) *n_edges_out += h[1 + b];
-    return MG_OK;
-}
-
-static int cluster_medoid_entry(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, uint32_t *medoid_out, uint64_t *score_out,
-                                bool on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out, const char *who)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!t || !n_clusters_out || !n_edges_out || ((!label_out || !medoid_out) && t->n)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the table carries no lengths");
-    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
-    return cluster_medoid_tri(ctx, t, cut, label_out, medoid_out, score_out, on_device, n_clusters_out, n_edges_out);
-}
-
-int mg_cluster_tri_medoid_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                               uint32_t *label_out_host, uint32_t *medoid_out_host, uint64_t *score_out_host, uint64_t *n_clusters_out,
-                               uint64_t *n_edges_out)
-{
-    return cluster_medoid_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_host, medoid_out_host, score_out_host, false,
-                                n_clusters_out, n_edges_out, "mg_cluster_tri_medoid_host");
-}
-
-int mg_cluster_tri_medoid_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                              uint32_t *label_out_dev, uint32_t *medoid_out_dev, uint64_t *score_out_dev, uint64_t *n_clusters_out,
-                              uint64_t *n_edges_out)
-{
-    return cluster_medoid_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, label_out_dev, medoid_out_dev, score_out_dev, true,
-                                n_clusters_out, n_edges_out, "mg_cluster_tri_medoid_dev");
-}
-
-
-/* ------------------------------------------------- greedy representative clusters of the thresholded triangle (cluster_greedy.hip) */
-
-// The edge list of one call: grown on demand, the pairs of every block appended behind those of the blocks before it.  E: an edge as
-// Append writes it ({hi, lo} for the greedy rounds, with the pair's counts beside them for the forest)
-template <class E, hipError_t (*Append)(const mg::FinishArgs &, const mg::PairSpace &, E *, uint64_t, unsigned long long *, uint32_t *, hipStream_t)>
-struct EdgeList {
-    mg_ctx *ctx;
-    DevBuf<E> buf;
-    DevBuf<unsigned long long> ctl;                           // [0] cursor, [1] pass A's count of the block, [2] overflow flag (its low word)
-    uint64_t cap = 0, used = 0, n_edges = 0, regrows = 0;
-    explicit EdgeList(mg_ctx *c) : ctx(c), buf(c), ctl(c) {}
-    int init(uint64_t want)
-    {
-        cap = std::max<uint64_t>(want, 1);
-        if (buf.alloc(cap) != hipSuccess || ctl.alloc(3) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(cap * sizeof(E)) + " bytes)");
-        }
-        HIP_TRY(ctx, hipMemsetAsync(ctl, 0, 24, ctx->stream));
-        return MG_OK;
-    }
-    // Pass A over f's counts, its marked pairs appended; waits for the block's figures and, if the
-    // list was too short for them, regrows it (the pairs of earlier blocks copied over) and appends the block again -- pass A's
-    // ballots are still there.  sp: where f's pairs stand in the index space of the list (the whole triangle of n rows: {n, n, 0, 0})
-    int append(mg::FinishArgs f, const PassABufs &b, const mg::PairSpace &sp)
-    {
-        b.bind(f);
-        unsigned long long h[3] = {0, 0, 0};
-        HIP_TRY(ctx, mg::launch_finish_mark(f, ctl + 1, ctx->stream));
-        for (int attempt = 0;; attempt++) {
-            HIP_TRY(ctx, Append(f, sp, buf, cap, ctl, reinterpret_cast<uint32_t *>(ctl + 2), ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(h, ctl, 24, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (h[0] <= cap && !h[2]) break;
-            if (attempt) return fail(ctx, MG_ERR_HIP, "cluster: the edge list overflowed after it was regrown");
-            const uint64_t want = std::max<uint64_t>(h[0], 2 * cap);
-            DevBuf<E> bigger(ctx);
-            if (bigger.alloc(want) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(ctx, MG_ERR_NOMEM, "cluster: no device memory for the edge list (" + std::to_string(want * sizeof(E)) + " bytes for " +
-                                                   std::to_string(h[0]) + " edges so far)");
-            }
-            if (used) HIP_TRY(ctx, hipMemcpyAsync(bigger, buf, used * sizeof(E), hipMemcpyDeviceToDevice, ctx->stream));
-            const unsigned long long back[3] = {used, h[1], 0};
-            HIP_TRY(ctx, hipMemcpyAsync(ctl, back, 24, hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the old list goes back to the pool behind the copy)
-            std::swap(buf.p, bigger.p);
-            cap = want;
-            regrows++;
-        }
-        used = h[0];
-        n_edges += h[1];
-        return MG_OK;
-    }
-};
-using GreedyEdges = EdgeList<uint2, mg::launch_greedy_append>;
-
-// the list with counts (cluster_forest.hip's append): the forest's, and the greedy rounds' when members join their NEAREST representative
-static hipError_t forest_append(const mg::FinishArgs &f, const mg::PairSpace &sp, uint4 *edges, uint64_t cap, unsigned long long *cursor,
-                                uint32_t *overflow, hipStream_t stream)
-{
-    return mg::launch_forest_append(f, sp.rows, edges, cap, cursor, overflow, stream);      // (whole triangles only: no bases)
-}
-using ForestEdges = EdgeList<uint4, forest_append>;
-
-// What follows the last append of a greedy call: the fixpoint over E's edges in batches (one wait per batch: the rows each of its
-// rounds left open), the assignment, the copy.  state[] holds n rows; the first n_old of them are seeded from d_seed
-// (launch_greedy_seed; seeded == false: every row open) and rep_out takes the rows from n_old on.
-// Edges == ForestEdges: the list carries the pairs' counts and the assignment is the nearest representative's (launch_nearest_assign:
-// two more launches in the last batch, no further wait); whole tables only (n_old == 0).
-template <class Edges>
-static int greedy_fixpoint(mg_ctx *ctx, Edges &E, uint32_t n, uint32_t n_old, bool seeded, const uint32_t *d_seed, uint32_t *rep_out,
-                           bool rep_on_device, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    constexpr bool kNearest = std::is_same<Edges, ForestEdges>::value;
-    DevBuf<uint32_t> state(ctx), rep(ctx), left(ctx);
-    DevBuf<unsigned long long> d_n(ctx), best_key(ctx);
-    constexpr uint32_t kBatchMax = 256;
-    if (state.alloc(n) != hipSuccess || left.alloc(kBatchMax) != hipSuccess || d_n.alloc(1) != hipSuccess ||
-        (!rep_on_device && rep.alloc(n - n_old) != hipSuccess) || (kNearest && best_key.alloc(n) != hipSuccess))
-        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
-    uint32_t *d_rep = rep_on_device ? rep_out : rep.p;
-    if (seeded) HIP_TRY(ctx, mg::launch_greedy_seed(state, d_seed, n_old, n, ctx->stream));
-    else HIP_TRY(ctx, hipMemsetAsync(state, 0, (size_t)n * 4, ctx->stream));
-    std::vector<uint32_t> h(kBatchMax);
-    uint64_t rounds = 0, batches = 0;
-    for (uint32_t batch = 8;; batch = std::min(batch * 2, kBatchMax)) {
-        HIP_TRY(ctx, mg::launch_greedy_rounds(E.buf, E.used, state, n, left, batch, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h.data(), left, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        batches++;
-        uint32_t r = 0;
-        while (r < batch && h[r]) r++;
-        rounds += std::min(r + 1, batch);
-        if (r < batch) break;
-        if (rounds > n) return fail(ctx, MG_ERR_HIP, "cluster: the rounds did not reach their fixpoint");      // (at most n are ever needed)
-    }
-    unsigned long long reps = 0;
-    if constexpr (kNearest) HIP_TRY(ctx, mg::launch_nearest_assign(E.buf, E.used, state, n, best_key, d_rep, d_n, ctx->stream));
-    else HIP_TRY(ctx, mg::launch_greedy_assign(E.buf, E.used, state, n, d_rep, d_n, ctx->stream, n_old));
-    HIP_TRY(ctx, hipMemcpyAsync(&reps, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (!rep_on_device && n > n_old) HIP_TRY(ctx, hipMemcpyAsync(rep_out, d_rep, (size_t)(n - n_old) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *n_clusters_out = reps;
-    *n_edges_out = E.n_edges;
-    ctx->greedy_rounds = rounds;
-    ctx->greedy_batches = batches;
-    ctx->greedy_regrows = E.regrows;
-    ctx->greedy_edge_cap = E.cap;
-    return MG_OK;
-}
-
-// The whole triangle of t: cluster_tri's way to the thresholded counts (cut_counts) with GreedyEdges::append as their consumer -- one
-// wait per block --, then the rounds in batches (one wait per batch: the rows each of its rounds left open), then the assignment.
-// Edges: GreedyEdges (the first representative), or ForestEdges (the nearest one: 16 bytes an edge instead of 8, nothing else differs
-// before the assignment)
-template <class Edges>
-static int cluster_greedy_tri_of(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
-                                 uint64_t *n_edges_out)
-{
-    *n_clusters_out = 0;
-    *n_edges_out = 0;
-    ctx->greedy_rounds = ctx->greedy_batches = ctx->greedy_regrows = ctx->greedy_edge_cap = 0;
-    OutRange R;
-    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
-    if (rc != MG_OK || R.empty()) return rc;
-    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
-    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
-    if (std::is_same<Edges, ForestEdges>::value && R.s >= mg::FOREST_DENOM_LIMIT)
-        return fail(ctx, MG_ERR_UNSUPPORTED, "cluster nearest: sketch size 2^21 or more (the weight key orders denominators below 2^21 exactly)");
-    const uint32_t n = (uint32_t)t->n;
-    uint64_t edge_cap = 1ull << 23;                           // 64 MB (128 with counts); the list doubles, or grows to what a block needs, when it is short
-    if (const char *o = ctx_opt(ctx, "MASHGPU_GREEDY_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
-    Edges E(ctx);
-    CutBufs bufs(ctx, ctx);
-    PassABufs pa(ctx);
-    // the list starts no longer than the pairs its route can bring: the candidates, or the whole triangle
-    auto begin = [&](uint64_t most_edges) -> int {
-        const int rci = E.init(std::min<uint64_t>(edge_cap, most_edges));
-        if (rci != MG_OK) return rci;
-        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-        return MG_OK;
-    };
-    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
-                    [&](uint64_t pairs, uint64_t, uint64_t, bool lists) -> int {
-        if (!pa.alloc(pairs, R.s)) return kAllocFailed;
-        return lists ? MG_OK : begin(R.pairs);                // (the list route begins once its tables stand: below)
-    },
-                    [&] { pa.release(); },
-                    [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
-        const int rcb = L ? begin(L->K) : MG_OK;
-        return rcb != MG_OK ? rcb : E.append(f, pa, mg::PairSpace{n, n, 0u, 0u});
-    });
-    return rc != MG_OK ? rc : greedy_fixpoint(ctx, E, n, 0, false, nullptr, rep_out, rep_on_device, n_clusters_out, n_edges_out);
-}
-
-static int cluster_greedy_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
-                              uint64_t *n_edges_out)
-{
-    return cluster_greedy_tri_of<GreedyEdges>(ctx, t, cut, rep_out, rep_on_device, n_clusters_out, n_edges_out);
-}
-
-static int cluster_nearest_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *rep_out, bool rep_on_device, uint64_t *n_clusters_out,
-                               uint64_t *n_edges_out)
-{
-    return cluster_greedy_tri_of<ForestEdges>(ctx, t, cut, rep_out, rep_on_device, n_clusters_out, n_edges_out);
-}
-
-int mg_cluster_tri_greedy_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                               uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_host, false, n_clusters_out, n_edges_out,
-                         "mg_cluster_tri_greedy_host", true);
-}
-
-int mg_cluster_tri_greedy_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                              uint32_t *rep_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_dev, true, n_clusters_out, n_edges_out,
-                         "mg_cluster_tri_greedy_dev", true);
-}
-
-int mg_cluster_tri_nearest_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                                uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_host, false, n_clusters_out, n_edges_out,
-                         "mg_cluster_tri_nearest_host", true, true);
-}
-
-int mg_cluster_tri_nearest_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                               uint32_t *rep_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    return cluster_entry(ctx, t, Cut{kmer_size, kmer_space, max_distance, max_p_value}, rep_out_dev, true, n_clusters_out, n_edges_out,
-                         "mg_cluster_tri_nearest_dev", true, true);
-}
-
-int mg_cluster_greedy_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out, uint64_t *edge_capacity_out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (rounds_out) *rounds_out = ctx->greedy_rounds;
-    if (batches_out) *batches_out = ctx->greedy_batches;
-    if (regrows_out) *regrows_out = ctx->greedy_regrows;
-    if (edge_capacity_out) *edge_capacity_out = ctx->greedy_edge_cap;
-    return MG_OK;
-}
-
-
-/* ------------------------------------------------- an earlier clustering extended by new rows (include/mashgpu.h: mg_cluster_extend_host) */
-
-// What one of the two jobs of an extending call keeps on the device until the call's last wait: nothing is waited for between the
-// jobs, so the second one takes buffers of its own
-struct ExtendJob {
-    CutBufs bufs;
-    PassABufs pa;
-    explicit ExtendJob(mg_ctx *ctx) : bufs(ctx, ctx), pa(ctx) {}
-};
-
-// The arguments both extending calls share, checked before anything is queued: `seed` is an earlier result over ref's rows
-static int extend_check(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *seed, const Cut &cut, const void *out, uint64_t out_rows,
-                        const uint64_t *n_clusters_out, const uint64_t *n_edges_out, const char *who, const char *seed_name)
-{
-    if (!ref || !qry || !n_clusters_out || !n_edges_out || (!out && out_rows)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (!ref->lengths || !qry->lengths || !ref->has_lengths || !qry->has_lengths)
-        return fail(ctx, MG_ERR_INVALID, std::string(who) + ": the tables carry no lengths");
-    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": both filters are off (every pair would be an edge)");
-    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
-    if (ref->s != qry->s)
-        return fail(ctx, MG_ERR_INVALID, std::string(who) + ": sketch sizes differ (" + std::to_string(ref->s) + " and " + std::to_string(qry->s) + ")");
-    if (ref->s > 0xFFFFFFFEull) return fail(ctx, MG_ERR_INVALID, "compare: sketch size too large");
-    if (ref->n + qry->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
-    for (uint64_t i = 0; seed && i < ref->n; i++) {
-        if (seed[i] > i)
-            return fail(ctx, MG_ERR_INVALID, std::string(who) + ": " + seed_name + "[" + std::to_string(i) + "] = " + std::to_string(seed[i]) + " is larger than its row");
-        if (seed[seed[i]] != seed[i])
-            return fail(ctx, MG_ERR_INVALID, std::string(who) + ": " + seed_name + "[" + std::to_string(i) + "] = " + std::to_string(seed[i]) +
-                                                 " is not the first row of its cluster (" + seed_name + "[" + std::to_string(seed[i]) + "] = " +
-                                                 std::to_string(seed[seed[i]]) + ")");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return MG_OK;
-}
-
-// The two jobs whose marked pairs are exactly the edges of the concatenated table that touch a new row: the rectangle qry x ref
-// (row = query q -> n + q, col = reference r) and the triangle of qry (both sides n + .).  consume(job, R, space) runs cut_counts.
-template <class Consume>
-static int extend_jobs(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, ExtendJob &rect, ExtendJob &tri, Consume consume)
-{
-    const uint32_t n = (uint32_t)ref->n, m = (uint32_t)qry->n;
-    OutRange R;
-    int rc = out_range(ctx, qry, ref, 0, m, false, &R);
-    if (rc == MG_OK && !R.empty() && R.pairs) rc = consume(rect, R, mg::PairSpace{m, n, n, 0u});
-    if (rc != MG_OK) return rc;
-    rc = out_range(ctx, qry, qry, 0, m, true, &R);
-    if (rc == MG_OK && !R.empty() && R.pairs) rc = consume(tri, R, mg::PairSpace{m, m, n, n});
-    return rc;
-}
-
-// cluster_tri's way, twice over one `parent` seeded with the earlier labels: no wait before the last one
-static int cluster_extend(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_label, const Cut &cut, uint32_t *label_out,
-                          uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    const uint32_t n = (uint32_t)ref->n, total = n + (uint32_t)qry->n;
-    if (!total) return MG_OK;
-    DevBuf<uint32_t> parent(ctx), label(ctx);
-    DevBuf<unsigned long long> d_roots(ctx), d_rect(ctx), d_tri(ctx);          // the clusters; pass A's count per block of either job
-    if (parent.alloc(total) != hipSuccess || label.alloc(total) != hipSuccess || d_roots.alloc(1) != hipSuccess)
-        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
-    // the earlier labels travel through `label`, which nobody writes before the label launch
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(label, ref_label, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, mg::launch_cluster_seed(parent, label, n, total, ctx->stream));
-    ExtendJob rect(ctx), tri(ctx);
-    uint64_t nb_rect = 0, nb_tri = 0;
-    int rc = extend_jobs(ctx, ref, qry, rect, tri, [&](ExtendJob &J, const OutRange &R, const mg::PairSpace &sp) -> int {
-        DevBuf<unsigned long long> &d_cnt = &J == &rect ? d_rect : d_tri;
-        uint64_t &nblocks = &J == &rect ? nb_rect : nb_tri;
-        return cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, J.bufs,
-                          [&](uint64_t pairs, uint64_t, uint64_t blocks, bool lists) -> int {
-            if (!J.pa.alloc(pairs, R.s) || d_cnt.alloc(blocks) != hipSuccess) return kAllocFailed;
-            if (lists) return MG_OK;                          // (the flags are cleared once the list's tables stand: below)
-            HIP_TRY(ctx, hipMemsetAsync(J.pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-            return MG_OK;
-        },
-                          [&] { J.pa.release(); },
-                          [&](mg::FinishArgs f, const RowBlock &, const CandLists *L) -> int {
-            if (L) HIP_TRY(ctx, hipMemsetAsync(J.pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-            J.pa.bind(f);
-            HIP_TRY(ctx, mg::launch_finish_mark(f, d_cnt + nblocks++, ctx->stream));
-            HIP_TRY(ctx, mg::launch_cluster_union(f, parent, sp, ctx->stream));
-            return MG_OK;
-        });
-    });
-    if (rc != MG_OK) return rc;
-    // the labels, the roots' number and pass A's counts, behind every union queued so far
-    std::vector<unsigned long long> h(1 + nb_rect + nb_tri);
-    HIP_TRY(ctx, mg::launch_cluster_label(parent, total, label, d_roots, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_roots, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (nb_rect) HIP_TRY(ctx, hipMemcpyAsync(h.data() + 1, d_rect, nb_rect * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (nb_tri) HIP_TRY(ctx, hipMemcpyAsync(h.data() + 1 + nb_rect, d_tri, nb_tri * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(label_out, label, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (both jobs' buffers are released behind this wait)
-    *n_clusters_out = h[0];
-    for (size_t b = 1; b < h.size(); b++) *n_edges_out += h[b];
-    return MG_OK;
-}
-
-// cluster_greedy_tri's way, twice into one edge list (one wait per block, as there), then the fixpoint over the seeded states
-static int cluster_extend_greedy(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_rep, const Cut &cut, uint32_t *rep_out,
-                                 uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    ctx->greedy_rounds = ctx->greedy_batches = ctx->greedy_regrows = ctx->greedy_edge_cap = 0;
-    const uint32_t n = (uint32_t)ref->n, total = n + (uint32_t)qry->n;
-    if (!total) return MG_OK;
-    uint64_t edge_cap = 1ull << 23;                           // (cluster_greedy_tri)
-    if (const char *o = ctx_opt(ctx, "MASHGPU_GREEDY_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));
-    DevBuf<uint32_t> seed(ctx);
-    if (ref_rep && n) {
-        if (seed.alloc(n) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
-        HIP_TRY(ctx, hipMemcpyAsync(seed, ref_rep, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    GreedyEdges E(ctx);
-    ExtendJob rect(ctx), tri(ctx);
-    int rc = extend_jobs(ctx, ref, qry, rect, tri, [&](ExtendJob &J, const OutRange &R, const mg::PairSpace &sp) -> int {
-        // the list begins with the first job that brings pairs, no longer than those; the second job's edges make it grow
-        auto begin = [&](uint64_t most_edges) -> int {
-            const int rci = E.buf.p ? MG_OK : E.init(std::min<uint64_t>(edge_cap, most_edges));
-            if (rci != MG_OK) return rci;
-            HIP_TRY(ctx, hipMemsetAsync(J.pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-            return MG_OK;
-        };
-        return cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, J.bufs,
-                          [&](uint64_t pairs, uint64_t, uint64_t, bool lists) -> int {
-            if (!J.pa.alloc(pairs, R.s)) return kAllocFailed;
-            return lists ? MG_OK : begin(R.pairs);
-        },
-                          [&] { J.pa.release(); },
-                          [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
-            const int rcb = L ? begin(L->K) : MG_OK;
-            return rcb != MG_OK ? rcb : E.append(f, J.pa, sp);
-        });
-    });
-    return rc != MG_OK ? rc : greedy_fixpoint(ctx, E, total, n, true, ref_rep ? seed.p : nullptr, rep_out, false, n_clusters_out, n_edges_out);
-}
-
-int mg_cluster_extend_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_label, int kmer_size, double kmer_space,
-                           double max_distance, double max_p_value, uint32_t *label_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
-    if (ref && ref->n && !ref_label) return fail(ctx, MG_ERR_INVALID, "mg_cluster_extend_host: NULL argument");
-    const int rc = extend_check(ctx, ref, qry, ref_label, cut, label_out_host, ref && qry ? ref->n + qry->n : 1, n_clusters_out, n_edges_out,
-                                "mg_cluster_extend_host", "ref_label");
-    if (rc != MG_OK) return rc;
-    *n_clusters_out = *n_edges_out = 0;
-    return cluster_extend(ctx, ref, qry, ref_label, cut, label_out_host, n_clusters_out, n_edges_out);
-}
-
-int mg_cluster_extend_greedy_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, const uint32_t *ref_rep, int kmer_size, double kmer_space,
-                                  double max_distance, double max_p_value, uint32_t *rep_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
-    const int rc = extend_check(ctx, ref, qry, ref_rep, cut, rep_out_host, qry ? qry->n : 1, n_clusters_out, n_edges_out,
-                                "mg_cluster_extend_greedy_host", "ref_rep");
-    if (rc != MG_OK) return rc;
-    *n_clusters_out = *n_edges_out = 0;
-    return cluster_extend_greedy(ctx, ref, qry, ref_rep, cut, rep_out_host, n_clusters_out, n_edges_out);
-}
-
-
-/* ------------------------------------------------- the minimum spanning forest of the thresholded triangle (cluster_forest.hip) */
-
-// The whole triangle of t: cluster_greedy_tri's way to the edge list (cut_counts with ForestEdges::append as the consumer, one wait per
-// block), then ONE batch -- the rounds, the labels, the sort, the denominators -- and one wait for it, then the distance rows of exactly
-// those denominators and the records
-static int cluster_forest_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, mg_result *out_host, uint64_t capacity, uint64_t *count_out,
-                              uint32_t *label_out, uint64_t *n_clusters_out, uint64_t *n_edges_out)
-{
-    *count_out = *n_clusters_out = *n_edges_out = 0;
-    ctx->forest_rounds = ctx->forest_regrows = ctx->forest_edge_cap = 0;
-    ctx->forest_live.clear();
-    ctx->forest_chosen.clear();
-    OutRange R;
-    int rc = out_range(ctx, t, t, 0, t->n, true, &R);
-    if (rc != MG_OK || R.empty()) return rc;
-    if (cut.k < 1) return fail(ctx, MG_ERR_INVALID, "compare: bad k-mer size");
-    if (t->n > 0x7FFFFFFFull) return fail(ctx, MG_ERR_UNSUPPORTED, "cluster: more than 2^31 - 1 rows");
-    if (R.s >= mg::FOREST_DENOM_LIMIT)
-        return fail(ctx, MG_ERR_UNSUPPORTED, "cluster forest: sketch size 2^21 or more (the weight key orders denominators below 2^21 exactly)");
-    const uint32_t n = (uint32_t)t->n;
-    uint64_t edge_cap = 1ull << 23;                           // 128 MB; the list doubles, or grows to what a block needs, when it is short
-    if (const char *o = ctx_opt(ctx, "MASHGPU_FOREST_EDGE_CAP")) edge_cap = std::max<uint64_t>(1, strtoull(o, nullptr, 10));   // (test knob)
-    ForestEdges E(ctx);
-    CutBufs bufs(ctx, ctx);
-    PassABufs pa(ctx);
-    // the list starts no longer than the pairs its route can bring: the candidates, or the whole triangle
-    auto begin = [&](uint64_t most_edges) -> int {
-        const int rci = E.init(std::min<uint64_t>(edge_cap, most_edges));
-        if (rci != MG_OK) return rci;
-        HIP_TRY(ctx, hipMemsetAsync(pa.seen, 0, ((size_t)R.s + 1) * 4, ctx->stream));
-        return MG_OK;
-    };
-    rc = cut_counts(ctx, R, cut, true, {1ull << 30, "MASHGPU_CLUSTER_BLOCK_PAIRS", "cluster"}, bufs,
-                    [&](uint64_t pairs, uint64_t, uint64_t, bool lists) -> int {
-        if (!pa.alloc(pairs, R.s)) return kAllocFailed;
-        return lists ? MG_OK : begin(R.pairs);                // (the list route begins once its tables stand: below)
-    },
-                    [&] { pa.release(); },
-                    [&](const mg::FinishArgs &f, const RowBlock &, const CandLists *L) -> int {
-        const int rcb = L ? begin(L->K) : MG_OK;
-        return rcb != MG_OK ? rcb : E.append(f, pa, mg::PairSpace{n, n, 0u, 0u});
-    });
-    if (rc != MG_OK) return rc;
-    const uint32_t rounds_queued = mg::forest_rounds(n);
-    DevBuf<uint32_t> parent(ctx), comp(ctx), merged(ctx), label(ctx), seen(ctx);
-    DevBuf<unsigned long long> best_key(ctx), best_rc(ctx), live(ctx), d_n(ctx);      // d_n: [0] the chosen edges, [1] the clusters
-    DevBuf<uint4> forest(ctx);
-    if (parent.alloc(n) != hipSuccess || comp.alloc(n) != hipSuccess || merged.alloc(rounds_queued) != hipSuccess || label.alloc(n) != hipSuccess ||
-        seen.alloc((uint64_t)R.s + 1) != hipSuccess || best_key.alloc(n) != hipSuccess || best_rc.alloc(n) != hipSuccess || live.alloc(rounds_queued) != hipSuccess ||
-        d_n.alloc(2) != hipSuccess ||
-        forest.alloc(mg::forest_room(n)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
-    }
-    const mg::ForestBufs fb{parent, comp, best_key, best_rc, forest, d_n, merged, live};
-    std::vector<uint32_t> h_merged(rounds_queued), h_seen((size_t)R.s + 1);
-    std::vector<unsigned long long> h_live(rounds_queued);
-    unsigned long long h_n[2] = {0, 0};
-    HIP_TRY(ctx, mg::launch_forest_rounds(E.buf, E.used, fb, n, label, d_n + 1, seen, R.s, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h_merged.data(), merged, (size_t)rounds_queued * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h_live.data(), live, (size_t)rounds_queued * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h_seen.data(), seen, h_seen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h_n, d_n, 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (label_out) HIP_TRY(ctx, hipMemcpyAsync(label_out, label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t r = 0;
-    while (r < rounds_queued && h_merged[r]) r++;
-    if (E.used && r == rounds_queued) return fail(ctx, MG_ERR_HIP, "cluster forest: the rounds did not reach their fixpoint");   // (floor(log2 n) + 1 suffice)
-    const uint64_t count = h_n[0];
-    if (count + h_n[1] != n) return fail(ctx, MG_ERR_HIP, "cluster forest: the chosen edges do not span the clusters");
-    *count_out = count;
-    *n_clusters_out = h_n[1];
-    *n_edges_out = E.n_edges;
-    ctx->forest_rounds = E.used ? r + 1 : 0;
-    ctx->forest_live.assign(h_live.begin(), h_live.begin() + ctx->forest_rounds);
-    ctx->forest_chosen.assign(h_merged.begin(), h_merged.begin() + ctx->forest_rounds);
-    ctx->forest_regrows = E.regrows;
-    ctx->forest_edge_cap = E.cap;
-    if (count > capacity) return fail(ctx, MG_ERR_NOMEM, "cluster forest: more forest edges than `capacity` (see *count_out)");
-    if (!count) return MG_OK;
-    FinishTables ft(ctx);
-    if ((rc = build_finish_tables(ctx, R.s, cut, h_seen, ft)) != MG_OK) return rc;
-    DevBuf<mg::FinishEdge> recs(ctx);
-    HIP_TRY(ctx, recs.alloc(count));
-    HIP_TRY(ctx, mg::launch_forest_finish(finish_args(R.rows, R.cols, R.s, true, nullptr, count, 0, ft, cut), forest, count, recs, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(out_host, recs, count * sizeof(mg_result), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (!ft.complete) patch_nan_distances(out_host, count, cut.k);
-    return MG_OK;
-}
-
-int mg_cluster_tri_forest_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
-                               mg_result *out_host, uint64_t capacity, uint64_t *count_out, uint32_t *label_out_host, uint64_t *n_clusters_out,
-                               uint64_t *n_edges_out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!t || !count_out || !n_clusters_out || !n_edges_out || (!out_host && capacity))
-        return fail(ctx, MG_ERR_INVALID, "mg_cluster_tri_forest_host: NULL argument");
-    if (!t->lengths || !t->has_lengths) return fail(ctx, MG_ERR_INVALID, "mg_cluster_tri_forest_host: the table carries no lengths");
-    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
-    if (!cut.filtered()) return fail(ctx, MG_ERR_INVALID, "mg_cluster_tri_forest_host: both filters are off (every pair would be an edge)");
-    return cluster_forest_tri(ctx, t, cut, out_host, capacity, count_out, label_out_host, n_clusters_out, n_edges_out);
-}
-
-int mg_cluster_forest_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *regrows_out, uint64_t *edge_capacity_out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (rounds_out) *rounds_out = ctx->forest_rounds;
-    if (regrows_out) *regrows_out = ctx->forest_regrows;
-    if (edge_capacity_out) *edge_capacity_out = ctx->forest_edge_cap;
-    return MG_OK;
-}
-
-int mg_cluster_forest_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *chosen_out, uint64_t capacity, uint64_t *rounds_out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!rounds_out || ((!live_out || !chosen_out) && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_cluster_forest_rounds: NULL argument");
-    *rounds_out = ctx->forest_live.size();
-    for (uint64_t r = 0; r < capacity && r < ctx->forest_live.size(); r++) {
-        live_out[r] = ctx->forest_live[r];
-        chosen_out[r] = ctx->forest_chosen[r];
-    }
-    return MG_OK;
 }
 
 

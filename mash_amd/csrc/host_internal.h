@@ -3,6 +3,7 @@
 // mashgpu.cpp      context, pool, parameters, tables, profiling
 // host_sketch.cpp  sketching: batch, packed input, streamed sessions, reads mode
 // host_compare.cpp comparing: tile engine, inverted-index engine, finishing, thresholded and list outputs
+// host_cluster.cpp clustering: unions and edge lists over the thresholded counts (cut_internal.h: what host_compare.cpp gives them)
 // host_comm.cpp    several GPUs: communicator, replicated / row-sharded tables, sharded calls
 // host_screen.cpp  screening, on one GPU and on several
 // host_taxscreen.cpp  taxonomy of a screen: per-hash LCA, per-taxon counts

@@ -12,7 +12,7 @@
 5. Calling conventions: the _dev form with a guard word, repeated calls, 0 and 1 rows, the error returns.
 Here, and only here, workgroups race on best_key[] and rep[]: the emulator (tests/test_cluster_nearest_emu.py) runs them one after
 another.  Every command runs under its own timeout; a non-zero exit ends the test.  The MG_ERR_UNSUPPORTED return for a sketch
-size of 2^21 or more is not exercised (it would need a table of that width); it is one comparison in cluster_greedy_tri_of."""
+size of 2^21 or more is not exercised (it would need a table of that width); it is one comparison in cluster_jobs (host_cluster.cpp)."""
 import ctypes as C
 import json
 import os
