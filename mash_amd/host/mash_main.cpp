@@ -1153,6 +1153,37 @@ struct Blocks {
     }
 };
 
+// Budgets of a block of rows whose survivors alone come back (the library cuts its own device blocks): triangle, rectangle
+const uint64_t kTriFilteredPairs = 1ull << 31, kDistFilteredPairs = 1ull << 30;
+
+// The pairs within d_max from one context's tables, block by block: of a triangle (rows 1 .. n of t) or of a rectangle (the nq
+// rows of qry against the nref of ref).  The p-value filter stays with the caller (finish_edge): use(edges) gets every block's
+// list.  Non-zero: an error has been reported.
+template <class Use>
+int tri_edge_blocks(Gpu &gpu, const mg_table *t, uint64_t n, int kmer, double d_max, Use use)
+{
+    vector<mg_edge> edges;
+    for (Blocks b(1, n, kTriFilteredPairs); b.next();) {
+        if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                return mg_compare_tri_filter_host(gpu.ctx, t, b.r0, b.r1, kmer, d_max, o, cap, cnt); }))
+            return 1;
+        use(edges);
+    }
+    return 0;
+}
+template <class Use>
+int rect_edge_blocks(Gpu &gpu, const mg_table *ref, const mg_table *qry, uint64_t nref, uint64_t nq, int kmer, double d_max, Use use)
+{
+    vector<mg_edge> edges;
+    for (Blocks b(0, nq, kDistFilteredPairs, nref); b.next();) {
+        if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
+                return mg_compare_rect_filter_host(gpu.ctx, ref, qry, b.r0, b.r1, kmer, d_max, o, cap, cnt); }))
+            return 1;
+        use(edges);
+    }
+    return 0;
+}
+
 // -N on the host (MASH_AMD_HOST_FINISH=1): appends the `keep` nearest of one row's passing pairs {row, neighbour, ...} to
 // res, in the order of mg_compare_*_topk_host: by shared hashes as an exact fraction, equal fractions by neighbour index
 void select_nearest(vector<mg_result> &row, uint64_t keep, vector<mg_result> &res)
@@ -1255,9 +1286,8 @@ using DTable = std::unique_ptr<mg_dtable, DTableFree>;
 int finish_run(const SketchSet &set, const KmerWarning &w, bool reads) { if (w.count > 0 && !reads) warn_kmer_size(set, w); return 0; }
 
 // ------------------------------------------------------------------------------- dist
-// Budgets of a block of query rows (MASH_AMD_BLOCK_PAIRS lowers them):
+// Budgets of a block of query rows (MASH_AMD_BLOCK_PAIRS lowers them; kDistFilteredPairs stands with rect_edge_blocks):
 const uint64_t kDistFullPairs = 1ull << 24;         // the whole matrix comes back: 512 MiB of mg_pair per block
-const uint64_t kDistFilteredPairs = 1ull << 30;     // only the survivors come back; the library cuts its own device blocks
 const uint64_t kDistNearestRecords = 1ull << 22;    // -N: `keep` records per query, 128 MiB of mg_result per block
 
 struct DistRun {
@@ -1336,26 +1366,22 @@ int dist_nearest(DistRun &r)
 // -d / -v without -t: the surviving pairs as finished records
 int dist_filtered(DistRun &r)
 {
-    vector<mg_result> res;
-    vector<mg_edge> edges;
-    for (Blocks b(0, r.nq, kDistFilteredPairs, r.nref); b.next();) {
-        if (!host_finish_wanted()) {
-            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
-                    return mg_compare_rect_results_sharded_host(r.gpu.comm, r.dr.get(), r.dq.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, n); }))
-                return 1;
-            dist_emit_results(r, res);
-        } else {
-            // MASH_AMD_HOST_FINISH=1: the pairs within -d from device 0's replicas, p-values and the -v filter here
-            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *n) {
-                    return mg_compare_rect_filter_host(r.gpu.ctx, r.tr, r.tq, b.r0, b.r1, r.kmer, r.d_max, o, cap, n); }))
-                return 1;
+    if (host_finish_wanted())
+        // MASH_AMD_HOST_FINISH=1: the pairs within -d from device 0's replicas, p-values and the -v filter here
+        return rect_edge_blocks(r.gpu, r.tr, r.tq, r.nref, r.nq, r.kmer, r.d_max, [&](const vector<mg_edge> &edges) {
             emit_rows(r.out, 0, edges.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
                 const mg_edge &e = edges[x];
                 mg_pair pr;
                 if (finish_edge(e, r.len_ref[e.col], r.len_qry[e.row], r.kmer, r.kspace, r.p_max, pr))
                     print_pair_line(o, r.ref.refs[e.col], r.qry.refs[e.row], r.comment, pr);
             });
-        }
+        });
+    vector<mg_result> res;
+    for (Blocks b(0, r.nq, kDistFilteredPairs, r.nref); b.next();) {
+        if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                return mg_compare_rect_results_sharded_host(r.gpu.comm, r.dr.get(), r.dq.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, n); }))
+            return 1;
+        dist_emit_results(r, res);
     }
     return 0;
 }
@@ -1480,10 +1506,9 @@ int cmd_dist(int argc, const char **argv)
 }
 
 // ------------------------------------------------------------------------------- triangle
-// Budgets of a block of rows (MASH_AMD_BLOCK_PAIRS lowers them):
+// Budgets of a block of rows (MASH_AMD_BLOCK_PAIRS lowers them; kTriFilteredPairs stands with tri_edge_blocks):
 const uint64_t kTriDensePairs = 1ull << 24;         // the whole block comes back: 128 MiB of mg_counts, 512 MiB of mg_pair
 const uint64_t kTriSparsePairs = 1ull << 26;        // only the pairs that share a hash come back: at most an eighth of these
-const uint64_t kTriFilteredPairs = 1ull << 31;      // only the survivors come back; the library cuts its own device blocks
 const uint64_t kTriNearestRecords = 1ull << 24;     // -N: `keep` records per row, 512 MiB of mg_result per block
 
 struct TriRun {
@@ -1562,21 +1587,9 @@ int tri_nearest(TriRun &r, uint64_t keep)
 // -E with -d / -v: the surviving pairs as finished records
 int tri_filtered(TriRun &r)
 {
-    vector<mg_result> res;
-    vector<mg_edge> edges;
-    for (Blocks b(1, r.n, kTriFilteredPairs); b.next();) {
-        if (!host_finish_wanted()) {
-            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *cnt) {
-                    return mg_compare_tri_results_sharded_host(r.gpu.comm, r.dt.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, cnt); }))
-                return 1;
-            r.clk.lap("compare+finish+filter+copy");
-            tri_emit_results(r, res);
-            r.clk.lap("format+write");
-        } else {
-            // MASH_AMD_HOST_FINISH=1: the pairs within -d from device 0's replica, p-values and the -v filter here
-            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
-                    return mg_compare_tri_filter_host(r.gpu.ctx, r.t, b.r0, b.r1, r.kmer, r.d_max, o, cap, cnt); }))
-                return 1;
+    if (host_finish_wanted())
+        // MASH_AMD_HOST_FINISH=1: the pairs within -d from device 0's replica, p-values and the -v filter here
+        return tri_edge_blocks(r.gpu, r.t, r.n, r.kmer, r.d_max, [&](const vector<mg_edge> &edges) {
             r.clk.lap("compare+filter+copy");
             emit_rows(r.out, 0, edges.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
                 const mg_edge &e = edges[x];
@@ -1585,7 +1598,15 @@ int tri_filtered(TriRun &r)
                     print_edge_line(o, r.label(e.row), r.label(e.col), pr.numer, pr.denom, pr.distance, pr.p_value);
             });
             r.clk.lap("finish+format+write");
-        }
+        });
+    vector<mg_result> res;
+    for (Blocks b(1, r.n, kTriFilteredPairs); b.next();) {
+        if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *cnt) {
+                return mg_compare_tri_results_sharded_host(r.gpu.comm, r.dt.get(), b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, cnt); }))
+            return 1;
+        r.clk.lap("compare+finish+filter+copy");
+        tri_emit_results(r, res);
+        r.clk.lap("format+write");
     }
     return 0;
 }
@@ -1764,61 +1785,162 @@ int cmd_triangle(int argc, const char **argv)
 
 // `mash cluster`: single-linkage clusters of the pairs `mash triangle -E -d -v` would print (the reference has no such command;
 // include/mashgpu.h: mg_cluster_tri_host).  One line per sketch in input order: cluster number (from 1, in order of the
-// clusters' first members), cluster size, name.  The clusters are found on the device and one label per sketch comes back;
-// MASH_AMD_HOST_FINISH=1 takes the edges of tri_filtered's host call and a union-find here.
+// clusters' first members), cluster size, name.  The clusters are found on the device and one label per sketch comes back.
 // -R: greedy representative clusters of the same pairs instead (mg_cluster_tri_greedy_host): walking the sketches in input
 // order, a sketch opens a cluster iff no earlier representative is within the threshold, else it joins the first one that is.
-// Lines and numbering are the same (the label is the representative); the host route runs that walk here.
+// Lines and numbering are the same (the label is the representative).
 // -B: -R's representatives, every other sketch under its NEAREST one (mg_cluster_tri_nearest_host): the representative, earlier or
 // later in the input, with which it shares the larger fraction of hashes, exactly (mg::forest_before); a fourth field names it.
 // -M: the single-linkage clusters, each line with a fourth field naming the cluster's MEDOID (mg_cluster_tri_medoid_host): the member
 // whose edges' weights floor(numer * 2^32 / max(denom, 1)) sum to the most, equal sums to the earlier member.  Numbers, sizes and
-// the first three fields are those of the run without -M.  The host route sums and picks here, from the edges it fetches anyway.
-// -T: the minimum spanning forest of the same pairs instead (cluster_forest below): edge-list lines, not cluster lines.
+// the first three fields are those of the run without -M.
+// -T: the minimum spanning forest of the same pairs instead (mg_cluster_tri_forest_host): one `triangle -E` line per forest edge,
+// best first, not cluster lines.
 // -A <earlier output>: the clusters of the first L inputs are read from an earlier run's stdout and only the pairs that touch a
-// later input are compared (cluster_extend below; include/mashgpu.h: mg_cluster_extend_host).
+// later input are compared (cluster_extend below; include/mashgpu.h: mg_cluster_extend_host).  With plain and with -R only.
+// MASH_AMD_HOST_FINISH=1 is the host route, which the tests judge the device route by: the pairs within -d come from the host calls
+// of `triangle -E -d` and `dist -d` (tri_edge_blocks, rect_edge_blocks), and what follows is done here, once for every form
+// (cluster_on_host: Sets, greedy_walk, nearest_pick, medoid_pick; -T: Kruskal over the same Sets).
 
-// `mash cluster -T`: one `triangle -E` line per edge of the minimum spanning forest of the pairs within -d / -v, best first.  The
-// forest is found on the device and its rows - clusters records come back (mg_cluster_tri_forest_host); MASH_AMD_HOST_FINISH=1 takes
-// the edges of tri_filtered's host call, sorts them by the exact fraction and runs Kruskal here.
-int cluster_forest(TriRun &r)
+enum ClusterMode { kSingle, kGreedy, kNearest, kMedoid, kForest };      // plain, -R, -B (with or without -R), -M, -T; -A is a flag beside it
+
+// The lap of a form's clustering (MASH_AMD_TIMING=1) on the device and on the host route: kClusterLaps[mode][with -A]
+const struct { const char *device, *host; } kClusterLaps[5][2] = {
+    {{"compare+mark+union+label+copy", "compare+filter+copy+union"},
+     {"seed+compare+mark+union (new x old, new x new)+label+copy", "compare+filter+copy (new x old, new x new)+union"}},
+    {{"compare+mark+append+rounds+assign+copy", "compare+filter+copy+walk"},
+     {"compare+mark+append (new x representatives, new x new)+rounds+assign+copy", "compare+filter+copy (new x representatives, new x new)+walk"}},
+    {{"compare+mark+append+rounds+nearest+copy", "compare+filter+copy+walk+nearest"}},
+    {{"compare+mark+union+score+label+pick+copy", "compare+filter+copy+union+score+pick"}},
+    {{"compare+mark+append+rounds+sort+finish+copy", "compare+filter+copy+sort+kruskal"}},
+};
+
+// Union-find in place over a vector of labels: a set's root is its smallest member, so the first input of a cluster names it
+struct Sets {
+    vector<uint32_t> &up;
+    uint32_t find(uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; }
+    bool unite(uint32_t a, uint32_t b) { a = find(a); b = find(b); if (a != b) up[std::max(a, b)] = std::min(a, b); return a != b; }      // false: one set already
+};
+
+// -R: the walk over the inputs from `first` on, in input order; smaller[i - first] holds the neighbours of i with a smaller index.
+// lab[j] == j says that j, decided before i, is a representative: i joins the first such neighbour and stays its own without one.
+void greedy_walk(vector<uint32_t> &lab, uint64_t first, const vector<vector<uint32_t>> &smaller)
 {
-    vector<mg_result> res;
-    if (!host_finish_wanted()) {
-        res.resize(r.n - 1);
-        uint64_t count = 0, n_clusters = 0, n_edges = 0;
-        if (mg_cluster_tri_forest_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, res.data(), res.size(), &count, nullptr, &n_clusters, &n_edges) != MG_OK)
-            return report_error(r.gpu);
-        res.resize(count);
-        r.clk.lap("compare+mark+append+rounds+sort+finish+copy");
-    } else {
-        vector<mg_edge> edges;
-        vector<mg_result> all;
-        for (Blocks b(1, r.n, kTriFilteredPairs); b.next();) {
-            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
-                    return mg_compare_tri_filter_host(r.gpu.ctx, r.t, b.r0, b.r1, r.kmer, r.d_max, o, cap, cnt); }))
-                return 1;
-            for (const mg_edge &e : edges) {
-                mg_pair pr;
-                if (finish_edge(e, r.lengths[e.row], r.lengths[e.col], r.kmer, r.kspace, r.p_max, pr))
-                    all.push_back(mg_result{e.row, e.col, pr.numer, pr.denom, pr.distance, pr.p_value});
-            }
+    for (uint64_t i = first; i < lab.size(); i++)
+        for (const uint32_t j : smaller[i - first])
+            if (lab[j] == j && (lab[i] == i || j < lab[i])) lab[i] = j;
+}
+
+// -B: the walk has named the representatives; a member now takes the best of ALL its edges to one, either end of the pair:
+// mg::forest_before with the representative in the row pair's place (equal fractions: the smaller one)
+void nearest_pick(vector<uint32_t> &lab, const vector<mg_edge> &edges)
+{
+    const uint64_t n = lab.size();
+    vector<uint8_t> is_rep(n);
+    vector<const mg_edge *> best(n, nullptr);
+    for (uint64_t i = 0; i < n; i++) is_rep[i] = lab[i] == i;
+    for (const mg_edge &e : edges) {
+        if (is_rep[e.row] == is_rep[e.col]) continue;
+        const uint32_t member = is_rep[e.row] ? e.col : e.row, r = is_rep[e.row] ? e.row : e.col;
+        const mg_edge *b = best[member];
+        if (!b || mg::forest_before(e.numer, e.denom, r, b->numer, b->denom, lab[member])) {
+            best[member] = &e;
+            lab[member] = r;
         }
+    }
+}
+
+// -M: per cluster the largest score, met first at its smallest row: the walk is in index order and only a larger score moves it
+void medoid_pick(const vector<uint32_t> &lab, const vector<uint64_t> &score, vector<uint32_t> &med)
+{
+    const uint64_t n = lab.size();
+    vector<uint32_t> top(n);
+    for (uint64_t i = 0; i < n; i++) top[i] = (uint32_t)i;
+    for (uint64_t i = 0; i < n; i++)
+        if (score[i] > score[top[lab[i]]]) top[lab[i]] = (uint32_t)i;
+    for (uint64_t i = 0; i < n; i++) med[i] = top[lab[i]];
+}
+
+// What a run finds: per input its label, the first member of its cluster (-R, -B: its representative), and with -M its cluster's
+// medoid; or with -T the forest's records, best first
+struct Clusters { vector<uint32_t> lab, med; vector<mg_result> forest; };
+
+// The host route of every form, with and without -A, from the passing edges.  Inputs below `first` are decided already and lab
+// holds their labels (-A: first == L; else 0).  passing_edges(take) calls take(edge, pair) for every edge that passes -d and -v,
+// row and col being inputs, and returns non-zero after a reported error.  -T sorts them by the exact fraction and runs Kruskal.
+template <class Source>
+int cluster_on_host(ClusterMode mode, uint64_t first, Clusters &c, Source passing_edges)
+{
+    vector<uint32_t> &lab = c.lab;
+    const uint64_t n = lab.size();
+    const bool greedy = mode == kGreedy || mode == kNearest;
+    for (uint64_t i = first; i < n; i++) lab[i] = (uint32_t)i;
+    Sets sets{lab};
+    vector<vector<uint32_t>> smaller(greedy ? n - first : 0);
+    vector<mg_edge> kept;                                      // -B: every edge with its counts
+    vector<uint64_t> score(mode == kMedoid ? n : 0);           // -M: per input the sum of its edges' weights
+    vector<mg_result> all;                                     // -T: every edge as the record of its line
+    if (passing_edges([&](const mg_edge &e, const mg_pair &pr) {
+            if (mode == kForest) {
+                all.push_back(mg_result{e.row, e.col, pr.numer, pr.denom, pr.distance, pr.p_value});
+            } else if (greedy) {
+                smaller[std::max(e.row, e.col) - first].push_back(std::min(e.row, e.col));
+                if (mode == kNearest) kept.push_back(e);
+            } else {
+                sets.unite(e.row, e.col);
+                if (mode == kMedoid) {
+                    const uint64_t wt = mg::medoid_weight(e.numer, e.denom);
+                    score[e.row] += wt;
+                    score[e.col] += wt;
+                }
+            }
+        }))
+        return 1;
+    if (mode == kForest) {
         std::sort(all.begin(), all.end(), [](const mg_result &a, const mg_result &b) {
             return mg::forest_before(a.numer, a.denom, mg::forest_rc(a.row, a.col), b.numer, b.denom, mg::forest_rc(b.row, b.col)); });
-        vector<uint32_t> up(r.n);
-        for (uint64_t i = 0; i < r.n; i++) up[i] = (uint32_t)i;
-        auto find = [&](uint32_t x) { while (up[x] != x) { up[x] = up[up[x]]; x = up[x]; } return x; };
-        for (const mg_result &e : all) {
-            const uint32_t a = find(e.row), b = find(e.col);
-            if (a == b) continue;
-            up[std::max(a, b)] = std::min(a, b);
-            res.push_back(e);
-        }
-        r.clk.lap("compare+filter+copy+sort+kruskal");
+        for (const mg_result &e : all)
+            if (sets.unite(e.row, e.col)) c.forest.push_back(e);
+    } else if (greedy) {
+        greedy_walk(lab, first, smaller);
+        if (mode == kNearest) nearest_pick(lab, kept);
+    } else {
+        for (uint64_t i = 0; i < n; i++) lab[i] = sets.find((uint32_t)i);
+        if (mode == kMedoid) medoid_pick(lab, score, c.med);
     }
-    tri_emit_results(r, res);
-    r.clk.lap("format+write");
+    return 0;
+}
+
+// Every form without -A, on one table
+int cluster_table(TriRun &r, ClusterMode mode, Clusters &c)
+{
+    if (host_finish_wanted()) {
+        if (cluster_on_host(mode, 0, c, [&](auto take) {
+                return tri_edge_blocks(r.gpu, r.t, r.n, r.kmer, r.d_max, [&](const vector<mg_edge> &edges) {
+                    mg_pair pr;
+                    for (const mg_edge &e : edges)
+                        if (finish_edge(e, r.lengths[e.row], r.lengths[e.col], r.kmer, r.kspace, r.p_max, pr)) take(e, pr);
+                });
+            }))
+            return 1;
+        r.clk.lap(kClusterLaps[mode][0].host);
+        return 0;
+    }
+    uint64_t count = 0, n_clusters = 0, n_edges = 0;
+    int rc = MG_OK;
+    switch (mode) {
+    case kSingle: rc = mg_cluster_tri_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.lab.data(), &n_clusters, &n_edges); break;
+    case kGreedy: rc = mg_cluster_tri_greedy_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.lab.data(), &n_clusters, &n_edges); break;
+    case kNearest: rc = mg_cluster_tri_nearest_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.lab.data(), &n_clusters, &n_edges); break;
+    case kMedoid: rc = mg_cluster_tri_medoid_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.lab.data(), c.med.data(), nullptr, &n_clusters, &n_edges); break;
+    case kForest:
+        c.forest.resize(r.n - 1);
+        rc = mg_cluster_tri_forest_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.forest.data(), c.forest.size(), &count, nullptr, &n_clusters, &n_edges);
+        break;
+    }
+    if (rc != MG_OK) return report_error(r.gpu);
+    c.forest.resize(count);
+    r.clk.lap(kClusterLaps[mode][0].device);
     return 0;
 }
 
@@ -1871,9 +1993,11 @@ bool read_earlier(const string &path, Earlier &e)
 // the first L sketches are one table, the rest a second one (mg_cluster_extend_host).  -R: only the earlier representatives are
 // uploaded beside the new sketches -- edges to earlier members decide nothing -- and the indices are mapped back
 // (mg_cluster_extend_greedy_host with ref_rep == NULL).  MASH_AMD_HOST_FINISH=1 takes the edges of the host calls of `dist -d` and
-// `triangle -E -d` over the same two tables and does the unions, or the walk, here.
-int cluster_extend(Gpu &gpu, const SketchSet &set, const Earlier &old, bool greedy, double d_max, double p_max, StageClock &clk, vector<uint32_t> &lab)
+// `triangle -E -d` over the same two tables, as edges between inputs, to cluster_on_host.
+int cluster_extend(Gpu &gpu, const SketchSet &set, const Earlier &old, ClusterMode mode, double d_max, double p_max, StageClock &clk, Clusters &c)
 {
+    vector<uint32_t> &lab = c.lab;
+    const bool greedy = mode == kGreedy;
     const uint64_t n = set.refs.size(), L = old.id.size(), m = n - L;
     vector<uint32_t> ref_rows, qry_rows;     // the inputs behind the rows of the two tables
     for (uint64_t i = 0; i < L; i++)
@@ -1895,49 +2019,30 @@ int cluster_extend(Gpu &gpu, const SketchSet &set, const Earlier &old, bool gree
             if (mg_cluster_extend_greedy_host(gpu.ctx, tr, tq, nullptr, kmer, kspace, d_max, p_max, rep.data(), &n_clusters, &n_edges) != MG_OK)
                 return report_error(gpu);
             for (uint64_t q = 0; q < m; q++) lab[L + q] = input_of(rep[q]);
-            clk.lap("compare+mark+append (new x representatives, new x new)+rounds+assign+copy");
         } else {
             if (mg_cluster_extend_host(gpu.ctx, tr, tq, old.label.data(), kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges) != MG_OK)
                 return report_error(gpu);
-            clk.lap("seed+compare+mark+union (new x old, new x new)+label+copy");
         }
+        clk.lap(kClusterLaps[mode][1].device);
         return 0;
     }
-    for (uint64_t i = L; i < n; i++) lab[i] = (uint32_t)i;
-    auto find = [&](uint32_t x) { while (lab[x] != x) { lab[x] = lab[lab[x]]; x = lab[x]; } return x; };
-    vector<vector<uint32_t>> smaller(greedy ? m : 0);          // -R: per new sketch its neighbours with a smaller index, as inputs
-    auto take = [&](uint32_t hi, uint32_t lo) {                 // an edge between inputs, hi a new one
-        if (greedy) { smaller[hi - L].push_back(lo); return; }
-        const uint32_t a = find(hi), b = find(lo);
-        if (a != b) lab[std::max(a, b)] = std::min(a, b);
-    };
-    vector<mg_edge> edges;
-    mg_pair pr;
-    if (nref)
-        for (Blocks b(0, m, kDistFilteredPairs, nref); b.next();) {
-            if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
-                    return mg_compare_rect_filter_host(gpu.ctx, tr, tq, b.r0, b.r1, kmer, d_max, o, cap, cnt); }))
+    // new x earlier (with -R: x the earlier representatives), then new x new; the walk and the unions go on from the earlier labels
+    if (cluster_on_host(mode, L, c, [&](auto take) {
+            mg_pair pr;
+            if (nref && rect_edge_blocks(gpu, tr, tq, nref, m, kmer, d_max, [&](const vector<mg_edge> &edges) {
+                    for (const mg_edge &e : edges)
+                        if (finish_edge(e, len_ref[e.col], len_qry[e.row], kmer, kspace, p_max, pr))
+                            take(mg_edge{(uint32_t)(L + e.row), ref_rows[e.col], e.numer, e.denom}, pr);
+                }))
                 return 1;
-            for (const mg_edge &e : edges)
-                if (finish_edge(e, len_ref[e.col], len_qry[e.row], kmer, kspace, p_max, pr)) take((uint32_t)(L + e.row), ref_rows[e.col]);
-        }
-    for (Blocks b(1, m, kTriFilteredPairs); b.next();) {
-        if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
-                return mg_compare_tri_filter_host(gpu.ctx, tq, b.r0, b.r1, kmer, d_max, o, cap, cnt); }))
-            return 1;
-        for (const mg_edge &e : edges)
-            if (finish_edge(e, len_qry[e.row], len_qry[e.col], kmer, kspace, p_max, pr))
-                take((uint32_t)(L + std::max(e.row, e.col)), (uint32_t)(L + std::min(e.row, e.col)));
-    }
-    if (greedy) {
-        // the walk goes on in input order: lab[j] == j says that j, decided before i, is a representative
-        for (uint64_t i = L; i < n; i++)
-            for (const uint32_t j : smaller[i - L])
-                if (lab[j] == j && (lab[i] == i || j < lab[i])) lab[i] = j;
-    } else {
-        for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
-    }
-    clk.lap(greedy ? "compare+filter+copy (new x representatives, new x new)+walk" : "compare+filter+copy (new x old, new x new)+union");
+            return tri_edge_blocks(gpu, tq, m, kmer, d_max, [&](const vector<mg_edge> &edges) {
+                for (const mg_edge &e : edges)
+                    if (finish_edge(e, len_qry[e.row], len_qry[e.col], kmer, kspace, p_max, pr))
+                        take(mg_edge{(uint32_t)(L + e.row), (uint32_t)(L + e.col), e.numer, e.denom}, pr);
+            });
+        }))
+        return 1;
+    clk.lap(kClusterLaps[mode][1].host);
     return 0;
 }
 
@@ -1995,30 +2100,18 @@ int cmd_cluster(int argc, const char **argv)
                 "            or -A (the weights between earlier inputs are not among the pairs -A compares).\n\n";
         return 0;
     }
-    const bool comment = c.o("comment").active, nearest = c.o("best").active, greedy = c.o("representatives").active || nearest;
-    const bool forest = c.o("tree").active, extend = c.o("assign").active;
+    const bool comment = c.o("comment").active, extend = c.o("assign").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
-    const bool medoid = c.o("medoid").active;
-    for (const char *other : {"representatives", "best", "tree", "assign"}) {
-        if (!medoid || !c.o(other).active) continue;
-        cerr << "ERROR: -" << c.o("medoid").id << " and -" << c.o(other).id << " cannot be given together"
-             << (string(other) == "assign" ? " (the weights between earlier inputs are not among the pairs -A compares)." : ".") << endl;
-        return 1;
-    }
-    if (nearest && forest) {
-        cerr << "ERROR: -" << c.o("best").id << " and -" << c.o("tree").id << " cannot be given together." << endl;
-        return 1;
-    }
-    if (nearest && extend) {
-        cerr << "ERROR: -" << c.o("best").id << " and -" << c.o("assign").id << " cannot be given together (a new representative can be nearer to an earlier member)." << endl;
-        return 1;
-    }
-    if (forest && greedy) {
-        cerr << "ERROR: -" << c.o("tree").id << " and -" << c.o("representatives").id << " cannot be given together." << endl;
-        return 1;
-    }
-    if (forest && extend) {
-        cerr << "ERROR: -" << c.o("tree").id << " and -" << c.o("assign").id << " cannot be given together." << endl;
+    // what cannot be given together, in order of precedence: the first row that matches is the one reported
+    static const struct { const char *a, *b, *why; } refusals[] = {
+        {"medoid", "representatives", ""}, {"medoid", "best", ""}, {"medoid", "tree", ""},
+        {"medoid", "assign", " (the weights between earlier inputs are not among the pairs -A compares)"},
+        {"best", "tree", ""}, {"best", "assign", " (a new representative can be nearer to an earlier member)"},
+        {"tree", "representatives", ""}, {"tree", "assign", ""},
+    };
+    for (const auto &x : refusals) {
+        if (!c.o(x.a).active || !c.o(x.b).active) continue;
+        cerr << "ERROR: -" << c.o(x.a).id << " and -" << c.o(x.b).id << " cannot be given together" << x.why << "." << endl;
         return 1;
     }
     if (d_max >= 1.0 && p_max >= 1.0) {
@@ -2028,6 +2121,8 @@ int cmd_cluster(int argc, const char **argv)
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // as `mash triangle` (CommandTriangle.cpp:74-77)
+    const ClusterMode mode = c.o("tree").active ? kForest : c.o("medoid").active ? kMedoid : c.o("best").active ? kNearest
+                             : c.o("representatives").active ? kGreedy : kSingle;
     Earlier old;
     if (extend && !read_earlier(c.o("assign").arg, old)) return 1;           // (before a device is opened)
     Gpu gpu;
@@ -2035,13 +2130,14 @@ int cmd_cluster(int argc, const char **argv)
     init_from_files(gpu, set, input_files(c), p, 1);
     const KmerWarning w = scan_kmer_warning(set);
     const uint64_t n = set.refs.size();
+    auto label = [&](uint64_t i) -> const string & { return comment ? set.refs[i].comment : set.refs[i].name; };      // (TriRun::label, for -A too)
     if (extend) {
         if (old.id.size() > n) {
             cerr << "ERROR: " << c.o("assign").arg << " has " << old.id.size() << " lines, but there are only " << n << " input sequences." << endl;
             return 1;
         }
         for (uint64_t i = 0; i < old.id.size(); i++) {
-            const string &id = comment ? set.refs[i].comment : set.refs[i].name;
+            const string &id = label(i);
             if (id == old.id[i]) continue;
             cerr << "ERROR: Line " << (i + 1) << " of " << c.o("assign").arg << " is about \"" << old.id[i] << "\", but input " << (i + 1) << " is \"" << id
                  << "\": the earlier inputs must come first, in the same order." << endl;
@@ -2049,110 +2145,37 @@ int cmd_cluster(int argc, const char **argv)
         }
     }
     if (n == 0) return 0;
-    if (forest) {
-        TriRun run(gpu, set, comment, true, 0, d_max, p_max);
-        if (cluster_forest(run)) return 1;
-        run.dt.reset();                                          // (inside the "teardown" lap, as the later lines)
+    Clusters found{vector<uint32_t>(n), vector<uint32_t>(mode == kMedoid ? n : 0), {}};
+    auto print_clusters = [&](FastOut &out) {
+        // label = the cluster's first member: numbers in order of first appearance are numbers by ascending label
+        const vector<uint32_t> &lab = found.lab, &med = found.med;
+        vector<uint32_t> number(n, 0), size(n, 0);
+        uint32_t next = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            if (lab[i] == i) number[i] = ++next;
+            size[lab[i]]++;
+        }
+        for (uint64_t i = 0; i < n; i++) {
+            out << number[lab[i]] << '\t' << size[lab[i]] << '\t' << label(i);
+            if (mode == kNearest) out << '\t' << label(lab[i]);
+            if (mode == kMedoid) out << '\t' << label(med[i]);
+            out.eol();
+        }
+    };
+    if (extend) {
+        StageClock clk;                                          // (-A uploads two tables of its own, inside its first lap)
+        FastOut out;
+        if (cluster_extend(gpu, set, old, mode, d_max, p_max, clk, found)) return 1;
+        print_clusters(out);
+        clk.lap("format+write");
         return finish_run(set, w, p.reads);
     }
-    vector<uint64_t> lengths;
-    DTable dt(extend ? nullptr : upload_all(gpu, set, set.p.sketch_size, &lengths));      // (-A uploads two tables of its own)
-    mg_table *t = extend ? nullptr : mg_dtable_local(dt.get(), 0);                        // (several devices selected: the first one's replica)
-    const double kspace = set.kmer_space();
-    StageClock clk;
-    vector<uint32_t> lab(n), med(medoid ? n : 0);
-    if (extend) {
-        if (cluster_extend(gpu, set, old, greedy, d_max, p_max, clk, lab)) return 1;
-    } else if (medoid && !host_finish_wanted()) {
-        uint64_t n_clusters = 0, n_edges = 0;
-        if (mg_cluster_tri_medoid_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), med.data(), nullptr, &n_clusters, &n_edges) != MG_OK)
-            return report_error(gpu);
-        clk.lap("compare+mark+union+score+label+pick+copy");
-    } else if (!host_finish_wanted()) {
-        uint64_t n_clusters = 0, n_edges = 0;
-        const int rc = nearest  ? mg_cluster_tri_nearest_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
-                       : greedy ? mg_cluster_tri_greedy_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges)
-                                : mg_cluster_tri_host(gpu.ctx, t, set.p.kmer, kspace, d_max, p_max, lab.data(), &n_clusters, &n_edges);
-        if (rc != MG_OK) return report_error(gpu);
-        clk.lap(nearest ? "compare+mark+append+rounds+nearest+copy" : greedy ? "compare+mark+append+rounds+assign+copy" : "compare+mark+union+label+copy");
-    } else {
-        for (uint64_t i = 0; i < n; i++) lab[i] = (uint32_t)i;
-        auto find = [&](uint32_t x) { while (lab[x] != x) { lab[x] = lab[lab[x]]; x = lab[x]; } return x; };
-        vector<mg_edge> edges;
-        vector<vector<uint32_t>> smaller(greedy ? n : 0);      // -R: per sketch its neighbours with a smaller index
-        vector<mg_edge> kept;                                  // -B: every edge with its counts
-        vector<uint64_t> score(medoid ? n : 0);                // -M: per sketch the sum of its edges' weights
-        for (Blocks b(1, n, kTriFilteredPairs); b.next();) {
-            if (!fetch_list(gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *cnt) {
-                    return mg_compare_tri_filter_host(gpu.ctx, t, b.r0, b.r1, set.p.kmer, d_max, o, cap, cnt); }))
-                return 1;
-            for (const mg_edge &e : edges) {
-                mg_pair pr;
-                if (!finish_edge(e, lengths[e.row], lengths[e.col], set.p.kmer, kspace, p_max, pr)) continue;
-                if (greedy) {
-                    smaller[std::max(e.row, e.col)].push_back(std::min(e.row, e.col));
-                    if (nearest) kept.push_back(e);
-                    continue;
-                }
-                const uint32_t a = find(e.row), b2 = find(e.col);
-                if (a != b2) lab[std::max(a, b2)] = std::min(a, b2);
-                if (medoid) {
-                    const uint64_t wt = mg::medoid_weight(e.numer, e.denom);
-                    score[e.row] += wt;
-                    score[e.col] += wt;
-                }
-            }
-        }
-        if (greedy) {
-            // the walk in input order: lab[j] == j says that j, decided before i, is a representative
-            for (uint64_t i = 0; i < n; i++)
-                for (const uint32_t j : smaller[i])
-                    if (lab[j] == j && (lab[i] == i || j < lab[i])) lab[i] = j;
-            if (nearest) {
-                // the walk has named the representatives; a member now takes the best of ALL its edges to one, either end of the
-                // pair: mg::forest_before with the representative in the row pair's place (equal fractions: the smaller one)
-                vector<uint8_t> is_rep(n);
-                vector<const mg_edge *> best(n, nullptr);
-                for (uint64_t i = 0; i < n; i++) is_rep[i] = lab[i] == i;
-                for (const mg_edge &e : kept) {
-                    if (is_rep[e.row] == is_rep[e.col]) continue;
-                    const uint32_t member = is_rep[e.row] ? e.col : e.row, r = is_rep[e.row] ? e.row : e.col;
-                    const mg_edge *b2 = best[member];
-                    if (!b2 || mg::forest_before(e.numer, e.denom, r, b2->numer, b2->denom, lab[member])) {
-                        best[member] = &e;
-                        lab[member] = r;
-                    }
-                }
-            }
-        } else {
-            for (uint64_t i = 0; i < n; i++) lab[i] = find((uint32_t)i);
-            if (medoid) {
-                // per cluster the largest score, met first at its smallest row: the walk is in index order and only a larger score moves it
-                vector<uint32_t> top(n);
-                for (uint64_t i = 0; i < n; i++) top[i] = (uint32_t)i;
-                for (uint64_t i = 0; i < n; i++)
-                    if (score[i] > score[top[lab[i]]]) top[lab[i]] = (uint32_t)i;
-                for (uint64_t i = 0; i < n; i++) med[i] = top[lab[i]];
-            }
-        }
-        clk.lap(medoid ? "compare+filter+copy+union+score+pick" : nearest ? "compare+filter+copy+walk+nearest" : greedy ? "compare+filter+copy+walk" : "compare+filter+copy+union");
-    }
-    // label = the cluster's first member: numbers in order of first appearance are numbers by ascending label
-    vector<uint32_t> number(n, 0), size(n, 0);
-    uint32_t next = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        if (lab[i] == i) number[i] = ++next;
-        size[lab[i]]++;
-    }
-    FastOut out;
-    for (uint64_t i = 0; i < n; i++) {
-        out << number[lab[i]] << '\t' << size[lab[i]] << '\t' << (comment ? set.refs[i].comment : set.refs[i].name);
-        if (nearest) out << '\t' << (comment ? set.refs[lab[i]].comment : set.refs[lab[i]].name);
-        if (medoid) out << '\t' << (comment ? set.refs[med[i]].comment : set.refs[med[i]].name);
-        out.eol();
-    }
-    clk.lap("format+write");
-    dt.reset();                                                  // (inside the "teardown" lap, as the later lines)
+    TriRun run(gpu, set, comment, true, 0, d_max, p_max);
+    if (cluster_table(run, mode, found)) return 1;
+    if (mode == kForest) tri_emit_results(run, found.forest);
+    else print_clusters(run.out);
+    run.clk.lap("format+write");
+    run.dt.reset();                                              // (inside the "teardown" lap, as the later lines)
     return finish_run(set, w, p.reads);
 }
 
