@@ -246,13 +246,26 @@ hipError_t dense_sort_universes(const unsigned long long *key, const uint32_t *v
 //    in one gap is flagged (bit 15 of the word's cx entry) and resolved from the list instead.  (Rounds 4-5a kept three
 //    unary masks -- up to three extras per gap.  Loosely related clusters have dozens of extras per word: every word of
 //    C3 was flagged, and the list walk was 3 000 instructions per pair.)
+//  * whether any entry of the row is left with a non-empty run -- a partner outside the group -- goes to row_any[row]
+//    (SparseArgs::row_any: discovery leaves a row at once whose flag is 0).  K5 set the flag from the unclipped runs; this
+//    store comes behind it on the stream.
 constexpr uint32_t DN_CX_MASK = 0x7FFFu, DN_CX_FLAG = 0x8000u;           // cx: a count (<= s <= 16384) | flag
+
+// the kernel's last argument (a bare ul_in_lds converts: no flags wanted)
+struct DnEncodeOpts {
+    uint32_t ul_in_lds;                // the universe is staged in LDS
+    uint32_t *row_any;                 // [n] or nullptr
+#ifdef __HIPCC__
+    __host__ __device__
+#endif
+    DnEncodeOpts(uint32_t ul, uint32_t *flags = nullptr) : ul_in_lds(ul), row_any(flags) {}
+};
 
 template <uint32_t DN_EK>                                  // entries a work-item takes at a time
 __global__ __launch_bounds__(256) void dn_encode_kernel(const uint32_t *off, const uint32_t *code_img, uint32_t *pos_img, uint32_t rs,
                                                         const uint32_t *grp_of, const DenseGroup *groups, const uint32_t *ulist,
                                                         const uint32_t *upos, unsigned long long *gdata, uint32_t wstride, uint16_t *ext,
-                                                        uint32_t xs, uint32_t n, uint32_t ul_in_lds)
+                                                        uint32_t xs, uint32_t n, DnEncodeOpts opt)
 {
     MG_DYN_SHARED(uint32_t, lds);          // [2 W] mask halves, [W + 1] extras per word, [16 W] extras per gap (bytes), [W] overflow flags, [8 W] plane halves, [8] scratch, [u] the universe
     // (the hardware deals workgroups to the eight XCDs round-robin; a row's words go to one lane of its block's lines, eight
@@ -270,13 +283,15 @@ __global__ __launch_bounds__(256) void dn_encode_kernel(const uint32_t *off, con
     uint32_t *ull = lds + 28u * wstride + 9u;
     for (uint32_t i = tid; i < 28u * W + 1u; i += 256u) lds[i] = 0;
     const uint32_t *ulg = ulist + G.ustart, *up = upos + G.ustart;
-    if (ul_in_lds)
+    if (opt.ul_in_lds)
         for (uint32_t i = tid; i < u; i += 256u) ull[i] = ulg[i];
-    const uint32_t *ul = ul_in_lds ? ull : ulg;
+    const uint32_t *ul = opt.ul_in_lds ? ull : ulg;
+    if (tid == 0) scr[4] = 0;                            // the row's flag (scr[0 .. 3]: the scans')
     __syncthreads();
     const uint32_t cnt = off[row + 1] - off[row];
     uint16_t *xrow = ext + (uint64_t)(G.xrow0 + (row - G.g0)) * xs;
     uint32_t nx = 0;                                     // extras written so far (uniform)
+    bool any = false;                                    // an entry of this work-item keeps a non-empty run [gs, end)
     if constexpr (DN_EK == 1) {
         // sketches of a thousand values: an entry per work-item, located in the universe by bisection (a round of 256 consecutive
         // entries reads and writes whole lines; with eight entries per work-item half a workgroup would idle)
@@ -286,7 +301,7 @@ __global__ __launch_bounds__(256) void dn_encode_kernel(const uint32_t *off, con
             bool extra = false;
             if (p < cnt) {
                 const uint64_t img = (uint64_t)row * rs + p;
-                const uint32_t gs = code_img[img] >> 1;
+                const uint32_t code = code_img[img], gs = code >> 1;
                 uint32_t lo = 0, hi = u;                      // lower bound of gs in the universe
                 while (lo < hi) {
                     const uint32_t mid = (lo + hi) >> 1;
@@ -295,9 +310,14 @@ __global__ __launch_bounds__(256) void dn_encode_kernel(const uint32_t *off, con
                 idx = lo;
                 if (lo < u && ul[lo] == gs) {
                     atomicOr(&mask32[idx >> 5], 1u << (idx & 31u));
-                    pos_img[img] = up[idx];                  // (the leader itself: its own position again)
+                    const uint32_t end = up[idx];            // (the leader itself: its own position again)
+                    pos_img[img] = end;
+                    any |= end != gs;
                 } else {
                     extra = true;
+                    // (its run stays as it is, and is empty if nobody else holds the value -- the code's low bit; else the one
+                    //  load the flag costs: a load for every extra made the kernel a fifth slower on clustered sketches)
+                    if (opt.row_any && (code & 1u)) any |= pos_img[img] != gs;
                 }
             }
             // extras keep their order (entries ascend, so gaps ascend): block-wide exclusive scan of the flags
@@ -374,6 +394,7 @@ __global__ __launch_bounds__(256) void dn_encode_kernel(const uint32_t *off, con
                                 if (j == nxt) xidx[j] = pos;  // (static indices: the array stays in registers)
                             nxt++;
                         }
+                        any |= pv[e] != gs;                  // (clipped or not: what discovery will read)
                     }
                 }
                 // (behind the row's last entry the position image holds nothing anybody reads: written back as it was read)
@@ -407,7 +428,9 @@ __global__ __launch_bounds__(256) void dn_encode_kernel(const uint32_t *off, con
             __syncthreads();                                 // scr is reused
         }
     }
+    if (__ballot(any) != 0 && lane == 0) atomicOr(&scr[4], 1u);
     __syncthreads();
+    if (opt.row_any && tid == 0) opt.row_any[row] = scr[4];
     const uint32_t jb = (row - G.g0) >> 7, bl = (row - G.g0) & 127u;
     const uint64_t bw = dense_block_words(W);
     unsigned long long *blk = gdata + G.data_off + (uint64_t)jb * bw;
@@ -447,7 +470,7 @@ __global__ __launch_bounds__(256) void dn_encode_kernel(const uint32_t *off, con
 
 hipError_t launch_dense_encode(const uint32_t *off, const uint32_t *code_img, uint32_t *pos_img, uint32_t rs, const uint32_t *grp_of,
                                const DenseGroup *groups, const uint32_t *ulist, const uint32_t *upos, unsigned long long *gdata,
-                               uint16_t *ext, uint32_t xs, uint32_t n, uint32_t wmax, hipStream_t stream, int ul_mode)
+                               uint16_t *ext, uint32_t xs, uint32_t n, uint32_t wmax, hipStream_t stream, int ul_mode, uint32_t *row_any)
 {
     if (n == 0) return hipSuccess;
     // The universe in LDS while that leaves a CU several workgroups: a universe of 15 000 values (C5: 86 KB with the masks) made it
@@ -462,7 +485,7 @@ hipError_t launch_dense_encode(const uint32_t *off, const uint32_t *code_img, ui
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((n + 63u) & ~63u), dim3(256), smem, stream, off, code_img, pos_img, rs, grp_of, groups, ulist, upos, gdata, wmax, ext, xs,
-                           n, ul_in_lds ? 1u : 0u);
+                           n, DnEncodeOpts(ul_in_lds ? 1u : 0u, row_any));
         return hipGetLastError();
     };
     return rs >= 4096u ? go(dn_encode_kernel<8>) : go(dn_encode_kernel<1>);

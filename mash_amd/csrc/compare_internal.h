@@ -87,6 +87,9 @@ struct SparseArgs {
     const uint32_t *lo_img;
     const uint32_t *hi_img;
     uint32_t lo_shift;
+    // triangle over an index built by tiles: per row of the images, != 0 if one of its entries has a non-empty run (written by
+    // K5, again by dn_encode_kernel for the rows of dense groups).  nullptr: not known, discovery scans the row's segment
+    const uint32_t *row_any = nullptr;
     const uint32_t *off;           // row side: compact entry offsets (triangle: the table's; rect: the queries' from q_begin)
     const uint32_t *row_img;       // row side code image (triangle: the table's; rect: query codes)
     const uint32_t *col_img;       // column side code image (codes 2 * start position of the value's group in the sorted index)
@@ -231,7 +234,8 @@ hipError_t dense_sort_universes(const unsigned long long *key, const uint32_t *v
                                 uint32_t group_bits, hipStream_t stream);
 hipError_t launch_dense_encode(const uint32_t *off, const uint32_t *code_img, uint32_t *pos_img, uint32_t rs, const uint32_t *grp_of,
                                const DenseGroup *groups, const uint32_t *ulist, const uint32_t *upos, unsigned long long *gdata,
-                               uint16_t *ext, uint32_t xs, uint32_t n, uint32_t wmax, hipStream_t stream, int ul_mode = -1);
+                               uint16_t *ext, uint32_t xs, uint32_t n, uint32_t wmax, hipStream_t stream, int ul_mode = -1,
+                               uint32_t *row_any = nullptr);     // [n] SparseArgs::row_any of the grouped rows, from their clipped runs
 size_t dense_pairs_lds(uint32_t W, uint32_t rows);
 uint32_t dense_rows_per_tile(uint64_t wave_rows);
 uint32_t dense_max_words();

@@ -746,11 +746,14 @@ __global__ __launch_bounds__(256) void sp_discover_kernel(SparseArgs a)
     const uint32_t W = (ncols + 31u) >> 5;
     const uint32_t er = (DEDUP && a.triangle) ? a.rep[row] : row;      // the row whose index entries speak for this one
     const bool copy = DEDUP && a.triangle && er != row;
+    // a row none of whose values is held by a row below it (most rows of a collection of unrelated genomes, and the rows of a
+    // dense group whose partners are all inside it) has nothing to mark: neither the bitmap (n / 8 bytes of LDS to clear and
+    // to scan) nor the rest is needed.  Whoever wrote the images knows that already (a.row_any: 4 bytes, read before the row's
+    // offsets -- a row without entries has no flag); otherwise the row's segment of both images is scanned for it
+    if (!copy && a.row_any != nullptr && a.row_any[er] == 0u) return;       // uniform
     const uint32_t cnt = a.off[er + 1] - a.off[er];
     if (cnt == 0 || ncols == 0) return;                  // uniform
-    if (!copy) {
-        // a row none of whose values is held by a row below it (most rows of a collection of unrelated genomes) has
-        // nothing to mark: neither the bitmap (n / 8 bytes of LDS to clear and to scan) nor the rest is needed
+    if (!copy && a.row_any == nullptr) {
         int any = 0;
         for (uint32_t p = tid; p < cnt; p += 256u) {
             const uint64_t at = (uint64_t)er * a.rs_row + p;

@@ -745,6 +745,9 @@ int SparseJobRun::row_side()
         a.lo_img = ix->code_img;
         a.hi_img = ix->pos_img;
         a.lo_shift = 1;
+        // the rows' flags speak of exactly these images (K5 and the dense groups' encode wrote both); the general sort writes none
+        const char *flags_opt = ctx_opt(ctx, "MASHGPU_DISCOVER_ROWFLAGS");
+        a.row_any = ix->by_tiles && !(flags_opt && atoi(flags_opt) == 0) ? ix->row_any : nullptr;
         a.off = ix->off;
         a.row_img = ix->code_img;
         a.rs_row = ix->rs;
@@ -794,6 +797,7 @@ int SparseJobRun::row_side()
         a.lo_img = q_lo;
         a.hi_img = q_hi;
         a.lo_shift = 0;
+        a.row_any = nullptr;                                  // (the located runs are this call's own: nobody has flagged them)
         a.off = q_off;
         a.row_img = q_img;
         a.rs_row = rsq;
@@ -930,6 +934,8 @@ int SparseJobRun::discover()
     want = first ? std::max<uint64_t>(ix->cand_cap, std::min<uint64_t>(pairs, std::min<uint64_t>(std::max<uint64_t>((uint64_t)ix->E / 2, 1u << 16), 1ull << 27)))
                           : plan->cand;
     nothing_to_find = triangle && ix->one_class != 0;      // nothing but copies of one sketch: every pair is inside the class
+    if (!nothing_to_find && ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+        fprintf(stderr, "compare discover: %s\n", a.row_any ? "rows without partners known by their flags" : "every row's segment scanned");
     for (int attempt = 0; !nothing_to_find; attempt++) {
         rc = ensure_lists(want);
         if (rc != MG_OK) return rc;

@@ -214,7 +214,7 @@ struct SparseIndexBuild {
     void drop()                                             // the retained buffers back to the pool: this index is not to be used
     {
             for (void **q : {(void **)&sp->off, (void **)&sp->keys_sorted, (void **)&sp->gend, (void **)&sp->sorted_rows, (void **)&sp->code_img,
-                             (void **)&sp->pos_img, (void **)&sp->short_rows, (void **)&sp->short_cnt, (void **)&sp->counters, (void **)&sp->order,
+                             (void **)&sp->pos_img, (void **)&sp->row_any, (void **)&sp->short_rows, (void **)&sp->short_cnt, (void **)&sp->counters, (void **)&sp->order,
                              (void **)&sp->rep, (void **)&sp->cls_of, (void **)&sp->cls_off, (void **)&sp->cls_rows, (void **)&sp->cls_first})
                 if (*q) { ctx_free(ctx, *q); *q = nullptr; }
     }
@@ -241,7 +241,7 @@ struct SparseIndexBuild {
         const mg::IxLeaders lv = lead.view(d_lead_rows);
         return mg::index_build_mapped(plan, H, rowmap, sp->off, d_lb, d_tcnt, w.start, w.big, w.pk, w.tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
                                sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf, lead_ready ? &lv : nullptr,
-                               ctx->stream, stages);
+                               ctx->stream, stages, sp->row_any);
     }
     // The bucket sorts: values, rows, groups, statistics, leaders are final behind them.  The leaders' lists are made one; their
     // totals come back with the statistics -- the host's after the caller's wait.
@@ -272,6 +272,7 @@ struct SparseIndexBuild {
     bool choose_groups(const std::vector<uint32_t> &us, const std::vector<uint32_t> &ue);
     int encode_groups();
     int dense_groups();
+    int check_row_flags();
     int run();
 };
 
@@ -629,7 +630,7 @@ int SparseIndexBuild::lay_out()
               (!want_order || (key64_a.alloc(n) == hipSuccess && key64_b.alloc(n) == hipSuccess));
     // retained buffers
     ok = ok && take(&sp->off, n + 1) && take(&sp->keys_sorted, E) && take(&sp->gend, E) && take(&sp->sorted_rows, E) &&
-         take(&sp->code_img, (size_t)n * sp->rs + 64) && take(&sp->pos_img, (size_t)n * sp->rs) && take(&sp->counters, 4) &&
+         take(&sp->code_img, (size_t)n * sp->rs + 64) && take(&sp->pos_img, (size_t)n * sp->rs) && take(&sp->row_any, n) && take(&sp->counters, 4) &&
          (!want_order || take(&sp->order, n));
     const size_t nshort = sp->short_rows_host.size();
     short_cnt.assign(nshort, 0);
@@ -931,7 +932,8 @@ int SparseIndexBuild::encode_groups()
     if (e == hipSuccess) e = hipMemcpyAsync(sp->grp_of, grp_of_h.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
         e = mg::launch_dense_encode(sp->off, sp->code_img, sp->pos_img, sp->rs, sp->grp_of, sp->dgroups, sp->ulist, sp->upos, sp->gdata, sp->ext, sp->dn_xs,
-                                    (uint32_t)n, sp->dn_wmax, ctx->stream, ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS") ? atoi(ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS")) : -1);
+                                    (uint32_t)n, sp->dn_wmax, ctx->stream, ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS") ? atoi(ctx_opt(ctx, "MASHGPU_DENSE_UL_LDS")) : -1,
+                                    sp->by_tiles ? sp->row_any : nullptr);
     // (no wait here: what the copies above read -- dgroups_host and the rows' group map -- lives in the index, what
     //  comes next is queued on the same stream, and a fault shows at its wait)
     sp->grp_of_host.swap(grp_of_h);
@@ -980,6 +982,26 @@ int SparseIndexBuild::dense_groups()
     return MG_OK;
 }
 
+// MASHGPU_SPARSE_INDEX=verify: the rows' flags (K5's, and the encode's for the rows of dense groups) against the images as they
+// stand now, clipped runs included
+int SparseIndexBuild::check_row_flags()
+{
+    if (!ix_verify || !sp->by_tiles || !sp->usable) return MG_OK;
+    DevBuf<unsigned long long> d_diff(ctx);
+    if (d_diff.alloc(2) != hipSuccess) return no_memory();
+    unsigned long long diff[2] = {0, ~0ull};
+    hipError_t e = hipMemcpyAsync(d_diff, diff, sizeof diff, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = mg::index_verify_row_flags(sp->off, sp->code_img, sp->pos_img, sp->rs, sp->row_any, (uint32_t)n, d_diff, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(diff, d_diff, sizeof diff, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return lost(e);
+    if (diff[0]) {
+        sp->usable = false;
+        return fail(ctx, MG_ERR_INVALID, "index verify: row flags -- " + std::to_string(diff[0]) + " differ, first at row " + std::to_string(diff[1]));
+    }
+    return MG_OK;
+}
+
 int SparseIndexBuild::run()
 {
     int rc = MG_OK;
@@ -990,7 +1012,8 @@ int SparseIndexBuild::run()
     if ((rc = build_by_tiles()) != MG_OK || stop) return rc;
     if ((rc = build_by_sort()) != MG_OK || stop) return rc;
     if ((rc = check_build()) != MG_OK || stop) return rc;
-    return dense_groups();
+    if ((rc = dense_groups()) != MG_OK || stop) return rc;
+    return check_row_flags();
 }
 
 }  // namespace

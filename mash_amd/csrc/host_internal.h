@@ -163,6 +163,7 @@ struct mg_table {
         uint32_t *sorted_rows = nullptr;   // [E] row of every sorted position
         uint32_t *code_img = nullptr;      // [n * rs + 64] 2 x (first sorted position of the entry's value), padding 0xFFFFFFFF
         uint32_t *pos_img = nullptr;       // [n * rs] the entry's own sorted position
+        uint32_t *row_any = nullptr;       // [n] != 0: an entry of the row has code / 2 != position, a run for discovery (by_tiles only)
         uint32_t *order = nullptr;         // [n] rows in visiting order (see sp_row_key_kernel); nullptr: table order
         // dense groups (compare_dense.hip): runs of consecutive near-identical rows whose inner pairs are bit-mask arithmetic;
         // the index's runs are clipped for their rows, so discovery only sees partners outside a row's group

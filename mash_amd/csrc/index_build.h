@@ -77,19 +77,22 @@ size_t index_stat_scratch_bytes();
 // All buffers are the caller's.  lb / cnt / start / big / pk / tc: scratch of the plan's sizes; the rest as sparse_build_index
 // (compare_internal.h) -- on return (stream order) the index arrays are complete unless flags say otherwise.
 // *incidences, *max_group, *groups, flags[4]: zeroed by the caller.
+// row_any (nullptr: not wanted): [n], zeroed here in front of K5, which leaves != 0 for every row that has an entry with holders
+// below it (code / 2 != position: a non-empty run for the triangle's discovery, SparseArgs::row_any).
 // test knob: two entries of one value swapped behind the partition (the bucket sorts' order check must fire); done: 1 u32, device
 hipError_t index_debug_swap(const IxPlan &plan, void *pk, const void *start, uint32_t *done, hipStream_t stream);
 hipError_t index_build(const IxPlan &plan, const uint64_t *hashes, const uint32_t *off, void *lb, void *cnt, void *start, void *big, void *pk, void *tc,
                        uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of, uint32_t *code_img, uint32_t *pos_img,
                        void *stat_scratch, unsigned long long *incidences, uint32_t *max_group, uint32_t *groups, uint32_t *flags,
-                       const IxLeaders *leaders, hipStream_t stream, int stages = 7);
+                       const IxLeaders *leaders, hipStream_t stream, int stages = 7, uint32_t *row_any = nullptr);
 // The same with the table read IN PLACE through a row map: index row a is read at hashes + rowmap[a] * stride (nullptr: identity,
 // what index_build passes).  K0, K1 and K3 are the kernels that read the table; the packed word, the images and everything
 // behind K3 speak of INDEX rows and do not know of the map.
 hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *off, void *lb, void *cnt, void *start,
                               void *big, void *pk, void *tc, uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of,
                               uint32_t *code_img, uint32_t *pos_img, void *stat_scratch, unsigned long long *incidences, uint32_t *max_group,
-                              uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages = 7);
+                              uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages = 7,
+                              uint32_t *row_any = nullptr);
 // K0 ahead of the build, through the map: the window offsets of the index's rows into lb, the rows' entry counts taken from
 // cnt_table[rowmap[a]] (the TABLE's order -- the index's offsets need not exist yet).  The build then takes stage bit 8.
 hipError_t index_window_offsets(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *cnt_table, void *lb, hipStream_t stream);
@@ -116,5 +119,9 @@ hipError_t index_gather_rows(const IxPlan &plan, const uint64_t *hashes, const u
 // mode 0: all words, 1: where cond[i] == i, 2: where cond[i] != 0xFFFFFFFF
 hipError_t index_verify_words(const uint32_t *a, const uint32_t *b, const uint32_t *cond, uint32_t mode, uint64_t count, unsigned long long *out2,
                               hipStream_t stream);
+// ... and the rows' flags: out2[0] += rows r with (row_any[r] != 0) != (an entry p < cnt of row r has code_img / 2 != pos_img),
+// out2[1] = min(out2[1], the first such row)
+hipError_t index_verify_row_flags(const uint32_t *off, const uint32_t *code_img, const uint32_t *pos_img, uint32_t rs, const uint32_t *row_any, uint32_t n,
+                                  unsigned long long *out2, hipStream_t stream);
 
 }  // namespace mg

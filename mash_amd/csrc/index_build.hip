@@ -639,11 +639,15 @@ __global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, c
 // positions, neighbouring values -- neighbouring buckets, whose pieces of this block K3 wrote side by side, and the pieces
 // of the next block right behind them.  Pieces follow each other block by block, positions ascending, an XCD taking a
 // contiguous eighth of them.
+// row_any (nullptr: not wanted; zeroed by the caller): |= 1 for every row one of whose entries has holders below it -- position !=
+// group start, a non-empty run for discovery (SparseArgs::row_any).  The eight work-items of a (row, piece) vote with a
+// ballot and one of them sends the atomic, if there is anything to say: the values are in registers on their way out.
 constexpr uint32_t IX5_CH = 32;                           // positions of a piece
 constexpr uint32_t IX5_UNR = 4;                           // rows a work-item has in flight
 
 __global__ __launch_bounds__(256) void ix_images_kernel(IxGeom g, const uint32_t *__restrict__ off, const uint32_t *__restrict__ flags,
-                                                        const uint2 *__restrict__ tc, uint32_t *__restrict__ code_img, uint32_t *pos_img, uint32_t nchunk)
+                                                        const uint2 *__restrict__ tc, uint32_t *__restrict__ code_img, uint32_t *pos_img, uint32_t nchunk,
+                                                        uint32_t *__restrict__ row_any)
 {
     const uint32_t per = gridDim.x >> 3;
     const uint32_t q = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
@@ -671,8 +675,10 @@ __global__ __launch_bounds__(256) void ix_images_kernel(IxGeom g, const uint32_t
             sl_n[u][3] = src[3];
         }
     };
-    if (rsub < nrows) slots(rsub);
-    for (uint32_t rb = rsub; rb < nrows; rb += 32u * IX5_UNR) {          // (32 rows per sweep of the workgroup)
+    // (a wave's eight rows of a sweep go through the loop together, rb & ~7 being the first of them -- the ballot below is the
+    //  whole wave's; a row past the block's last has no entries: slots() gives it a count of 0 and the block's first line to load)
+    if ((rsub & ~7u) < nrows) slots(rsub);
+    for (uint32_t rb = rsub; (rb & ~7u) < nrows; rb += 32u * IX5_UNR) {  // (32 rows per sweep of the workgroup)
         uint32_t cnt[IX5_UNR];
         uint32_t sl[IX5_UNR][4];
 #pragma unroll
@@ -686,10 +692,11 @@ __global__ __launch_bounds__(256) void ix_images_kernel(IxGeom g, const uint32_t
         for (uint32_t u = 0; u < IX5_UNR; u++)
 #pragma unroll
             for (uint32_t e = 0; e < 4u; e++) cp[u][e] = tc[p0 + e < cnt[u] ? sl[u][e] : 0u];
-        if (rb + 32u * IX5_UNR < nrows) slots(rb + 32u * IX5_UNR);
+        if (((rb + 32u * IX5_UNR) & ~7u) < nrows) slots(rb + 32u * IX5_UNR);
 #pragma unroll
         for (uint32_t u = 0; u < IX5_UNR; u++) {
             const uint32_t r = rb + 32u * u;
+            bool any = false;
             if (r < nrows && p0 < g.rs) {
                 const uint64_t at = (uint64_t)(row0 + r) * g.rs + p0;
 #pragma unroll
@@ -697,8 +704,17 @@ __global__ __launch_bounds__(256) void ix_images_kernel(IxGeom g, const uint32_t
                     // (behind the row's last entry: the code image's padding -- larger than every code, so chunked loads past a
                     //  row's end are harmless --, the position image stays whatever it was)
                     code_img[at + e] = p0 + e < cnt[u] ? cp[u][e].x : 0xFFFFFFFFu;
-                    if (p0 + e < cnt[u]) pos_img[at + e] = cp[u][e].y;
+                    if (p0 + e < cnt[u]) {
+                        pos_img[at + e] = cp[u][e].y;
+                        any |= (cp[u][e].x >> 1) != cp[u][e].y;
+                    }
                 }
+            }
+            if (row_any != nullptr) {                         // uniform
+                // (the eight votes of this row out of the wave's half: a 64-bit shift by the lane cost four registers and a wave per SIMD)
+                const uint64_t votes = __ballot(any);
+                const uint32_t half = (tid & 32u) ? (uint32_t)(votes >> 32) : (uint32_t)votes;
+                if (quad == 0 && ((half >> (tid & 24u)) & 0xFFu) != 0) atomicOr(&row_any[row0 + r], 1u);
             }
         }
     }
@@ -1360,6 +1376,35 @@ hipError_t index_verify_words(const uint32_t *a, const uint32_t *b, const uint32
     return hipGetLastError();
 }
 
+// ... and the rows' flags against the finished images (behind the dense groups' encode, which clips runs and writes flags): a
+// wave per row says whether any entry has code / 2 != position.  out[0] = rows whose flag says otherwise -- 0 over a
+// non-empty run loses pairs, != 0 over empty runs only costs discovery its scan: both are counted --, out[1] = the first.
+__global__ __launch_bounds__(256) void ix_verify_row_flags_kernel(const uint32_t *off, const uint32_t *code_img, const uint32_t *pos_img, uint32_t rs,
+                                                                  const uint32_t *row_any, uint32_t n, unsigned long long *out)
+{
+    const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (row >= n) return;                                // uniform in the wave
+    const uint32_t cnt = off[row + 1u] - off[row];
+    bool any = false;
+    for (uint32_t p = lane; p < cnt; p += 64u) {
+        const uint64_t at = (uint64_t)row * rs + p;
+        any |= (code_img[at] >> 1) != pos_img[at];
+    }
+    const bool want = __ballot(any) != 0;
+    if (lane == 0 && want != (row_any[row] != 0u)) {
+        atomicAdd(&out[0], 1ull);
+        atomicMin(&out[1], (unsigned long long)row);
+    }
+}
+
+hipError_t index_verify_row_flags(const uint32_t *off, const uint32_t *code_img, const uint32_t *pos_img, uint32_t rs, const uint32_t *row_any, uint32_t n,
+                                  unsigned long long *out2, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(ix_verify_row_flags_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, off, code_img, pos_img, rs, row_any, n, out2);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side
 
@@ -1493,16 +1538,16 @@ hipError_t index_offsets_counts(const IxPlan &plan, const uint64_t *hashes, cons
 hipError_t index_build(const IxPlan &plan, const uint64_t *hashes, const uint32_t *off, void *lb_v, void *cnt_v, void *start_v, void *big_v, void *pk_v, void *tc_v,
                        uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of, uint32_t *code_img, uint32_t *pos_img,
                        void *stat_scratch, unsigned long long *incidences, uint32_t *max_group, uint32_t *groups, uint32_t *flags,
-                       const IxLeaders *leaders, hipStream_t stream, int stages)
+                       const IxLeaders *leaders, hipStream_t stream, int stages, uint32_t *row_any)
 {
     return index_build_mapped(plan, hashes, nullptr, off, lb_v, cnt_v, start_v, big_v, pk_v, tc_v, keys_sorted, sorted_rows, gend, gs_of, code_img, pos_img,
-                              stat_scratch, incidences, max_group, groups, flags, leaders, stream, stages);
+                              stat_scratch, incidences, max_group, groups, flags, leaders, stream, stages, row_any);
 }
 
 hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *off, void *lb_v, void *cnt_v, void *start_v,
                               void *big_v, void *pk_v, void *tc_v, uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of,
                               uint32_t *code_img, uint32_t *pos_img, void *stat_scratch, unsigned long long *incidences, uint32_t *max_group,
-                              uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages)
+                              uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages, uint32_t *row_any)
 {
     // (leaders: looked at by stage 2 only)
     if (!plan.ok) return hipErrorInvalidValue;
@@ -1547,7 +1592,12 @@ hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const 
     {
         const uint32_t nchunk = (g.rs + IX5_CH - 1u) / IX5_CH;
         const uint32_t pieces = 8u * ((g.nblk * nchunk + 7u) / 8u);
-        hipLaunchKernelGGL(ix_images_kernel, dim3(pieces), dim3(256), 0, stream, g, off, (const uint32_t *)flags, (const uint2 *)tc, code_img, pos_img, nchunk);
+        if (row_any != nullptr) {
+            e = hipMemsetAsync(row_any, 0, (size_t)g.n * 4u, stream);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(ix_images_kernel, dim3(pieces), dim3(256), 0, stream, g, off, (const uint32_t *)flags, (const uint2 *)tc, code_img, pos_img, nchunk,
+                           row_any);
     }
     return hipGetLastError();
 }

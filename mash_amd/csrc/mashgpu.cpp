@@ -345,7 +345,7 @@ static void table_drop_derived(mg_table *t)
             if (pl.dtiles) ctx_free(ctx, pl.dtiles);
         }
         for (void *q : {(void *)sp->off, (void *)sp->keys_sorted, (void *)sp->gend, (void *)sp->sorted_rows,
-                        (void *)sp->pos_img, (void *)sp->code_img, (void *)sp->short_rows, (void *)sp->short_cnt, (void *)sp->cand,
+                        (void *)sp->pos_img, (void *)sp->code_img, (void *)sp->row_any, (void *)sp->short_rows, (void *)sp->short_cnt, (void *)sp->cand,
                         (void *)sp->res, (void *)sp->seg_base, (void *)sp->seg_cnt, (void *)sp->chunks, (void *)sp->chunk_inc,
                         sp->scan_temp, (void *)sp->counters, (void *)sp->rep, (void *)sp->cls_of, (void *)sp->cls_off,
                         (void *)sp->cls_rows, (void *)sp->cls_first, (void *)sp->order, (void *)sp->dgroups, (void *)sp->grp_of,
