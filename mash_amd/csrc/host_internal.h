@@ -1,7 +1,8 @@
 // host_internal.h -- what the host-side translation units of libmashgpu.so share: the context (its stream, block pool,
 // knobs, profiling records), the table with its cached derived structures, and the helpers every entry point uses.
 // mashgpu.cpp      context, pool, parameters, tables, profiling
-// host_sketch.cpp  sketching: batch, packed input, streamed sessions, reads mode
+// host_sketch.cpp  sketching: batch, packed input, streamed sessions
+// host_reads.cpp   sketching in reads mode: sessions fed chunk by chunk, the reference's heap on the host
 // host_compare.cpp comparing: tile engine, inverted-index engine, finishing, thresholded and list outputs
 // host_cluster.cpp clustering: unions and edge lists over the thresholded counts (cut_internal.h: what host_compare.cpp gives them)
 // host_comm.cpp    several GPUs: communicator, replicated / row-sharded tables, sharded calls
@@ -286,6 +287,17 @@ void prof_end(mg_ctx *ctx, std::vector<ProfRec> &v, hipStream_t stream = nullptr
 
 // ---- host_sketch.cpp
 bool alphabet_is_dna(const mg_params *p);
+// What the sketch entry points refuse in their parameters, each stated once: k outside 1..32; canonical k-mers of another
+// alphabet than ACGT; target_cov and bloom_bytes outside reads mode (`reads`: the reads session, which has its own rules
+// for bloom_bytes).  `who` names the entry point in the messages.  *mode_out (nullable): the kernels' mode -- 0: DNA
+// canonical, 1: DNA forward only, 2: table alphabet forward only.
+int sketch_check_params(mg_ctx *ctx, const mg_params *p, const char *who, bool reads, int *mode_out);
+// chunk of k-mer starts per work item: npos in about target_items items, at least min_chunk each, whole tiles
+uint64_t sketch_chunk_size(uint64_t npos, uint64_t target_items, uint64_t min_chunk, uint64_t tile);
+// appends the work items of k-mer starts [begin, begin + npos) in chunks of `chunk`, none reading at or past `limit`; with
+// slot0, several chunks take the pool slots *slot0 ... to be merged; without, every chunk stands alone
+void append_chunk_work(std::vector<mg::SketchWork> &work, uint64_t begin, uint64_t npos, uint64_t chunk, uint64_t limit,
+                       uint32_t sketch, const uint64_t *slot0);
 // table probe fused into the sketch pass (mash screen)
 struct ProbeHook {
     const unsigned long long *keys;

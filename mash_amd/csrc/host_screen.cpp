@@ -139,24 +139,20 @@ int mg_screen_add_dev(mg_screen *sc, const uint8_t *bases_dev, uint64_t nbases)
     // one pass over the batch: its bottom-s (folded into the mixture's running sketch) and,
     // fused into the same kernel, the table probe of every k-mer (hashCounts[key]++)
     const uint64_t s = sc->p.sketch_size;
-    uint64_t *d_h = nullptr;
-    uint32_t *d_n = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d_h, s * 8));
-    if (hipMalloc(&d_n, 4) != hipSuccess) { hipFree(d_h); return fail(ctx, MG_ERR_NOMEM, "mg_screen_add: allocation failed"); }
+    DevBuf<uint64_t> d_h(ctx);
+    DevBuf<uint32_t> d_n(ctx);
+    HIP_TRY(ctx, d_h.alloc(s));
+    if (d_n.alloc(1) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_screen_add: allocation failed");
     const uint64_t off[2] = {0, nbases};
     const ProbeHook hook{sc->keys, sc->obs, sc->slots - 1, sc->key_max, sc->touched, sc->ntouched, sc->touched_cap, sc->tier, sc->bits, sc->bits_scale};
-    int rc = sketch_dev_impl(ctx, &sc->p, bases_dev, nbases, off, 1, d_h, d_n, nullptr, &hook);
+    const int rc = sketch_dev_impl(ctx, &sc->p, bases_dev, nbases, off, 1, d_h, d_n, nullptr, &hook);
+    if (rc != MG_OK) return rc;
     std::vector<uint64_t> bh(s);
     uint32_t bn = 0;
-    if (rc == MG_OK) {
-        if (hipMemcpyAsync(bh.data(), d_h, s * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(&bn, d_n, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            rc = fail(ctx, MG_ERR_HIP, "mg_screen_add: D2H copy failed");
-    }
-    hipFree(d_h);
-    hipFree(d_n);
-    if (rc != MG_OK) return rc;
+    if (hipMemcpyAsync(bh.data(), d_h, s * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(&bn, d_n, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return fail(ctx, MG_ERR_HIP, "mg_screen_add: D2H copy failed");
     std::vector<uint64_t> merged;
     merged.reserve(sc->mix.size() + bn);
     std::merge(sc->mix.begin(), sc->mix.end(), bh.begin(), bh.begin() + bn, std::back_inserter(merged));
@@ -175,18 +171,13 @@ static int screen_add_translated(mg_screen *sc, const uint8_t *bases_dev, uint64
     if (nbases < 3) return MG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t seg = (nbases / 3 + 1 + 15) & ~15ull;        // >= one separator byte after every frame
-    uint8_t *d_aa = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d_aa, 6 * seg + 64));
-    hipError_t e = mg::launch_translate6(bases_dev, nbases, d_aa, seg, !sc->p.preserve_case, ctx->stream);
-    int rc = MG_OK;
-    if (e != hipSuccess) rc = fail(ctx, MG_ERR_HIP, std::string("mg_screen_add (translate): ") + hipGetErrorString(e));
-    if (rc == MG_OK) {
-        sc->translate = false;                                   // the translated bytes take the plain path
-        rc = mg_screen_add_dev(sc, d_aa, 6 * seg);
-        sc->translate = true;
-    }
-    hipStreamSynchronize(ctx->stream);
-    hipFree(d_aa);
+    DevBuf<uint8_t> d_aa(ctx);
+    HIP_TRY(ctx, d_aa.alloc(6 * seg + 64));
+    const hipError_t e = mg::launch_translate6(bases_dev, nbases, d_aa, seg, !sc->p.preserve_case, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, MG_ERR_HIP, std::string("mg_screen_add (translate): ") + hipGetErrorString(e));
+    sc->translate = false;                                       // the translated bytes take the plain path
+    const int rc = mg_screen_add_dev(sc, d_aa, 6 * seg);
+    sc->translate = true;
     return rc;
 }
 
@@ -198,15 +189,12 @@ int mg_screen_add_host(mg_screen *sc, const uint8_t *bases, uint64_t nbases)
     if (!bases && nbases) return fail(ctx, MG_ERR_INVALID, "mg_screen_add_host: NULL bases");
     if (nbases == 0) return MG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t *d = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, nbases + 64));
-    int rc = MG_OK;
+    DevBuf<uint8_t> d(ctx);
+    HIP_TRY(ctx, d.alloc(nbases + 64));
     if (hipMemcpyAsync(d, bases, nbases, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        rc = fail(ctx, MG_ERR_HIP, "mg_screen_add_host: H2D copy failed");
-    else
-        rc = mg_screen_add_dev(sc, d, nbases);
-    hipStreamSynchronize(ctx->stream);
-    hipFree(d);
+        return fail(ctx, MG_ERR_HIP, "mg_screen_add_host: H2D copy failed");
+    const int rc = mg_screen_add_dev(sc, d, nbases);
+    hipStreamSynchronize(ctx->stream);                          // (a batch shorter than k: the copy out of `bases` may still be queued)
     return rc;
 }
 

@@ -1,4 +1,5 @@
-// host_sketch.cpp -- the sketching entry points of include/mashgpu.h: batch, packed input, streamed sessions, reads mode
+// host_sketch.cpp -- the sketching entry points of include/mashgpu.h that drive the selector kernels: batch, packed input,
+// streamed sessions (reads mode: host_reads.cpp)
 #include "host_internal.h"
 
 /* ------------------------------------------------------------------ sketching */
@@ -7,6 +8,58 @@ bool alphabet_is_dna(const mg_params *p)
 {
     if (p->alphabet_size != 4) return false;
     return p->alphabet['A'] && p->alphabet['C'] && p->alphabet['G'] && p->alphabet['T'];
+}
+
+int sketch_check_params(mg_ctx *ctx, const mg_params *p, const char *who, bool reads, int *mode_out)
+{
+    if (p->kmer_size < 1 || p->kmer_size > 32) return fail(ctx, MG_ERR_INVALID, "mg_sketch: k must be 1..32");
+    if (reads) {
+        // (neither -c nor -b: plain reads mode, any min_copies, in constant memory -- nothing stops the reading)
+        if (p->bloom_bytes && p->min_copies > 1) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": min_copies cannot be used with bloom_bytes");   // sketchParameterSetup.cpp:44-48
+        if (p->bloom_bytes > (1ull << 60)) return fail(ctx, MG_ERR_INVALID, std::string(who) + ": bloom_bytes out of range");
+    } else {
+        if (p->target_cov > 0) return fail(ctx, MG_ERR_UNSUPPORTED, std::string(who) + ": target_cov needs mg_sketch_reads_host");
+        if (p->bloom_bytes) return fail(ctx, MG_ERR_UNSUPPORTED, std::string(who) + ": bloom_bytes needs mg_sketch_reads_host");
+    }
+    const bool dna = alphabet_is_dna(p);
+    if (!p->noncanonical && !dna) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: canonical k-mers need the ACGT alphabet");
+    if (mode_out) *mode_out = dna ? (p->noncanonical ? 1 : 0) : 2;
+    return MG_OK;
+}
+
+// Packed bases go to the sketch kernel as they are (SketchArgs::packed) for plain nucleotide sketches of a size the LDS
+// selector serves; multiplicities, min_copies and larger sketches go through an ASCII copy (unpack_bases_kernel) and the
+// ordinary path.  MASHGPU_PACKED_UNPACK=1: always the copy.
+static bool packed_direct(mg_ctx *ctx, const mg_params *p, bool counts)
+{
+    int nt = 0;
+    uint32_t cap = 0;
+    return !counts && p->min_copies <= 1 && alphabet_is_dna(p) && mg::sketch_geometry(p->sketch_size, &nt, &cap) &&
+           !ctx_opt(ctx, "MASHGPU_PACKED_UNPACK");
+}
+
+uint64_t sketch_chunk_size(uint64_t npos, uint64_t target_items, uint64_t min_chunk, uint64_t tile)
+{
+    const uint64_t chunk = std::max((npos + target_items - 1) / target_items, min_chunk);
+    return (chunk + tile - 1) / tile * tile;
+}
+
+void append_chunk_work(std::vector<mg::SketchWork> &work, uint64_t begin, uint64_t npos, uint64_t chunk, uint64_t limit,
+                       uint32_t sketch, const uint64_t *slot0)
+{
+    const uint64_t nch = (npos + chunk - 1) / chunk;
+    const bool pooled = slot0 && nch > 1;
+    for (uint64_t c = 0; c < nch; c++) {
+        mg::SketchWork w;
+        w.begin = begin + c * chunk;
+        w.end = begin + std::min(npos, (c + 1) * chunk);
+        w.limit = limit;
+        w.sketch = sketch;
+        w.slot = pooled ? (uint32_t)(*slot0 + c) : 0u;
+        w.nchunks = pooled ? (uint32_t)nch : 1u;
+        w._pad = 0;
+        work.push_back(w);
+    }
 }
 
 // Work decomposition of one sketching call: chunks of k-mer start positions (one workgroup each)
@@ -33,11 +86,9 @@ static int plan_sketch_work(mg_ctx *ctx, const mg_params *p, const uint64_t *ske
     uint64_t target_items = 2048;
     if (const char *e = ctx_opt(ctx, "MASHGPU_SKETCH_ITEMS")) target_items = strtoull(e, nullptr, 10);
     if (target_items < 1) target_items = 1;
-    uint64_t chunk = (total_pos + target_items - 1) / target_items;
     uint64_t min_chunk = 4 * tile;
     if (const char *e = ctx_opt(ctx, "MASHGPU_SKETCH_MIN_CHUNK")) min_chunk = strtoull(e, nullptr, 10);
-    if (chunk < min_chunk) chunk = min_chunk;
-    chunk = (chunk + tile - 1) / tile * tile;
+    const uint64_t chunk = sketch_chunk_size(total_pos, target_items, min_chunk, tile);
 
     std::vector<mg::MergeWork> level1;
     uint64_t nslots = 0;
@@ -61,17 +112,7 @@ static int plan_sketch_work(mg_ctx *ctx, const mg_params *p, const uint64_t *ske
                 plan->merges.push_back(mg::MergeWork{(uint32_t)i, (uint32_t)nslots, (uint32_t)nch, 1, 0});
             }
         }
-        for (uint64_t c = 0; c < nch; c++) {
-            mg::SketchWork w;
-            w.begin = b + c * chunk;
-            w.end = b + std::min(npos, (c + 1) * chunk);
-            w.limit = e;
-            w.sketch = (uint32_t)i;
-            w.slot = nch > 1 ? (uint32_t)(nslots + c) : 0u;
-            w.nchunks = (uint32_t)nch;
-            w._pad = 0;
-            plan->work.push_back(w);
-        }
+        append_chunk_work(plan->work, b, npos, chunk, e, (uint32_t)i, &nslots);
         if (nch > 1) nslots += nch;
     }
     plan->nfinal = plan->merges.size();
@@ -278,31 +319,22 @@ int mg_sketch_dev(mg_ctx *ctx, const mg_params *p, const uint8_t *bases_dev, uin
                            counts_out_dev, nullptr);
 }
 
-// minCov >= 2: bottom-s of the hashes seen at least m times (see range_count_kernel).  One
-// sketch at a time; `work` holds the chunks of all sketches, grouped by sketch.
-static int sketch_min_copies(mg_ctx *ctx, const mg_params *p, int mode, const uint8_t *bases_dev,
-                             const std::vector<mg::SketchWork> &work, const mg::SketchWork *d_work,
-                             const uint8_t *d_alpha, uint64_t nsketch, uint64_t *hashes_out_dev,
-                             uint32_t *nhash_out_dev)
+// minCov >= 2 (and sketch sizes beyond the LDS selector): bottom-s of the hashes seen at least m times (see
+// range_count_kernel).  One sketch at a time; the plan's work holds the chunks of all sketches, grouped by sketch.
+static int sketch_min_copies(SketchRun &r, const uint8_t *bases_dev, uint64_t *hashes_out_dev, uint32_t *nhash_out_dev)
 {
-    const uint64_t s = p->sketch_size;
+    mg_ctx *ctx = r.ctx;
+    const mg_params *p = r.p;
+    const std::vector<mg::SketchWork> &work = r.plan.work;
+    const uint64_t s = r.s;
     const uint64_t hash_max = p->use64 ? 0xFFFFFFFFFFFFFFFEull : 0xFFFFFFFFull;
     const uint64_t max_expect = 1ull << 24;                 // distinct hashes aimed at per round (table: 4x slots)
-    unsigned long long *d_keys = nullptr, *d_out = nullptr, *d_outn = nullptr;
-    uint32_t *d_cnts = nullptr, *d_ovf = nullptr;
+    DevBuf<unsigned long long> d_keys(ctx), d_out(ctx), d_outn(ctx);
+    DevBuf<uint32_t> d_cnts(ctx), d_ovf(ctx);
     uint64_t slots_cap = 0, out_cap = 0;
-    int rc = MG_OK;
-    auto release = [&]() {
-        hipStreamSynchronize(ctx->stream);
-        for (void *q : {(void *)d_keys, (void *)d_out, (void *)d_outn, (void *)d_cnts, (void *)d_ovf})
-            if (q) hipFree(q);
-    };
-    if (hipMalloc(&d_outn, 8) != hipSuccess || hipMalloc(&d_ovf, 4) != hipSuccess) {
-        release();
-        return fail(ctx, MG_ERR_NOMEM, "mg_sketch: allocation failed");
-    }
+    if (d_outn.alloc(1) != hipSuccess || d_ovf.alloc(1) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_sketch: allocation failed");
     size_t w0 = 0;
-    while (w0 < work.size() && rc == MG_OK) {
+    while (w0 < work.size()) {
         const uint32_t sk = work[w0].sketch;
         size_t w1 = w0;
         uint64_t npos = 0;
@@ -313,7 +345,7 @@ static int sketch_min_copies(mg_ctx *ctx, const mg_params *p, int mode, const ui
         uint64_t expect = std::max<uint64_t>((p->min_copies > 1 ? 64 : 2) * s, 1ull << 16);
         if (const char *e = ctx_opt(ctx, "MASHGPU_MINCOPIES_EXPECT")) expect = std::max<uint64_t>(1024, strtoull(e, nullptr, 10));  // test knob
         bool exhausted = false;
-        while (kept.size() < s && !exhausted && rc == MG_OK) {
+        while (kept.size() < s && !exhausted) {
             // range [lo, hi] expected to hold <= `expect` distinct hashes (there are <= npos k-mers)
             const long double frac = npos <= expect ? 1.0L : (long double)expect / (long double)npos;
             const long double width = frac * ((long double)hash_max + 1.0L);
@@ -323,28 +355,18 @@ static int sketch_min_copies(mg_ctx *ctx, const mg_params *p, int mode, const ui
             uint64_t slots = 1024;
             while (slots < 4 * want) slots <<= 1;
             if (slots > slots_cap) {
-                if (d_keys) hipFree(d_keys);
-                if (d_cnts) hipFree(d_cnts);
-                d_keys = nullptr; d_cnts = nullptr;
-                if (hipMalloc(&d_keys, slots * 8) != hipSuccess || hipMalloc(&d_cnts, slots * 4) != hipSuccess) {
-                    rc = fail(ctx, MG_ERR_NOMEM, "mg_sketch: allocation failed (min_copies table)");
-                    break;
-                }
+                if (d_keys.alloc(slots) != hipSuccess || d_cnts.alloc(slots) != hipSuccess)
+                    return fail(ctx, MG_ERR_NOMEM, "mg_sketch: allocation failed (min_copies table)");
                 slots_cap = slots;
             }
             if (slots / 2 > out_cap) {
-                if (d_out) hipFree(d_out);
-                d_out = nullptr;
-                if (hipMalloc(&d_out, slots / 2 * 8) != hipSuccess) {
-                    rc = fail(ctx, MG_ERR_NOMEM, "mg_sketch: allocation failed (min_copies list)");
-                    break;
-                }
+                if (d_out.alloc(slots / 2) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_sketch: allocation failed (min_copies list)");
                 out_cap = slots / 2;
             }
             mg::RangeCountArgs ra;
             ra.bases = bases_dev;
-            ra.work = d_work + w0;
-            ra.alphabet = d_alpha;
+            ra.work = r.d_work + w0;
+            ra.alphabet = r.d_alpha;
             ra.keys = d_keys;
             ra.cnts = d_cnts;
             ra.overflow = d_ovf;
@@ -355,43 +377,34 @@ static int sketch_min_copies(mg_ctx *ctx, const mg_params *p, int mode, const ui
             ra.fold_case = p->preserve_case ? 0 : 1;
             unsigned long long n_out = 0;
             uint32_t ovf = 0;
-            hipError_t e = hipMemsetAsync(d_keys, 0xFF, slots * 8, ctx->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_cnts, 0, slots * 4, ctx->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_ovf, 0, 4, ctx->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_outn, 0, 8, ctx->stream);
-            if (e == hipSuccess) e = mg::launch_range_count(p->kmer_size, mode, ra, (uint32_t)(w1 - w0), ctx->stream);
-            if (e == hipSuccess) e = mg::launch_range_extract(d_keys, d_cnts, slots, p->min_copies > 1 ? p->min_copies : 1, d_out, d_outn, out_cap, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&n_out, d_outn, 8, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) { rc = fail(ctx, MG_ERR_HIP, std::string("mg_sketch (min_copies): ") + hipGetErrorString(e)); break; }
+            HIP_TRY(ctx, hipMemsetAsync(d_keys, 0xFF, slots * 8, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_cnts, 0, slots * 4, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_ovf, 0, 4, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_outn, 0, 8, ctx->stream));
+            HIP_TRY(ctx, mg::launch_range_count(p->kmer_size, r.mode, ra, (uint32_t)(w1 - w0), ctx->stream));
+            HIP_TRY(ctx, mg::launch_range_extract(d_keys, d_cnts, slots, p->min_copies > 1 ? p->min_copies : 1, d_out, d_outn, out_cap, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(&n_out, d_outn, 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (ovf || n_out > out_cap) {                    // more distinct hashes than planned: narrow the range
-                if (expect <= 1024) { rc = fail(ctx, MG_ERR_HIP, "mg_sketch (min_copies): counting table overflow"); break; }
+                if (expect <= 1024) return fail(ctx, MG_ERR_HIP, "mg_sketch (min_copies): counting table overflow");
                 expect /= 4;
                 continue;
             }
             std::vector<uint64_t> got(n_out);
-            if (n_out && hipMemcpy(got.data(), d_out, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = fail(ctx, MG_ERR_HIP, "mg_sketch (min_copies): D2H copy failed");
-                break;
-            }
+            if (n_out) HIP_TRY(ctx, hipMemcpy(got.data(), d_out, n_out * 8, hipMemcpyDeviceToHost));
             std::sort(got.begin(), got.end());
             for (uint64_t v : got) { if (kept.size() < s) kept.push_back(v); }
             if (hi >= hash_max) exhausted = true;
             else lo = hi + 1;
             if (expect < max_expect) expect *= 8;
         }
-        if (rc != MG_OK) break;
         const uint32_t n = (uint32_t)kept.size();
-        if (n && hipMemcpy(hashes_out_dev + (uint64_t)sk * s, kept.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(ctx, MG_ERR_HIP, "mg_sketch (min_copies): H2D copy failed");
-        if (rc == MG_OK && hipMemcpy(nhash_out_dev + sk, &n, 4, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(ctx, MG_ERR_HIP, "mg_sketch (min_copies): H2D copy failed");
+        if (n) HIP_TRY(ctx, hipMemcpy(hashes_out_dev + (uint64_t)sk * s, kept.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(nhash_out_dev + sk, &n, 4, hipMemcpyHostToDevice));
         w0 = w1;
     }
-    (void)nsketch;
-    release();
-    return rc;
+    return MG_OK;
 }
 
 int sketch_dev_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *bases_dev, uint64_t nbases,
@@ -402,22 +415,19 @@ int sketch_dev_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *bases_dev, u
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!p || !sketch_off || !hashes_out_dev || !nhash_out_dev || (!bases_dev && nbases && !pk))
         return fail(ctx, MG_ERR_INVALID, "mg_sketch: NULL argument");
-    if (pk && (counts_out_dev || probe || p->min_copies > 1 || !alphabet_is_dna(p)))
+    if (pk && (probe || !packed_direct(ctx, p, counts_out_dev != nullptr)))
         return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: packed bases in the kernel serve plain nucleotide sketches only");
     // (what the unpack kernel's launcher checked before the sketch kernel read packed bases itself: ADVICE r5)
     if (pk && (!pk->packed || pk->skip >= 16u || pk->mskip >= 32u || ((uintptr_t)pk->packed & 3) != 0 || ((uintptr_t)pk->mask & 3) != 0))      // (mask: nullable)
         return fail(ctx, MG_ERR_INVALID, "mg_sketch: packed bases must be 4-byte aligned words, base skip < 16, mask skip < 32");
-    if (p->kmer_size < 1 || p->kmer_size > 32) return fail(ctx, MG_ERR_INVALID, "mg_sketch: k must be 1..32");
+    int mode = 0;
+    int rc = sketch_check_params(ctx, p, "mg_sketch", false, &mode);
+    if (rc != MG_OK) return rc;
     if (counts_out_dev && !mg::count_supported(p->sketch_size))
         return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: sketch size too large for the multiplicity pass");
-    if (p->target_cov > 0) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: target_cov needs mg_sketch_reads_host");
-    if (p->bloom_bytes) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: bloom_bytes needs mg_sketch_reads_host");
     if (nsketch == 0) return MG_OK;
     if (nsketch > 0xFFFFFFFFull) return fail(ctx, MG_ERR_INVALID, "mg_sketch: too many sketches");
     if (((uintptr_t)bases_dev & 15) != 0) return fail(ctx, MG_ERR_INVALID, "mg_sketch: bases must be 16-byte aligned");
-    const bool dna = alphabet_is_dna(p);
-    if (!p->noncanonical && !dna)
-        return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: canonical k-mers need the ACGT alphabet");
     int nt = 0;
     uint32_t cap = 0;
     // sketch sizes beyond the LDS selector (s > 12288) take the exact range-counting path that
@@ -428,13 +438,12 @@ int sketch_dev_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *bases_dev, u
         nt = 256;                                          // chunk geometry only
         cap = 0;
     }
-    const int mode = dna ? (p->noncanonical ? 1 : 0) : 2;
     const uint64_t s = p->sketch_size;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     SketchRun run(ctx, p);
     run.mode = mode; run.nt = nt; run.cap = cap; run.s = s; run.nsketch = nsketch;
-    int rc = plan_sketch_work(ctx, p, sketch_off, nsketch, nbases, nt, &run.plan);
+    rc = plan_sketch_work(ctx, p, sketch_off, nsketch, nbases, nt, &run.plan);
     if (rc != MG_OK) return rc;
     const SketchPlan &plan = run.plan;
 
@@ -491,11 +500,10 @@ int sketch_dev_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *bases_dev, u
     a.pmask = pk ? pk->mask : nullptr;
     a.pskip = pk ? pk->skip : 0;
     a.pmskip = pk ? pk->mskip : 0;
-    if (pk && range_path) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: packed bases in the kernel need the LDS selector's sketch sizes");
     if (range_path) {
         // -m / s beyond the LDS selector: bottom-s of the hashes seen at least m times, by exact range counting
         if (probe) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_screen: min_copies does not apply");
-        rc = sketch_min_copies(ctx, p, mode, bases_dev, plan.work, run.d_work, run.d_alpha, nsketch, hashes_out_dev, nhash_out_dev);
+        rc = sketch_min_copies(run, bases_dev, hashes_out_dev, nhash_out_dev);
         if (rc != MG_OK) return rc;
     } else {
         rc = seed_thresholds(run, sketch_off);
@@ -516,6 +524,26 @@ int sketch_dev_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *bases_dev, u
     return MG_OK;
 }
 
+// What mg_sketch_host, mg_sketch_host_packed and mg_sketch_finish (`who`, for the messages) end in: the device blocks of
+// nsketch x s results -- counts only where the caller wants them -- are handed to `sketch` to be filled, then copied out.
+template <class Sketch>
+static int sketch_to_host(mg_ctx *ctx, const char *who, uint64_t s, uint64_t nsketch, uint64_t *hashes_out, uint32_t *nhash_out,
+                          uint32_t *counts_out, Sketch sketch)
+{
+    DevBuf<uint64_t> d_hashes(ctx);
+    DevBuf<uint32_t> d_nhash(ctx), d_counts(ctx);
+    if ((counts_out && d_counts.alloc(nsketch * s) != hipSuccess) || d_hashes.alloc(nsketch * s) != hipSuccess || d_nhash.alloc(nsketch) != hipSuccess)
+        return fail(ctx, MG_ERR_NOMEM, std::string(who) + ": device allocation failed");
+    const int rc = sketch(d_hashes.p, d_nhash.p, d_counts.p);
+    if (rc != MG_OK) return rc;
+    if ((counts_out && hipMemcpyAsync(counts_out, d_counts, nsketch * s * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+        hipMemcpyAsync(hashes_out, d_hashes, nsketch * s * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(nhash_out, d_nhash, nsketch * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return fail(ctx, MG_ERR_HIP, std::string(who) + ": D2H copy failed");
+    return MG_OK;
+}
+
 int mg_sketch_host(mg_ctx *ctx, const mg_params *p, const uint8_t *bases, uint64_t nbases,
                    const uint64_t *sketch_off, uint64_t nsketch, uint64_t *hashes_out,
                    uint32_t *nhash_out, uint32_t *counts_out)
@@ -525,23 +553,14 @@ int mg_sketch_host(mg_ctx *ctx, const mg_params *p, const uint8_t *bases, uint64
     if (!p || !hashes_out || !nhash_out) return fail(ctx, MG_ERR_INVALID, "mg_sketch_host: NULL argument");
     if (nsketch == 0) return MG_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t s = p->sketch_size;
-    DevBuf<uint8_t> d_bases(ctx);
-    DevBuf<uint64_t> d_hashes(ctx);
-    DevBuf<uint32_t> d_nhash(ctx), d_counts(ctx);
-    if ((counts_out && d_counts.alloc(nsketch * s) != hipSuccess) || d_bases.alloc(nbases + 64) != hipSuccess ||
-        d_hashes.alloc(nsketch * s) != hipSuccess || d_nhash.alloc(nsketch) != hipSuccess)
-        return fail(ctx, MG_ERR_NOMEM, "mg_sketch_host: device allocation failed");
-    if (hipMemcpyAsync(d_bases, bases, nbases, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return fail(ctx, MG_ERR_HIP, "mg_sketch_host: H2D copy failed");
-    const int rc = mg_sketch_dev(ctx, p, d_bases, nbases, sketch_off, nsketch, d_hashes, d_nhash, d_counts);
-    if (rc != MG_OK) return rc;
-    if ((counts_out && hipMemcpyAsync(counts_out, d_counts, nsketch * s * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
-        hipMemcpyAsync(hashes_out, d_hashes, nsketch * s * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(nhash_out, d_nhash, nsketch * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return fail(ctx, MG_ERR_HIP, "mg_sketch_host: D2H copy failed");
-    return MG_OK;
+    return sketch_to_host(ctx, "mg_sketch_host", p->sketch_size, nsketch, hashes_out, nhash_out, counts_out,
+                          [&](uint64_t *d_hashes, uint32_t *d_nhash, uint32_t *d_counts) {
+        DevBuf<uint8_t> d_bases(ctx);
+        if (d_bases.alloc(nbases + 64) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_sketch_host: device allocation failed");
+        if (hipMemcpyAsync(d_bases, bases, nbases, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            return fail(ctx, MG_ERR_HIP, "mg_sketch_host: H2D copy failed");
+        return mg_sketch_dev(ctx, p, d_bases, nbases, sketch_off, nsketch, d_hashes, d_nhash, d_counts);
+    });
 }
 
 /* ------------------------------------------------- packed nucleotide input (ingest.hip, pack_bases.cpp) */
@@ -557,7 +576,7 @@ static int sketch_packed_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *pa
     const uint64_t s = p->sketch_size;
     uint64_t cap = 1ull << 28;
     if (const char *e = ctx_opt(ctx, "MASHGPU_PACKED_PIECE")) cap = std::max<uint64_t>(strtoull(e, nullptr, 10), 1);      // (test knob)
-    for (uint64_t i = 0; i < nsketch; i++)
+    for (uint64_t i = 0; i < nsketch; i++)                   // (here: the pieces are cut, and their bytes copied, by these offsets)
         if (sketch_off[i] > sketch_off[i + 1] || sketch_off[i + 1] > nbases) return fail(ctx, MG_ERR_INVALID, "mg_sketch_packed: sketch_off must ascend and end within nbases");
     struct Piece { uint64_t i0, i1, b0, b1; };
     std::vector<Piece> pieces;
@@ -569,12 +588,7 @@ static int sketch_packed_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *pa
         longest = std::max(longest, sketch_off[i1] - sketch_off[i0]);
         i0 = i1;
     }
-    // plain sketches: the kernel reads the packed arrays itself; multiplicities, min_copies and sketch sizes beyond the LDS
-    // selector go through an ASCII copy (unpack_bases_kernel) and the ordinary path.  MASHGPU_PACKED_UNPACK=1: always the copy.
-    int nt_unused = 0;
-    uint32_t cap_unused = 0;
-    const bool direct = !d_counts && p->min_copies <= 1 && alphabet_is_dna(p) && mg::sketch_geometry(p->sketch_size, &nt_unused, &cap_unused) &&
-                        !ctx_opt(ctx, "MASHGPU_PACKED_UNPACK");
+    const bool direct = packed_direct(ctx, p, d_counts != nullptr);
     DevBuf<uint8_t> d_ascii(ctx), d_pk[2] = {DevBuf<uint8_t>(ctx), DevBuf<uint8_t>(ctx)}, d_mk[2] = {DevBuf<uint8_t>(ctx), DevBuf<uint8_t>(ctx)};
     if (!direct && d_ascii.alloc(((longest + 15u) & ~15ull) + 64u) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_sketch_packed: device allocation failed");
     hipStream_t copy_stream = nullptr;
@@ -624,19 +638,9 @@ static int sketch_packed_impl(mg_ctx *ctx, const mg_params *p, const uint8_t *pa
         }
         struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join{next};
         const uint64_t len = q.b1 - q.b0;
-        const uint8_t *src_pk, *src_mk;
-        uint32_t skip, mskip;
-        if (host_input) {
-            src_pk = d_pk[c & 1];
-            src_mk = mask ? d_mk[c & 1].p : nullptr;
-            skip = (uint32_t)(q.b0 - pk_byte0(q) * 4u);
-            mskip = (uint32_t)(q.b0 - mk_byte0(q) * 8u);
-        } else {
-            src_pk = packed + pk_byte0(q);
-            src_mk = mask ? mask + mk_byte0(q) : nullptr;
-            skip = (uint32_t)(q.b0 - pk_byte0(q) * 4u);
-            mskip = (uint32_t)(q.b0 - mk_byte0(q) * 8u);
-        }
+        const uint8_t *src_pk = host_input ? d_pk[c & 1].p : packed + pk_byte0(q);
+        const uint8_t *src_mk = !mask ? nullptr : host_input ? d_mk[c & 1].p : mask + mk_byte0(q);
+        const uint32_t skip = (uint32_t)(q.b0 - pk_byte0(q) * 4u), mskip = (uint32_t)(q.b0 - mk_byte0(q) * 8u);
         off.resize(q.i1 - q.i0 + 1);
         for (uint64_t i = q.i0; i <= q.i1; i++) off[i - q.i0] = sketch_off[i] - q.b0;
         int rc;
@@ -686,19 +690,10 @@ int mg_sketch_host_packed(mg_ctx *ctx, const mg_params *p, const uint8_t *packed
     int rc = sketch_packed_check(ctx, p, packed, nbases, sketch_off, hashes_out, nhash_out);
     if (rc != MG_OK || nsketch == 0) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t s = p->sketch_size;
-    DevBuf<uint64_t> d_hashes(ctx);
-    DevBuf<uint32_t> d_nhash(ctx), d_counts(ctx);
-    if ((counts_out && d_counts.alloc(nsketch * s) != hipSuccess) || d_hashes.alloc(nsketch * s) != hipSuccess || d_nhash.alloc(nsketch) != hipSuccess)
-        return fail(ctx, MG_ERR_NOMEM, "mg_sketch_host_packed: device allocation failed");
-    rc = sketch_packed_impl(ctx, p, packed, invalid_mask, true, nbases, sketch_off, nsketch, d_hashes, d_nhash, d_counts);
-    if (rc != MG_OK) return rc;
-    if ((counts_out && hipMemcpyAsync(counts_out, d_counts, nsketch * s * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
-        hipMemcpyAsync(hashes_out, d_hashes, nsketch * s * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(nhash_out, d_nhash, nsketch * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return fail(ctx, MG_ERR_HIP, "mg_sketch_host_packed: D2H copy failed");
-    return MG_OK;
+    return sketch_to_host(ctx, "mg_sketch_host_packed", p->sketch_size, nsketch, hashes_out, nhash_out, counts_out,
+                          [&](uint64_t *d_hashes, uint32_t *d_nhash, uint32_t *d_counts) {
+        return sketch_packed_impl(ctx, p, packed, invalid_mask, true, nbases, sketch_off, nsketch, d_hashes, d_nhash, d_counts);
+    });
 }
 
 /* ------------------------------------------------- streamed ingest: segments in, sketches out */
@@ -713,7 +708,7 @@ int mg_sketch_host_packed(mg_ctx *ctx, const mg_params *p, const uint8_t *packed
 struct mg_sketch_session {
     mg_ctx *ctx = nullptr;
     mg_params p;
-    uint8_t *d_bases = nullptr;
+    DevBuf<uint8_t> d_bases;                  // (no pool: the arena outlives calls)
     uint64_t d_cap = 0, d_used = 0;
     uint8_t *stage[2] = {nullptr, nullptr};
     uint64_t stage_cap = 32ull << 20, fill = 0;
@@ -734,13 +729,12 @@ static int session_submit(mg_sketch_session *ss)
         // grow the device arena (copies what has arrived; rare: capacity doubles)
         uint64_t cap = std::max<uint64_t>(ss->d_cap * 2, 256ull << 20);
         while (cap < ss->d_used + ss->fill + 64) cap *= 2;
-        uint8_t *nb = nullptr;
-        if (hipMalloc(&nb, cap) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_sketch_add: device allocation failed");
+        DevBuf<uint8_t> nb;
+        if (nb.alloc(cap) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_sketch_add: device allocation failed");
         if (ss->d_used)
             HIP_TRY(ctx, hipMemcpyAsync(nb, ss->d_bases, ss->d_used, hipMemcpyDeviceToDevice, ss->copy_stream));
         HIP_TRY(ctx, hipStreamSynchronize(ss->copy_stream));
-        if (ss->d_bases) hipFree(ss->d_bases);
-        ss->d_bases = nb;
+        std::swap(ss->d_bases.p, nb.p);                     // (the old arena goes with nb)
         ss->d_cap = cap;
     }
     HIP_TRY(ctx, hipMemcpyAsync(ss->d_bases + ss->d_used, ss->stage[ss->cur], ss->fill, hipMemcpyHostToDevice, ss->copy_stream));
@@ -761,8 +755,8 @@ int mg_sketch_begin(mg_ctx *ctx, const mg_params *p, mg_sketch_session **out)
     if (!ctx) return MG_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (!p || !out) return fail(ctx, MG_ERR_INVALID, "mg_sketch_begin: NULL argument");
-    if (p->target_cov > 0) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch_begin: target_cov needs mg_sketch_reads_host");
-    if (p->bloom_bytes) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch_begin: bloom_bytes needs mg_sketch_reads_host");
+    const int rc = sketch_check_params(ctx, p, "mg_sketch_begin", false, nullptr);
+    if (rc != MG_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     mg_sketch_session *ss = new mg_sketch_session;
     ss->ctx = ctx;
@@ -847,19 +841,11 @@ int mg_sketch_finish(mg_sketch_session *ss, uint64_t *hashes_out, uint32_t *nhas
         if (rc != MG_OK) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ss->copy_stream));
         ss->ev_pending[0] = ss->ev_pending[1] = false;
-        const uint64_t s = ss->p.sketch_size;
-        DevBuf<uint64_t> d_hashes(ctx);
-        DevBuf<uint32_t> d_nhash(ctx), d_counts(ctx);
-        if ((counts_out && d_counts.alloc(nsketch * s) != hipSuccess) || d_hashes.alloc(nsketch * s) != hipSuccess ||
-            d_nhash.alloc(nsketch) != hipSuccess)
-            return fail(ctx, MG_ERR_NOMEM, "mg_sketch_finish: device allocation failed");
-        rc = mg_sketch_dev(ctx, &ss->p, ss->d_bases, ss->d_used, ss->off.data(), nsketch, d_hashes, d_nhash, d_counts);
+        rc = sketch_to_host(ctx, "mg_sketch_finish", ss->p.sketch_size, nsketch, hashes_out, nhash_out, counts_out,
+                            [&](uint64_t *d_hashes, uint32_t *d_nhash, uint32_t *d_counts) {
+            return mg_sketch_dev(ctx, &ss->p, ss->d_bases, ss->d_used, ss->off.data(), nsketch, d_hashes, d_nhash, d_counts);
+        });
         if (rc != MG_OK) return rc;
-        if ((counts_out && hipMemcpyAsync(counts_out, d_counts, nsketch * s * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
-            hipMemcpyAsync(hashes_out, d_hashes, nsketch * s * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(nhash_out, d_nhash, nsketch * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            return fail(ctx, MG_ERR_HIP, "mg_sketch_finish: D2H copy failed");
     }
     ss->d_used = 0;                                       // the arena and the staging ring are kept for the next batch
     ss->fill = 0;
@@ -876,358 +862,5 @@ void mg_sketch_session_free(mg_sketch_session *ss)
         if (ss->stage[i]) hipHostFree(ss->stage[i]);
         if (ss->ev[i]) hipEventDestroy(ss->ev[i]);
     }
-    if (ss->d_bases) hipFree(ss->d_bases);
     delete ss;
 }
-
-/* ------------------------------------------------- reads mode with early stop (-c) */
-
-namespace {
-
-// MinHashHeap::tryInsert (MinHashHeap.cpp:68-145) over explicit containers: kept hashes with
-// counts, pending hashes (multiplicityMinimum > 1) and the pending max-queue that may hold hashes
-// already erased from the pending set; with -b, the Bloom filter in front of the kept set.
-//
-// The filter (MinHashHeap.cpp:19-41: vendored bloom_filter.hpp with projected_element_count 1e9,
-// false_positive_probability 0, maximum_size = bytes * 8): probability 0 makes
-// compute_optimal_parameters (bloom_filter.hpp:107-155) pick one hash function and cast -inf to
-// the table size, which x86-64 builds turn into 2^63 and the clamp into maximum_size -- ONE hash
-// over bytes * 8 bits.  Salt :449-508 (salt_count 1), hash_ap :526-568 over the hash's 8 or 4
-// bytes, bit = hash % table_size :443-447.
-struct ReadsBloom {
-    std::vector<uint8_t> bits;
-    uint64_t nbits = 0;
-    bool use64 = true;
-    void init(uint64_t bytes, bool u64)
-    {
-        nbits = bytes * 8;
-        use64 = u64;
-        bits.assign((size_t)std::min<uint64_t>(bytes, 1ull << 29), 0);   // a 32-bit hash stays below bit 2^32
-    }
-    uint64_t bit_of(uint64_t hash) const
-    {
-        const uint64_t seed = 0xA5A5A5A55A5A5A5Aull * 0xA5A5A5A5ull + 1ull;     // random_seed_
-        uint32_t h = 0xAAAAAAAAu * 0xAAAAAAAAu + (uint32_t)seed;                // the filter's only salt
-        if (use64) {
-            const uint32_t w0 = (uint32_t)hash, w1 = (uint32_t)(hash >> 32);
-            h ^= (h << 7) ^ (w0 * (h >> 3)) ^ (~((h << 11) + (w1 ^ (h >> 5))));
-        } else {
-            h ^= ~((h << 11) + ((uint32_t)hash ^ (h >> 5)));
-        }
-        return (uint64_t)h % nbits;
-    }
-    bool test_and_set(uint64_t hash)                        // contains ? true : (insert, false)
-    {
-        const uint64_t b = bit_of(hash);
-        const uint8_t m = (uint8_t)(1u << (b & 7));
-        if (bits[b >> 3] & m) return true;
-        bits[b >> 3] |= m;
-        return false;
-    }
-};
-
-struct ReadsHeap {
-    uint64_t cap, mmin;
-    std::map<uint64_t, uint32_t> kept;
-    std::map<uint64_t, uint32_t> pending;
-    std::priority_queue<uint64_t> pending_q;
-    uint64_t msum = 0;                                       // multiplicitySum
-    ReadsBloom bloom;                                        // nbits == 0: none
-
-    ReadsHeap(uint64_t s, uint64_t m) : cap(s), mmin(m < 1 ? 1 : m) {}
-    bool full() const { return kept.size() >= cap; }
-    uint64_t top() const { return kept.rbegin()->first; }
-    double multiplicity() const { return kept.empty() ? 0.0 : (double)msum / (double)kept.size(); }   // MinHashHeap.h:44
-
-    void try_insert(uint64_t h)
-    {
-        if (!(kept.size() < cap || h < top())) return;       // :70-74
-        auto it = kept.find(h);
-        if (it != kept.end()) {                              // :120-124
-            it->second++;
-            msum++;
-        } else if (bloom.nbits) {                            // :78-94
-            if (bloom.test_and_set(h)) {
-                kept.emplace(h, 2u);
-                msum += 2;
-            }
-        } else {
-            auto pit = pending.find(h);
-            const uint64_t pc = pit == pending.end() ? 0 : pit->second;
-            if (mmin == 1 || pc == mmin - 1) {               // :96-109
-                kept.emplace(h, (uint32_t)mmin);
-                msum += mmin;
-                if (mmin > 1 && pit != pending.end()) pending.erase(pit);
-            } else {                                         // :110-118
-                if (pit == pending.end()) { pending_q.push(h); pending.emplace(h, 1u); }
-                else pit->second++;
-            }
-        }
-        if (kept.size() > cap) {                             // :126-144
-            auto last = std::prev(kept.end());
-            const uint64_t tv = last->first;
-            msum -= last->second;
-            kept.erase(last);
-            while (!pending_q.empty() && tv < pending_q.top()) {
-                pending.erase(pending_q.top());
-                pending_q.pop();
-            }
-        }
-    }
-};
-
-}  // namespace
-
-// Reads mode as a SESSION: chunks of whole records in reading order; the heap (incl. the -m pending
-// set) lives on the host between chunks, the device sees one chunk at a time, and with -c the caller
-// stops reading its files the moment a chunk reports the target coverage.  Host and device memory are
-// bounded by one chunk for EVERY reads option (-r, -m, -c, -b): what the reference's reader loop does
-// (Sketch.cpp:1196-1270), where mg_sketch_host / mg_sketch_begin keep the whole read set in HBM.
-struct mg_reads_session {
-    mg_ctx *ctx = nullptr;
-    mg_params p;
-    int mode = 0;
-    ReadsHeap heap;
-    bool stopped = false;
-    uint64_t used = 0;                  // records consumed when the stop occurred
-    uint64_t records = 0;               // records (>= k) seen so far
-    double shrink = 1.0;
-    uint8_t *d_bases = nullptr;
-    uint64_t d_cap = 0;
-    uint8_t *d_alpha = nullptr;
-    mg::HashEvent *d_ev = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    std::vector<mg::HashEvent> ev;
-    mg_reads_session(uint64_t s, uint64_t m) : heap(s, m) {}
-};
-
-static const uint64_t kReadsEventCap = 1ull << 23;           // events per pass (128 MiB)
-
-int mg_reads_begin(mg_ctx *ctx, const mg_params *p, mg_reads_session **out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!p || !out) return fail(ctx, MG_ERR_INVALID, "mg_reads_begin: NULL argument");
-    if (p->kmer_size < 1 || p->kmer_size > 32) return fail(ctx, MG_ERR_INVALID, "mg_sketch: k must be 1..32");
-    // (neither -c nor -b: plain reads mode, any min_copies, in constant memory -- nothing stops the reading)
-    if (p->bloom_bytes && p->min_copies > 1) return fail(ctx, MG_ERR_INVALID, "mg_reads_begin: min_copies cannot be used with bloom_bytes");   // sketchParameterSetup.cpp:44-48
-    if (p->bloom_bytes > (1ull << 60)) return fail(ctx, MG_ERR_INVALID, "mg_reads_begin: bloom_bytes out of range");
-    const bool dna = alphabet_is_dna(p);
-    if (!p->noncanonical && !dna) return fail(ctx, MG_ERR_UNSUPPORTED, "mg_sketch: canonical k-mers need the ACGT alphabet");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    mg_reads_session *rs = new mg_reads_session(p->sketch_size, p->min_copies);
-    rs->ctx = ctx;
-    rs->p = *p;
-    rs->mode = dna ? (p->noncanonical ? 1 : 0) : 2;
-    if (p->bloom_bytes) {
-        try { rs->heap.bloom.init(p->bloom_bytes, p->use64 != 0); }
-        catch (const std::bad_alloc &) { delete rs; return fail(ctx, MG_ERR_NOMEM, "mg_reads_begin: the Bloom filter does not fit in host memory"); }
-    }
-    if (hipMalloc(&rs->d_alpha, 256) != hipSuccess || hipMalloc(&rs->d_ev, kReadsEventCap * sizeof(mg::HashEvent)) != hipSuccess ||
-        hipMalloc(&rs->d_cnt, 8) != hipSuccess ||
-        hipMemcpyAsync(rs->d_alpha, p->alphabet, 256, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        mg_reads_free(rs);
-        return fail(ctx, MG_ERR_NOMEM, "mg_reads_begin: device allocation failed");
-    }
-    *out = rs;
-    return MG_OK;
-}
-
-int mg_reads_add_host(mg_reads_session *rs, const uint8_t *bases, uint64_t nbases, int *stopped_out)
-{
-    if (!rs) return MG_ERR_INVALID;
-    mg_ctx *ctx = rs->ctx;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (stopped_out) *stopped_out = rs->stopped ? 1 : 0;
-    if (!bases && nbases) return fail(ctx, MG_ERR_INVALID, "mg_reads_add_host: NULL bases");
-    if (rs->stopped || nbases == 0) return MG_OK;
-    const mg_params *p = &rs->p;
-    const uint64_t k = (uint64_t)p->kmer_size;
-    // records of the chunk (kseq drops nothing inside a record, so separators are record ends)
-    std::vector<uint64_t> rec_begin, rec_end;
-    for (uint64_t b = 0; b < nbases;) {
-        const void *q = memchr(bases + b, MG_RECORD_SEP, nbases - b);
-        const uint64_t e = q ? (uint64_t)((const uint8_t *)q - bases) : nbases;
-        if (e - b >= k) { rec_begin.push_back(b); rec_end.push_back(e); }   // shorter records are skipped (Sketch.cpp:1222-1226)
-        b = e + 1;
-    }
-    if (rec_begin.empty()) return MG_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (nbases + 64 > rs->d_cap) {
-        if (rs->d_bases) { hipStreamSynchronize(ctx->stream); hipFree(rs->d_bases); rs->d_bases = nullptr; }
-        rs->d_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(nbases + 64, 1ull << 20);
-        if (hipMalloc(&rs->d_bases, cap) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_reads_add_host: device allocation failed");
-        rs->d_cap = cap;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(rs->d_bases, bases, nbases, hipMemcpyHostToDevice, ctx->stream));
-
-    ReadsHeap &heap = rs->heap;
-    const bool cov = p->target_cov > 0;                     // without -c (a -b session) nothing stops the reading
-    const double hash_space = p->use64 ? 18446744073709551616.0 : 4294967296.0;
-    const uint64_t tile = mg::sketch_tile(256);
-    std::vector<mg::HashEvent> &ev = rs->ev;
-    // The unit of a launch is a PIECE: a range of k-mer start positions inside one record.  A record of any length (a
-    // chromosome under -r, Sketch.cpp:1196-1270 has no limit) is cut into pieces of at most kPiece positions -- every
-    // position yields at most one event, so a piece always fits the event buffer -- and the stop test of -c still
-    // follows whole records only (Sketch.cpp:1258).
-    constexpr uint64_t kPiece = kReadsEventCap / 4;
-    struct Piece { uint64_t pb, pe; uint32_t rec; bool last; };
-    std::vector<Piece> pieces;
-    for (size_t r = 0; r < rec_begin.size(); r++) {
-        const uint64_t p0 = rec_begin[r], p1 = rec_end[r] - k + 1;       // k-mer starts [p0, p1)
-        for (uint64_t o = p0; o < p1; o += kPiece) pieces.push_back({o, std::min(p1, o + kPiece), (uint32_t)r, o + kPiece >= p1});
-    }
-    size_t r0 = 0;                                           // next piece
-    size_t rr = 0;                                           // record the replay is in
-    bool touched = false;                                    // ... and whether it changed the heap
-    const uint64_t want_bytes = 2ull << 20;                  // while the heap is not full everything is an event
-    while (r0 < pieces.size() && !rs->stopped) {
-        // pieces [r0, r1): as many as are expected to stay within the event capacity
-        const uint64_t bound = heap.full() ? heap.top() : 0xFFFFFFFFFFFFFFFFull;
-        const double pass = heap.full() ? std::min(1.0, ((double)bound + 1.0) / hash_space) : 1.0;
-        uint64_t budget = (uint64_t)std::min<double>((double)(1ull << 40), (double)(kReadsEventCap / 2) / std::max(pass, 1e-12));
-        if (budget < want_bytes || !heap.full()) budget = want_bytes;
-        budget = (uint64_t)std::max(1.0, (double)budget * rs->shrink);
-        size_t r1 = r0;
-        uint64_t bytes = 0;
-        while (r1 < pieces.size() && (r1 == r0 || bytes + (pieces[r1].pe - pieces[r1].pb) <= budget)) {
-            bytes += pieces[r1].pe - pieces[r1].pb;
-            r1++;
-        }
-        // work items: k-mer start positions [b0, b0 + npos), none reading past the last piece's record
-        const uint64_t b0 = pieces[r0].pb, b1 = rec_end[pieces[r1 - 1].rec];
-        std::vector<mg::SketchWork> work;
-        const uint64_t npos = pieces[r1 - 1].pe - b0;
-        uint64_t chunk = (npos + 4095) / 4096;
-        if (chunk < 2 * tile) chunk = 2 * tile;
-        chunk = (chunk + tile - 1) / tile * tile;
-        for (uint64_t o = 0; o < npos; o += chunk) {
-            mg::SketchWork w;
-            w.begin = b0 + o; w.end = b0 + std::min(npos, o + chunk); w.limit = b1;
-            w.sketch = 0; w.slot = 0; w.nchunks = 1; w._pad = 0;
-            work.push_back(w);
-        }
-        DevBuf<mg::SketchWork> d_work(ctx);
-        if (d_work.alloc(work.size()) != hipSuccess) return fail(ctx, MG_ERR_NOMEM, "mg_reads_add_host: device allocation failed");
-        mg::EventArgs ea;
-        ea.bases = rs->d_bases; ea.work = d_work; ea.alphabet = rs->d_alpha; ea.out = rs->d_ev; ea.count = rs->d_cnt;
-        ea.capacity = kReadsEventCap; ea.bound = bound; ea.seed = p->seed; ea.use64 = p->use64;
-        ea.fold_case = p->preserve_case ? 0 : 1;
-        unsigned long long n_ev = 0;
-        hipError_t e = hipMemcpyAsync(d_work, work.data(), work.size() * sizeof(mg::SketchWork), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(rs->d_cnt, 0, 8, ctx->stream);
-        if (e == hipSuccess) e = mg::launch_hash_events(p->kmer_size, rs->mode, ea, (uint32_t)work.size(), ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&n_ev, rs->d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, MG_ERR_HIP, std::string("mg_reads_add_host: ") + hipGetErrorString(e));
-        if (n_ev > kReadsEventCap) {                         // denser than expected: take fewer pieces
-            if (r1 - r0 == 1) return fail(ctx, MG_ERR_HIP, "mg_reads_add_host: more events than k-mer positions in a piece");
-            rs->shrink /= 4;
-            continue;
-        }
-        rs->shrink = 1.0;
-        ev.resize(n_ev);
-        if (n_ev && hipMemcpy(ev.data(), rs->d_ev, n_ev * sizeof(mg::HashEvent), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(ctx, MG_ERR_HIP, "mg_reads_add_host: D2H copy failed");
-        std::sort(ev.begin(), ev.end(), [](const mg::HashEvent &x, const mg::HashEvent &y) { return x.pos < y.pos; });
-        // replay, record by record; the stop test follows every record that changed the heap
-        auto close_records = [&](size_t upto) {               // records [rr, upto) are complete
-            if (rr < upto) {
-                if (cov && touched && heap.multiplicity() >= p->target_cov) { rs->stopped = true; rs->used = rs->records + rr + 1; }
-                touched = false;
-                rr = upto;
-            }
-        };
-        for (size_t i = 0; i < ev.size() && !rs->stopped; i++) {
-            size_t at = rr;
-            while (ev[i].pos >= rec_end[at]) at++;           // the event's record
-            close_records(at);
-            if (rs->stopped) break;
-            heap.try_insert(ev[i].hash);
-            touched = true;
-        }
-        if (!rs->stopped) close_records(pieces[r1 - 1].last ? (size_t)pieces[r1 - 1].rec + 1 : (size_t)pieces[r1 - 1].rec);
-        r0 = r1;
-    }
-    rs->records += rec_begin.size();
-    if (stopped_out) *stopped_out = rs->stopped ? 1 : 0;
-    return MG_OK;
-}
-
-int mg_reads_finish(mg_reads_session *rs, uint64_t *hashes_out, uint32_t *nhash_out, uint32_t *counts_out, uint64_t *records_used_out)
-{
-    if (!rs) return MG_ERR_INVALID;
-    if (!hashes_out || !nhash_out) return fail(rs->ctx, MG_ERR_INVALID, "mg_reads_finish: NULL argument");
-    const uint64_t s = rs->p.sketch_size;
-    for (uint64_t i = 0; i < s; i++) hashes_out[i] = MG_HASH_PAD;
-    if (counts_out) memset(counts_out, 0, s * 4);
-    uint32_t n = 0;
-    for (const auto &kv : rs->heap.kept) {
-        hashes_out[n] = kv.first;
-        if (counts_out) counts_out[n] = kv.second;
-        n++;
-    }
-    *nhash_out = n;
-    if (records_used_out) *records_used_out = rs->stopped ? rs->used : rs->records;
-    return MG_OK;
-}
-
-int mg_reads_reset(mg_reads_session *rs)
-{
-    if (!rs) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(rs->ctx->mu);
-    ReadsBloom bloom;
-    std::swap(bloom, rs->heap.bloom);                       // keep the filter's memory, clear its bits
-    std::fill(bloom.bits.begin(), bloom.bits.end(), 0);
-    rs->heap = ReadsHeap(rs->p.sketch_size, rs->p.min_copies);
-    std::swap(bloom, rs->heap.bloom);
-    rs->stopped = false;
-    rs->used = rs->records = 0;
-    rs->shrink = 1.0;
-    return MG_OK;
-}
-
-void mg_reads_free(mg_reads_session *rs)
-{
-    if (!rs) return;
-    hipSetDevice(rs->ctx->device);
-    hipStreamSynchronize(rs->ctx->stream);
-    for (void *q : {(void *)rs->d_bases, (void *)rs->d_alpha, (void *)rs->d_ev, (void *)rs->d_cnt})
-        if (q) hipFree(q);
-    delete rs;
-}
-
-int mg_sketch_reads_host(mg_ctx *ctx, const mg_params *p, const uint8_t *bases, uint64_t nbases, uint64_t *hashes_out,
-                         uint32_t *nhash_out, uint32_t *counts_out, uint64_t *records_used_out)
-{
-    if (!ctx) return MG_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!p || !hashes_out || !nhash_out || (!bases && nbases)) return fail(ctx, MG_ERR_INVALID, "mg_sketch_reads_host: NULL argument");
-    if (p->kmer_size < 1 || p->kmer_size > 32) return fail(ctx, MG_ERR_INVALID, "mg_sketch: k must be 1..32");
-    if (!(p->target_cov > 0) && p->bloom_bytes == 0) {
-        // records of the batch (shorter ones are skipped, Sketch.cpp:1222-1226): the "reads used" of a run without -c
-        const uint64_t k = (uint64_t)p->kmer_size;
-        uint64_t nrec = 0;
-        for (uint64_t b = 0; b < nbases;) {
-            const void *q = memchr(bases + b, MG_RECORD_SEP, nbases - b);
-            const uint64_t e = q ? (uint64_t)((const uint8_t *)q - bases) : nbases;
-            if (e - b >= k) nrec++;
-            b = e + 1;
-        }
-        if (records_used_out) *records_used_out = nrec;
-        mg_params q = *p;
-        q.target_cov = 0;
-        const uint64_t off[2] = {0, nbases};
-        return mg_sketch_host(ctx, &q, bases, nbases, off, 1, hashes_out, nhash_out, counts_out);
-    }
-    // one chunk through the session
-    mg_reads_session *rs = nullptr;
-    int rc = mg_reads_begin(ctx, p, &rs);
-    if (rc != MG_OK) return rc;
-    rc = mg_reads_add_host(rs, bases, nbases, nullptr);
-    if (rc == MG_OK) rc = mg_reads_finish(rs, hashes_out, nhash_out, counts_out, records_used_out);
-    mg_reads_free(rs);
-    return rc;
-}
-

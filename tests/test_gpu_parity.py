@@ -302,6 +302,46 @@ def test_sketch_packed_input_matches_the_ascii_path(eng, oracle, kw, monkeypatch
         assert want_n[i] == len(oh) and np.array_equal(h[i, : len(oh)], oh) and np.array_equal(c[i, : len(oh)], oc), (kw, i)
 
 
+def _reads_of(rng, g, cov, lo=60, hi=200):
+    """reads of both strands over genome g until `cov` times its length is covered"""
+    out, tot = [], 0
+    while tot < cov * len(g):
+        l = int(rng.integers(lo, hi))
+        st = int(rng.integers(0, len(g) - l))
+        r = g[st:st + l]
+        out.append(r if rng.random() < 0.5 else _revcomp(r))
+        tot += l
+    return out
+
+
+@pytest.mark.parametrize("kw", [dict(k=21, s=200, min_copies=2), dict(k=21, s=13000)])
+def test_sketch_packed_input_into_the_range_path(eng, oracle, kw, monkeypatch):
+    """Packed input that the sketch kernel cannot read itself -- min_copies > 1, a sketch size beyond the LDS selector -- is
+    unpacked to ASCII and takes the range-counting path: == mg_sketch_host on the same bytes, hashes, counts and multiplicities,
+    the batch as one piece and in pieces of a few thousand bases; three sketches also against the oracle.  Read sets at 4x so
+    that k-mers repeat; at s = 13000 one sketch comes out full and the others short."""
+    rng = np.random.default_rng(131 + kw["s"])
+    sketches = [synth.adversarial_dna_records(rng, v) for v in range(5)]
+    sketches += [_reads_of(rng, synth._rand_dna(rng, 6000), 4.0) for _ in range(2)]
+    sketches.append([b""])
+    bases, off, packed, mask, ninv = _packed_batch(sketches)
+    p = eng.params(**kw)
+    want_h, want_n, want_c = eng.sketch_host_raw(bases, off, p, counts=True)
+    for piece in (None, "4000"):
+        if piece:
+            monkeypatch.setenv("MASHGPU_PACKED_PIECE", piece)
+        h, n, c = eng.sketch_host_packed_raw(packed, mask, len(bases), off, p, counts=True)
+        assert np.array_equal(n, want_n), (kw, piece, n, want_n)
+        assert np.array_equal(h, want_h), (kw, piece, np.argwhere(h != want_h)[:5])
+        assert np.array_equal(c, want_c), (kw, piece, np.argwhere(c != want_c)[:5])
+    if kw["s"] == 13000:
+        assert np.all(want_n[[0, 5, 6]] < 13000) and want_n.max() == 13000
+    for i in (0, 5, 6):
+        oh, oc, _, _, _ = oracle.sketch_records(sketches[i], oracle.params(**kw))
+        assert want_n[i] == len(oh) and np.array_equal(h[i, : len(oh)], oh) and np.array_equal(c[i, : len(oh)], oc), (kw, i)
+    assert want_n[5] > 0 and want_n[6] > 0
+
+
 def test_sketch_batch_of_nothing_but_empty_sketches(eng):
     """No sketch of the batch holds a k-mer: hashes padded, counts ZERO (they used to be left as the pool handed them out --
     found by the packed path, which sketches piece by piece)."""
@@ -495,6 +535,21 @@ def test_streamed_ingest_equals_one_batch(eng, oracle, stage, monkeypatch):
             eng.lib.mg_sketch_session_free(ss)
     h, n = eng.sketch_stream([[b""], [b"AC"]], p)                       # nothing but empty sketches
     assert h.shape == (2, 400) and not n.any() and np.all(h == np.uint64(abi.HASH_PAD))
+
+
+def test_streamed_ingest_with_min_copies_and_counts(eng, monkeypatch):
+    """A streamed session whose parameters take the range-counting path (min_copies = 2) and the multiplicity pass ==
+    mg_sketch_host on the same sketches: the first two read sets of test_sketch_min_copies_rounds_and_batches and its sketch
+    without a k-mer, in pieces of 1000 bytes through staging buffers of 4096, so that every read set spans many of them."""
+    monkeypatch.setenv("MASHGPU_STAGE_BYTES", "4096")
+    rng = np.random.default_rng(21)
+    sets = [_reads_of(rng, synth._rand_dna(rng, 30000), 5.0), _reads_of(rng, synth._rand_dna(rng, 8000), 2.0), [b"ACGT"]]
+    p = eng.params(k=21, s=400, min_copies=2)
+    want = eng.sketch_host(sets, p, counts=True)
+    got = eng.sketch_stream(sets, p, counts=True, piece=1000)
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b)
+    assert want[1][0] > 0 and want[1][2] == 0 and want[2][0, : want[1][0]].min() >= 2
 
 
 def test_sketch_reads_json_golden(eng, golden_dir):
