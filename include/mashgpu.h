@@ -414,6 +414,32 @@ int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *
 int mg_compare_tri_topk_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, int kmer_size,
                              double kmer_space, double max_distance, double max_p_value, uint32_t k, mg_result *out_host,
                              uint64_t capacity, uint64_t *count_out);
+/* Containment of queries in references, ON THE DEVICE (within.hip) -- `mash within`.  containSketches (CommandContain.cpp:
+ * 231-263) walks reference R and query Q, both ascending, with two pointers and stops when the query pointer j reaches
+ * min(|R|, |Q|) or R is exhausted; it returns score = common / j and error = 1 / sqrt(j).  In closed form, in integers:
+ *   c      = #{q in Q : q <= max(R)}
+ *   j      = min(|R|, |Q|, c)                 (0 if either sketch is empty)
+ *   common = #(Q[0 .. j) ∩ R)
+ * and these calls return the two integers, {numer = common, denom = j}; the caller divides.  |R| and |Q| are the rows' OWN hash
+ * counts (nhash), not min(nhash, s) of a common s: the tables may differ in sketch size, either way round (Sketch.cpp:150
+ * accepts smaller query sketches).  Lengths are not needed.  Pairs are query-major as in mg_compare_rect_host; q_end is clamped
+ * to the query table and an empty range writes nothing.
+ *   mg_within_rect_host          every pair: out[(q - q_begin) * nref + r]                  (contain(), CommandContain.cpp:205-229)
+ *   mg_within_rect_results_host  only the pairs `mash within -e` prints (writeOutput, CommandContain.cpp:179-203: `error <=
+ *                                threshold`), that is j >= 1 and 1 / sqrt(j) <= max_error, as {row = query, col = reference,
+ *                                numer, denom}, strictly ascending by (row, col).  The host turns max_error into the smallest
+ *                                passing j and the device compares integers: a pair is dropped after one binary search, a
+ *                                sketch of too few hashes drops its row or column without any, and `common` is counted for
+ *                                the survivors alone.  max_error >= 1 (or +inf) keeps every pair with j >= 1; max_error <= 0
+ *                                or NaN keeps none.  The reference compares against (double)(float)e: that conversion is the
+ *                                caller's.  capacity / *count_out / MG_ERR_NOMEM as for mg_compare_rect_results_host
+ *                                (capacity 0 with out_host NULL asks for the count alone).
+ * Limits: one device (no sharded form), host output only (no *_dev form), sketch sizes below 2^32 - 1, fewer than 2^31
+ * references. */
+int mg_within_rect_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin, uint64_t q_end,
+                        mg_counts *out_host);
+int mg_within_rect_results_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin, uint64_t q_end,
+                                double max_error, mg_edge *out_host, uint64_t capacity, uint64_t *count_out);
 /* Single-linkage clusters of the thresholded all-vs-all, found ON THE DEVICE (cluster.hip) -- `mash cluster`.  The reference
  * has no such command (its user feeds the lines of `mash triangle -E` to a union-find of their own); the definition stands on
  * those lines:

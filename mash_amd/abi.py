@@ -32,6 +32,7 @@ EXPORTS = [
     "mg_finish_tri_host", "mg_finish_rect_host", "mg_distance", "mg_p_value",
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host", "mg_compare_tri_topk_host",
+    "mg_within_rect_host", "mg_within_rect_results_host",
     "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
     "mg_cluster_tri_nearest_host", "mg_cluster_tri_nearest_dev", "mg_cluster_tri_medoid_host", "mg_cluster_tri_medoid_dev",
     "mg_cluster_extend_host", "mg_cluster_extend_greedy_host",
@@ -325,6 +326,8 @@ def load_library():
     lib.mg_compare_rect_results_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
     lib.mg_compare_rect_topk_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_compare_tri_topk_host.argtypes = [vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
+    lib.mg_within_rect_host.argtypes = [vp, vp, vp, u64, u64, vp]
+    lib.mg_within_rect_results_host.argtypes = [vp, vp, vp, u64, u64, dbl, vp, u64, vp]
     lib.mg_comm_create_local.argtypes = [C.POINTER(C.c_int), i32, C.POINTER(vp)]
     lib.mg_comm_unique_id.argtypes = [vp, C.c_size_t]
     lib.mg_comm_create_rank.argtypes = [vp, vp, C.c_size_t, i32, i32, C.POINTER(vp)]
@@ -946,6 +949,20 @@ class MashGpu:
     def compare_rect_sparse(self, ref, qry, q_begin=0, q_end=None, capacity=1 << 20):
         q_end = qry.rows if q_end is None else min(q_end, qry.rows)
         return self._filter(lambda o, c, n: self.lib.mg_compare_rect_sparse_host(self.ctx, ref.handle, qry.handle, q_begin, q_end, o, c, n), capacity)
+
+    def within_rect_host(self, ref, qry, q_begin=0, q_end=None):
+        """`mash within`, every pair: out[q - q_begin, r] = {numer = common, denom = j} (mg_within_rect_host)"""
+        q_end = qry.rows if q_end is None else min(q_end, qry.rows)
+        out = np.zeros((max(q_end - q_begin, 0), ref.rows), dtype=COUNTS_DTYPE)
+        self._check(self.lib.mg_within_rect_host(self.ctx, ref.handle, qry.handle, q_begin, q_end, out.ctypes.data))
+        return out
+
+    def within_rect_results(self, ref, qry, max_error, q_begin=0, q_end=None, capacity=1 << 20):
+        """the pairs with j >= 1 and 1 / sqrt(j) <= max_error as {row = query, col = reference, numer = common, denom = j},
+        query-major (mg_within_rect_results_host)"""
+        q_end = qry.rows if q_end is None else min(q_end, qry.rows)
+        return self._filter(lambda o, c, n: self.lib.mg_within_rect_results_host(
+            self.ctx, ref.handle, qry.handle, q_begin, q_end, max_error, o, c, n), capacity)
 
     def expand_tri_sparse(self, edges, nhash, s, row_begin, row_end):
         """the dense triangle out of the rule and the exceptions (host arithmetic)"""

@@ -21,6 +21,18 @@ int out_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t 
 // rows [r, r2): `pairs` pairs, `before` pairs of the range ahead of them
 struct RowBlock { uint64_t r, r2, pairs, before; };
 
+// The range in blocks of whole rows of at most max_pairs pairs (a block always takes its first row); *largest: the pairs of the
+// largest block, which the caller's device buffers hold
+std::vector<RowBlock> row_blocks(const OutRange &R, uint64_t max_pairs, uint64_t *largest);
+
+// A caller's buffer of `capacity` records while blocks fill it: `total` counts on past the capacity (the caller is told the true
+// count), nothing is written past it
+struct Room {
+    uint64_t capacity, total = 0;
+    uint64_t left() const { return total <= capacity ? capacity - total : 0; }
+    template <class T> T *at(T *out) const { return out + std::min(total, capacity); }
+};
+
 // How a caller has its matrix cut: row blocks of at most `pairs` pairs -- or of what the option `knob` says (the tests' way to many
 // blocks): below `pairs`, or up to `ceiling` where a caller sets one -- and the caller's name in the allocation error
 struct Blocks { uint64_t pairs; const char *knob, *who; uint64_t ceiling = 0; };

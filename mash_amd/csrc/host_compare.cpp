@@ -1519,7 +1519,7 @@ int out_range(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t 
 
 // The range in blocks of whole rows of at most max_pairs pairs (a block always takes its first row); *largest: the pairs of the
 // largest block, which the caller's device buffers hold
-static std::vector<RowBlock> row_blocks(const OutRange &R, uint64_t max_pairs, uint64_t *largest)
+std::vector<RowBlock> row_blocks(const OutRange &R, uint64_t max_pairs, uint64_t *largest)
 {
     std::vector<RowBlock> v;
     *largest = 0;
@@ -1562,14 +1562,6 @@ static int matrix_blocks(mg_ctx *ctx, const OutRange &R, const Blocks &how, DevB
     }
     return MG_OK;
 }
-
-// A caller's buffer of `capacity` records while blocks fill it: `total` counts on past the capacity (the caller is told the true
-// count), nothing is written past it
-struct Room {
-    uint64_t capacity, total = 0;
-    uint64_t left() const { return total <= capacity ? capacity - total : 0; }
-    template <class T> T *at(T *out) const { return out + std::min(total, capacity); }
-};
 
 // host-output variants: bounded device staging, processed in row blocks
 static int compare_host(mg_ctx *ctx, const mg_table *rows, const mg_table *cols, uint64_t rb, uint64_t re,

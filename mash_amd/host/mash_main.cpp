@@ -748,7 +748,7 @@ void queue_parsed_group(Gpu &gpu, SketchSet &set, PendingBatch &b, vector<Parsed
 }
 
 void init_from_files(Gpu &gpu, SketchSet &set, const vector<string> &files, const Params &p, int verbosity = 1,
-                     bool enforce_parameters = false, ParsePool *early = nullptr)
+                     bool enforce_parameters = false, ParsePool *early = nullptr, bool contain = false)
 {
     set.p = p;
     PendingBatch b;
@@ -784,7 +784,7 @@ void init_from_files(Gpu &gpu, SketchSet &set, const vector<string> &files, cons
         if (has_suffix(files[i], kSuffix)) {
             g_progress.flush();
             flush_batch(gpu, set, b);                      // keep input order
-            load_msh_into(set, files[i], i == 0 && !enforce_parameters);
+            load_msh_into(set, files[i], i == 0 && !enforce_parameters, contain);
             if (pool) pool->skip(i);
             continue;
         }
@@ -1428,6 +1428,36 @@ int dist_full(DistRun &r)
     return 0;
 }
 
+// What `dist` and `within` do with their first argument before a device is opened: a .msh reference refuses the options it
+// fixes itself -- `fatal` end the run, `message_only` print the same message and the run goes on --, anything else is
+// announced as being sketched.  Non-zero: refused.
+int reference_announce(const Cmd &c, const string &file_ref, bool is_sketch, std::initializer_list<const char *> fatal,
+                       std::initializer_list<const char *> message_only)
+{
+    if (!is_sketch) {
+        cerr << "Sketching " << file_ref << " (provide sketch file made with \"mash sketch\" to skip)...";
+        return 0;
+    }
+    auto refuse = [&](const char *o) {
+        if (c.o(o).active) cerr << "ERROR: The option -" << c.o(o).id << " cannot be used when a sketch is provided; it is inherited from the sketch." << endl;
+        return c.o(o).active;
+    };
+    for (const char *o : fatal) if (refuse(o)) return 1;
+    for (const char *o : message_only) refuse(o);
+    return 0;
+}
+
+// the parameters the queries are sketched with come from a .msh reference (CommandDistance.cpp:130-140, CommandContain.cpp:95-106)
+void inherit_from_reference(Params &p, const SketchSet &ref)
+{
+    p.sketch_size = ref.p.sketch_size;
+    p.kmer = ref.p.kmer;
+    p.noncanonical = ref.p.noncanonical;
+    p.preserve_case = ref.p.preserve_case;
+    p.seed = ref.p.seed;
+    set_alphabet(p, ref.p.alphabet);
+}
+
 int cmd_dist(int argc, const char **argv)
 {
     Cmd c;
@@ -1460,15 +1490,7 @@ int cmd_dist(int argc, const char **argv)
     if (sketch_parameter_setup(p, c)) return 1;
     const string &file_ref = c.args[0];
     const bool is_sketch = has_suffix(file_ref, kSuffix);
-    if (is_sketch) {
-        for (const char *o : {"kmer", "noncanonical", "protein", "alphabet"})
-            if (c.o(o).active) {
-                cerr << "ERROR: The option -" << c.o(o).id << " cannot be used when a sketch is provided; it is inherited from the sketch." << endl;
-                return 1;
-            }
-    } else {
-        cerr << "Sketching " << file_ref << " (provide sketch file made with \"mash sketch\" to skip)...";
-    }
+    if (reference_announce(c, file_ref, is_sketch, {"kmer", "noncanonical", "protein", "alphabet"}, {})) return 1;
     Gpu gpu;
     SketchSet ref;
     init_from_files(gpu, ref, {file_ref}, p, is_sketch ? 1 : 0);
@@ -1478,12 +1500,7 @@ int cmd_dist(int argc, const char **argv)
             cerr << "ERROR: The sketch size must match the reference when using a bloom filter (leave this option out to inherit from the reference sketch)." << endl;
             return 1;
         }
-        p.sketch_size = ref.p.sketch_size;
-        p.kmer = ref.p.kmer;
-        p.noncanonical = ref.p.noncanonical;
-        p.preserve_case = ref.p.preserve_case;
-        p.seed = ref.p.seed;
-        set_alphabet(p, ref.p.alphabet);
+        inherit_from_reference(p, ref);
     } else {
         w = scan_kmer_warning(ref);
         cerr << "done.\n";
@@ -1503,6 +1520,89 @@ int cmd_dist(int argc, const char **argv)
     DistRun run(gpu, ref, qry, table, comment, nearest, d_max, p_max, ref_by_rows);
     if (nearest ? dist_nearest(run) : !table && edge_filter_wanted(d_max, p_max) ? dist_filtered(run) : dist_full(run)) return 1;
     return finish_run(ref, w, p.reads);
+}
+
+// ------------------------------------------------------------------------------- within
+// `mash within` (CommandContain.cpp): per query and reference, how much of the query's sketch lies inside the reference's --
+// score = common / j and error = 1 / sqrt(j) of containSketches (:231-263), printed where error <= -e (writeOutput, :179-203).
+// The device returns the two integers (mg_within_rect_results_host: only the pairs that pass -e cross PCIe; with
+// MASH_AMD_HOST_FINISH=1 every pair's, filtered here); both doubles are formed here.
+const uint64_t kWithinFullPairs = 1ull << 26;       // MASH_AMD_HOST_FINISH=1: 512 MiB of mg_counts per block
+
+inline void print_within_line(FastOut &out, const Ref &ref, const Ref &qry, uint32_t common, uint32_t j)
+{
+    out << double(common) / j << '\t' << 1. / sqrt(j) << '\t' << ref.name << '\t' << qry.name;
+    out.eol();
+}
+
+int cmd_within(int argc, const char **argv)
+{
+    Cmd c;
+    c.name = "within";
+    c.add("help", Opt::Boolean, "h");
+    c.add("list", Opt::Boolean, "l");
+    c.add("errorThreshold", Opt::Number, "e", "0.05");
+    c.use_sketch_options();
+    if (c.parse(argc, argv)) return 1;
+    if (c.args.size() < 2 || c.o("help").active) {
+        cout << "\nUsage:\n\n  mash within [options] <reference> <query> [<query>] ...\n\n"
+                "Estimate the containment of each query file (or sequence with -i) in the reference: the number of\n"
+                "intersecting min-hashes divided by the query set size.\n"
+                "Output fields: [score, error-bound, reference-ID, query-ID].\n"
+                "Options: -l -e <max error> and the sketch options of `mash sketch`.\n"
+                "  -e <num>  Error bound threshold for reporting scores values. [0.05]\n\n";
+        return 0;
+    }
+    // the threshold reaches writeOutput as a float (CommandContain.cpp:167, :179) and is compared as a double (:188)
+    const double e_max = (double)c.o("errorThreshold").num;
+    Params p;
+    if (sketch_parameter_setup(p, c)) return 1;
+    const string &file_ref = c.args[0];
+    const bool is_sketch = has_suffix(file_ref, kSuffix);
+    // (-a and -z print the refusal and the run goes on: CommandContain.cpp:73-81 has no `return 1`)
+    if (reference_announce(c, file_ref, is_sketch, {"kmer", "noncanonical"}, {"protein", "alphabet"})) return 1;
+    Gpu gpu;
+    SketchSet ref;
+    init_from_files(gpu, ref, {file_ref}, p, is_sketch ? 1 : 0);
+    if (is_sketch) inherit_from_reference(p, ref);
+    else cerr << "done.\n";
+    SketchSet qry;
+    init_from_files(gpu, qry, input_files(c, 1), p, 0, true, nullptr, true);     // (a smaller sketch size is accepted, Sketch.cpp:150)
+    const uint64_t nref = ref.refs.size(), nq = qry.refs.size();
+    if (nref == 0 || nq == 0) return 0;
+    // the rows' own hash counts decide, so each table is as wide as its longest row
+    uint64_t s_ref = 1, s_qry = 1;
+    for (const Ref &r : ref.refs) s_ref = std::max<uint64_t>(s_ref, r.hashes.size());
+    for (const Ref &r : qry.refs) s_qry = std::max<uint64_t>(s_qry, r.hashes.size());
+    DTable dr(upload_all(gpu, ref, s_ref)), dq(upload_all(gpu, qry, s_qry));
+    const mg_table *tr = mg_dtable_local(dr.get(), 0), *tq = mg_dtable_local(dq.get(), 0);
+    FastOut out;
+    if (host_finish_wanted()) {
+        vector<mg_counts> counts;
+        for (Blocks b(0, nq, kWithinFullPairs, nref); b.next();) {
+            counts.resize(b.npairs);
+            if (mg_within_rect_host(gpu.ctx, tr, tq, b.r0, b.r1, counts.data()) != MG_OK) return report_error(gpu);
+            const uint64_t q0 = b.r0;
+            emit_rows(out, b.r0, b.r1, [&](uint64_t) { return nref; }, [&](FastOut &o, uint64_t q, unsigned) {
+                for (uint64_t x = 0; x < nref; x++) {
+                    const mg_counts &k = counts[(q - q0) * nref + x];
+                    if (k.denom && 1. / sqrt(k.denom) <= e_max) print_within_line(o, ref.refs[x], qry.refs[q], k.numer, k.denom);
+                }
+            });
+        }
+        return 0;
+    }
+    vector<mg_edge> res;
+    for (Blocks b(0, nq, kDistFilteredPairs, nref); b.next();) {
+        if (!fetch_list(gpu, res, [&](mg_edge *o, uint64_t cap, uint64_t *n) {
+                return mg_within_rect_results_host(gpu.ctx, tr, tq, b.r0, b.r1, e_max, o, cap, n); }))
+            return 1;
+        emit_rows(out, 0, res.size(), [](uint64_t) { return 1; }, [&](FastOut &o, uint64_t x, unsigned) {
+            const mg_edge &k = res[x];
+            print_within_line(o, ref.refs[k.col], qry.refs[k.row], k.numer, k.denom);
+        });
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------- triangle
@@ -2715,6 +2815,7 @@ int main(int argc, const char **argv)
     const string usage =
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
         "  dist      Estimate the distance of query sequences to references.\n"
+        "  within    Estimate the containment of query sequences within references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n"
         "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), name each single-linkage cluster's medoid (-M), extend an earlier clustering by new sequences (-A), or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
@@ -2733,6 +2834,7 @@ int main(int argc, const char **argv)
     int rc;
     if (cmd == "sketch") rc = cmd_sketch(argc - 2, argv + 2);
     else if (cmd == "dist") rc = cmd_dist(argc - 2, argv + 2);
+    else if (cmd == "within") rc = cmd_within(argc - 2, argv + 2);
     else if (cmd == "triangle") rc = cmd_triangle(argc - 2, argv + 2);
     else if (cmd == "cluster") rc = cmd_cluster(argc - 2, argv + 2);
     else if (cmd == "info") rc = cmd_info(argc - 2, argv + 2);

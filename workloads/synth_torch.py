@@ -169,3 +169,45 @@ def synthetic_reads(genomes, n_reads, read_len=150, seed=0, err=0.005):
     out[:, :read_len] = lut[code]
     return out
 
+
+
+def containment_tables(nref, s_ref, nqry, s_qry, shares=(0.02, 0.05), mutate=0.03, seed=0, device="cuda", block=4096):
+    """Tables for `mash within`: nref references, each the bottom s_ref hashes of a genome of its own (ascending values below a
+    bound T = 2^40 * s_ref), and nqry queries of s_qry hashes, query q a contig of reference q % nref that covers share
+    shares[q % len(shares)] of it: every (1 / share)-th hash of the reference from a random offset -- a fraction `mutate` of them
+    replaced by new values below T --, then hashes of its own above T up to s_qry (a contig's sketch reaches further up than
+    its genome's).  Returns ((ref hashes int64[nref, s_ref], nhash int32, lengths int64), (the same for the queries)); rows are
+    full, ascending and distinct."""
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    T = (1 << 40) * s_ref
+
+    def distinct_rows(rows, lo, hi, n):
+        while True:
+            h = torch.sort(torch.randint(lo, hi, (rows, n), generator=g, device=device, dtype=torch.int64), dim=1).values
+            if n < 2 or bool((h[:, 1:] > h[:, :-1]).all()):
+                return h
+    ref = distinct_rows(nref, 0, T, s_ref)
+    qry = torch.empty((nqry, s_qry), dtype=torch.int64, device=device)
+    for b in range(0, nqry, block):
+        e = min(nqry, b + block)
+        q = torch.arange(b, e, device=device)
+        for v, share in enumerate(shares):
+            rows = q[q % len(shares) == v]
+            if not len(rows):
+                continue
+            c = min(int(share * s_ref), s_qry)
+            step = max(1, s_ref // max(c, 1))
+            off = torch.randint(0, step, (len(rows), 1), generator=g, device=device)
+            idx = off + step * torch.arange(c, device=device).unsqueeze(0)
+            part = ref[(rows % nref).unsqueeze(1), idx]
+            new = torch.randint(0, T, part.shape, generator=g, device=device, dtype=torch.int64)
+            part = torch.where(torch.rand(part.shape, generator=g, device=device) < mutate, new, part)
+            own = torch.randint(T, 2 * T, (len(rows), s_qry - c), generator=g, device=device, dtype=torch.int64)
+            qry[rows] = torch.sort(torch.cat([part, own], dim=1), dim=1).values
+    assert bool((qry[:, 1:] > qry[:, :-1]).all()), "a query row is not strictly ascending: another seed"
+
+    def pack(h, length):
+        n, s = h.shape
+        return h.contiguous(), torch.full((n,), s, dtype=torch.int32, device=device), torch.full((n,), length, dtype=torch.int64, device=device)
+    return pack(ref, 5_000_000), pack(qry, 100_000)
