@@ -594,6 +594,44 @@ int mg_cluster_forest_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *regrows
  * r < min(*rounds_out, capacity), live_out[r] = the edges whose ends lay in two components when it began, chosen_out[r] = the forest
  * edges it chose (0 in the last round).  *rounds_out = mg_cluster_forest_stats' rounds, always. */
 int mg_cluster_forest_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *chosen_out, uint64_t capacity, uint64_t *rounds_out);
+/* Complete-linkage clusters of the same thresholded all-vs-all, cut at the threshold, found ON THE DEVICE (cluster_complete.hip) --
+ * `mash cluster -L`.  The reference has no such command (its user pipes `mash triangle -E -d` into hclust or scipy on the host); the
+ * definition stands on those lines:
+ *   edge     : exactly a pair {row, col}, col < row, that mg_compare_tri_results_host(ctx, t, 0, rows, kmer_size, kmer_space,
+ *              max_distance, max_p_value, ...) returns -- the edge of mg_cluster_tri_host -- with its counts numer / denom;
+ *   cluster  : its id is its smallest row; start from singletons;
+ *   link     : two clusters A, B are linked iff every pair {a in A, b in B} is an edge; the link's weight is the worst of those
+ *              edges, the smallest fraction numer/denom, compared exactly by cross-multiplication in 64-bit integers (0/0, two
+ *              empty sketches, counts as 0/1);
+ *   order    : larger weight first; equal weights, also under different denominators, by ascending larger id, then ascending
+ *              smaller id -- the order of mg_cluster_tri_forest_host's edges with the ids in the rows' place;
+ *   clusters : repeat: merge the first link in that order, the new cluster keeps the smaller id; stop when no link is left;
+ *   label[i] : the id of i's final cluster;  n_clusters : the number of i with label[i] == i;  n_edges : mg_cluster_tri_host's.
+ * Every cluster is a clique of the edge graph, no two final clusters are linked, and the partition is a function of the edges and
+ * their counts alone: of no execution order, route or blocking.  (The device merges every link that is the first of BOTH its
+ * clusters at once, round after round; that performs exactly the merges of the walk above.)
+ * The whole table only, one device, at most 2^31 - 1 rows; a sketch size of 2^21 or more: MG_ERR_UNSUPPORTED (the 64-bit weight key
+ * is exact for denominators below 2^21).  Both filters disabled (each < 0 or >= 1): MG_ERR_INVALID; everything else fails as
+ * mg_cluster_tri_host does.  A table of 0 or 1 rows: MG_OK.  While the call runs the device keeps 16 bytes an edge (the list of
+ * mg_cluster_tri_forest_host: it grows on demand, MASHGPU_FOREST_EDGE_CAP sets its first capacity), 8 for its key, 8 for the key a
+ * round decides on, and 32 for the index from a pair to its edge (open addressing, load below one half); if they do not fit the
+ * call returns MG_ERR_NOMEM, it never drops an edge.  Dead links are skipped, not compacted.  The rounds are queued in batches of 8,
+ * 16, ... 256 with one wait per batch (the context option MASHGPU_COMPLETE_BATCH sets the first batch's size, a test knob); a clique
+ * whose fractions tie throughout merges one pair per round, so up to `rows` rounds can be needed.  Only rows x 4 bytes cross PCIe;
+ * _dev leaves the labels on the device.  There is no dendrogram output.
+ * mg_cluster_complete_stats: what the context's last such call needed -- rounds (the last of them merging nothing; 0 without an
+ * edge), batches waited for, times the edge list was regrown, its final capacity in edges (any pointer may be NULL).
+ * mg_cluster_complete_rounds: those rounds one by one (a measuring aid, tools/complete_bench.py): for round r < min(*rounds_out,
+ * capacity), live_out[r] = the links alive when it began, merged_out[r] = the links it merged.  *rounds_out = the stats' rounds. */
+int mg_cluster_tri_complete_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                                 double max_p_value, uint32_t *label_out_host /* [rows] */, uint64_t *n_clusters_out,
+                                 uint64_t *n_edges_out);
+int mg_cluster_tri_complete_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                                double max_p_value, uint32_t *label_out_dev /* [rows] */, uint64_t *n_clusters_out,
+                                uint64_t *n_edges_out);
+int mg_cluster_complete_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out,
+                              uint64_t *edge_capacity_out);
+int mg_cluster_complete_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *merged_out, uint64_t capacity, uint64_t *rounds_out);
 /* Scalar helpers (same arithmetic as the bulk calls). */
 double mg_distance(uint32_t numer, uint32_t denom, int kmer_size);
 double mg_p_value(uint64_t x, uint64_t len_ref, uint64_t len_qry, double kmer_space,

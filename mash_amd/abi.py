@@ -37,6 +37,7 @@ EXPORTS = [
     "mg_cluster_tri_nearest_host", "mg_cluster_tri_nearest_dev", "mg_cluster_tri_medoid_host", "mg_cluster_tri_medoid_dev",
     "mg_cluster_extend_host", "mg_cluster_extend_greedy_host",
     "mg_cluster_tri_forest_host", "mg_cluster_forest_stats", "mg_cluster_forest_rounds",
+    "mg_cluster_tri_complete_host", "mg_cluster_tri_complete_dev", "mg_cluster_complete_stats", "mg_cluster_complete_rounds",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
@@ -377,6 +378,10 @@ def load_library():
     lib.mg_cluster_tri_forest_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, u64, vp, vp, vp, vp]
     lib.mg_cluster_forest_stats.argtypes = [vp, vp, vp, vp]
     lib.mg_cluster_forest_rounds.argtypes = [vp, vp, vp, u64, vp]
+    lib.mg_cluster_tri_complete_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_tri_complete_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
+    lib.mg_cluster_complete_stats.argtypes = [vp, vp, vp, vp, vp]
+    lib.mg_cluster_complete_rounds.argtypes = [vp, vp, vp, u64, vp]
     lib.mg_compare_rect_topk_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_dscreen_create.argtypes = [vp, C.POINTER(MgParams), vp, i32, C.POINTER(vp)]
     lib.mg_dscreen_add_host.argtypes = [vp, vp, u64]
@@ -1146,6 +1151,37 @@ class MashGpu:
         n = C.c_uint64(0)
         self._check(self.lib.mg_cluster_forest_rounds(self.ctx, live.ctypes.data, chosen.ctypes.data, 64, C.byref(n)))
         return live[:n.value].tolist(), chosen[:n.value].tolist()
+
+    def cluster_tri_complete_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0):
+        """complete-linkage clusters of the pairs compare_tri_results returns for the whole table, cut at the threshold, found on the
+        device: (label u32[rows] = the smallest row of the row's cluster, clusters, edges).  Every cluster is a clique of those
+        pairs; links merge best first by the exact fraction numer/denom of their worst pair, equal fractions by the larger, then the
+        smaller cluster id (mg_cluster_tri_complete_host)"""
+        label = np.zeros(table.rows, dtype=np.uint32)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_complete_host(self.ctx, table.handle, k, kmer_space, max_d, max_p, label.ctypes.data, C.byref(nc), C.byref(ne)))
+        return label, int(nc.value), int(ne.value)
+
+    def cluster_tri_complete_dev(self, table, k, kmer_space, label_ptr, max_d=-1.0, max_p=-1.0):
+        """cluster_tri_complete_host with the labels left on the device at label_ptr (u32[rows]): (clusters, edges)"""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_complete_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, label_ptr, C.byref(nc), C.byref(ne)))
+        return int(nc.value), int(ne.value)
+
+    def cluster_complete_stats(self):
+        """what this context's last cluster_tri_complete_* call needed: {rounds, batches, regrows, edge_capacity} (mg_cluster_complete_stats)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._check(self.lib.mg_cluster_complete_stats(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("rounds", "batches", "regrows", "edge_capacity"), (int(x.value) for x in v)))
+
+    def cluster_complete_rounds(self):
+        """the rounds of this context's last cluster_tri_complete_* call: (links alive when each began, links each merged)
+        (mg_cluster_complete_rounds)"""
+        n = C.c_uint64(0)
+        self._check(self.lib.mg_cluster_complete_rounds(self.ctx, None, None, 0, C.byref(n)))
+        live, merged = np.zeros(max(n.value, 1), dtype=np.uint64), np.zeros(max(n.value, 1), dtype=np.uint64)
+        self._check(self.lib.mg_cluster_complete_rounds(self.ctx, live.ctypes.data, merged.ctypes.data, n.value, C.byref(n)))
+        return live[:n.value].tolist(), merged[:n.value].tolist()
 
     def finish_tri_dev(self, table, counts_ptr, row_begin, row_end, k, kmer_space, max_d, max_p, out_ptr):
         self._check(self.lib.mg_finish_tri_dev(self.ctx, table.handle, counts_ptr, row_begin, row_end, k, kmer_space,

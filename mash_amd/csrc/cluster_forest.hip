@@ -25,7 +25,7 @@
 //        change while edges are read, so "live" means the same to K1, K2 and K3 of a round.
 //   (F2) Inside a launch the only racing accesses are the monotone atomics on best_key (only ever raised) and best_rc (only ever
 //        lowered), and the union's on parent[], which has its proof in cluster.hip.  The relaxed agent-scope load in front of an atomic
-//        (cf_offer_*) only SKIPS an edge that cannot win: a stale value is an older one -- smaller for best_key, larger for best_rc --
+//        (cf_offer_*, cluster_internal.h) only SKIPS an edge that cannot win: a stale value is an older one -- smaller for best_key, larger for best_rc --
 //        so a stale read can only let through an atomic that changes nothing.  The final value is the max / min over all offers,
 //        whatever the order.
 //   (F3) The picks of a round are acyclic: were they a cycle of components, each edge of it would have to rank strictly before the
@@ -57,9 +57,6 @@
 namespace mg {
 
 constexpr int CF_NT = 256;
-constexpr unsigned long long CF_NONE = ~0ull;
-
-__device__ __forceinline__ unsigned long long cf_load(unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // cg_append_kernel with the counts: a wave loads 64 ballot words, counts their bits, takes room for all of them with ONE atomicAdd on
 // the cursor, then writes the words that are not zero one after the other, a lane per bit.  An entry whose place is at or behind `cap`
@@ -145,44 +142,6 @@ __device__ __forceinline__ CfEdge cf_edge(const uint4 *edges, unsigned long long
         }
     }
     return r;
-}
-
-// atomicMax(&best[c], v) for the lanes with `on`, skipping what cannot win (F2); one atomic for the wave where they all name one
-// component.  Called by whole waves.
-__device__ __forceinline__ void cf_offer_max(unsigned long long *best, bool on, uint32_t c, unsigned long long v)
-{
-    const unsigned long long act = __ballot(on);
-    if (!act) return;                                          // (wave-uniform)
-    const uint32_t first = (uint32_t)__builtin_ctzll(act);
-    const uint32_t c0 = __shfl(c, first);
-    if (__ballot(on && c != c0) == 0) {
-        unsigned long long k = on ? v : 0ull;
-        for (uint32_t d = 32; d; d >>= 1) {
-            const unsigned long long o = __shfl_xor(k, d);
-            if (o > k) k = o;
-        }
-        if ((threadIdx.x & 63) == first && k > cf_load(best + c0)) atomicMax(best + c0, k);
-    } else if (on && v > cf_load(best + c)) {
-        atomicMax(best + c, v);
-    }
-}
-
-__device__ __forceinline__ void cf_offer_min(unsigned long long *best, bool on, uint32_t c, unsigned long long v)
-{
-    const unsigned long long act = __ballot(on);
-    if (!act) return;                                          // (wave-uniform)
-    const uint32_t first = (uint32_t)__builtin_ctzll(act);
-    const uint32_t c0 = __shfl(c, first);
-    if (__ballot(on && c != c0) == 0) {
-        unsigned long long k = on ? v : CF_NONE;
-        for (uint32_t d = 32; d; d >>= 1) {
-            const unsigned long long o = __shfl_xor(k, d);
-            if (o < k) k = o;
-        }
-        if ((threadIdx.x & 63) == first && k < cf_load(best + c0)) atomicMin(best + c0, k);
-    } else if (on && v < cf_load(best + c)) {
-        atomicMin(best + c, v);
-    }
 }
 
 // `go`: the edges the round before chose (nullptr: the first round); a round queued behind the fixpoint does nothing

@@ -1,7 +1,7 @@
 // cluster_internal.h — launch interface between host_cluster.cpp and cluster.hip (single-linkage clusters of a thresholded triangle),
 // cluster_medoid.hip (the same clusters with their medoids), cluster_greedy.hip (greedy representative clusters of the same graph) and
-// cluster_forest.hip (its minimum spanning forest), and the lock-free union-find that cluster.hip, cluster_medoid.hip and
-// cluster_forest.hip share.
+// cluster_forest.hip (its minimum spanning forest) and cluster_complete.hip (its complete-linkage clusters), and the lock-free
+// union-find that cluster.hip, cluster_medoid.hip and cluster_forest.hip share.
 #pragma once
 #include "finish_internal.h"          // (under MG_HIP_EMU that header brings tools/hipemu: tests/test_cluster_emu.py)
 #include <stdint.h>
@@ -101,6 +101,49 @@ hipError_t launch_greedy_rounds(const uint4 *edges, uint64_t m, uint32_t *state,
 hipError_t launch_nearest_assign(const uint4 *edges, uint64_t m, const uint32_t *state, uint32_t n, unsigned long long *best_key, uint32_t *rep,
                                  unsigned long long *n_reps, hipStream_t stream);
 
+// ---- what cluster_forest.hip and cluster_complete.hip share: a per-row best under a monotone 64-bit atomic
+constexpr unsigned long long CF_NONE = ~0ull;
+
+__device__ __forceinline__ unsigned long long cf_load(unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// atomicMax(&best[c], v) for the lanes with `on`, skipping what cannot win (F2 of cluster_forest.hip); one atomic for the wave where they all name one
+// component.  Called by whole waves.
+__device__ __forceinline__ void cf_offer_max(unsigned long long *best, bool on, uint32_t c, unsigned long long v)
+{
+    const unsigned long long act = __ballot(on);
+    if (!act) return;                                          // (wave-uniform)
+    const uint32_t first = (uint32_t)__builtin_ctzll(act);
+    const uint32_t c0 = __shfl(c, first);
+    if (__ballot(on && c != c0) == 0) {
+        unsigned long long k = on ? v : 0ull;
+        for (uint32_t d = 32; d; d >>= 1) {
+            const unsigned long long o = __shfl_xor(k, d);
+            if (o > k) k = o;
+        }
+        if ((threadIdx.x & 63) == first && k > cf_load(best + c0)) atomicMax(best + c0, k);
+    } else if (on && v > cf_load(best + c)) {
+        atomicMax(best + c, v);
+    }
+}
+
+__device__ __forceinline__ void cf_offer_min(unsigned long long *best, bool on, uint32_t c, unsigned long long v)
+{
+    const unsigned long long act = __ballot(on);
+    if (!act) return;                                          // (wave-uniform)
+    const uint32_t first = (uint32_t)__builtin_ctzll(act);
+    const uint32_t c0 = __shfl(c, first);
+    if (__ballot(on && c != c0) == 0) {
+        unsigned long long k = on ? v : CF_NONE;
+        for (uint32_t d = 32; d; d >>= 1) {
+            const unsigned long long o = __shfl_xor(k, d);
+            if (o < k) k = o;
+        }
+        if ((threadIdx.x & 63) == first && k < cf_load(best + c0)) atomicMin(best + c0, k);
+    } else if (on && v < cf_load(best + c)) {
+        atomicMin(best + c, v);
+    }
+}
+
 // ---- cluster_forest.hip
 // launch_greedy_append with the pair's counts beside it: {x = larger, y = smaller index, z = numer, w = denom} of a.counts, 16 bytes an
 // edge.  Cursor, `cap` and *overflow as there.
@@ -124,5 +167,27 @@ hipError_t launch_forest_rounds(const uint4 *edges, uint64_t m, const ForestBufs
                                 uint32_t *seen, uint32_t s, hipStream_t stream);
 // out[i] = the finished record of forest[i], i < count: f's distance table and lengths, the device functions of finish.hip
 hipError_t launch_forest_finish(const FinishArgs &f, const uint4 *forest, uint64_t count, FinishEdge *out, hipStream_t stream);
+
+// ---- cluster_complete.hip
+// What the complete-linkage rounds work on.  The LINKS are the appended list itself ({hi, lo, numer, denom}; an entry with hi == lo
+// is skipped by every reader); everything here is written by launch_complete_begin and the rounds.
+struct CompleteBufs {
+    uint32_t *parent, *mate;                   // [n] "larger id under smaller" of every merge so far; this round's partner of an id (~0: none)
+    unsigned long long *best_key, *best_rc;    // [n] per id of this round: the best weight key of its links, the smallest {hi, lo} that has it
+    unsigned long long *key, *next;            // [m] a link's weight key (forest_key.h) or CC_DEAD; what K4 decided it becomes
+    unsigned long long *slot_rc, *slot_e;      // [slots] the lookup: forest_rc(hi, lo) of a link (CF_NONE: empty) and its place in the list
+    uint64_t slots;                            // complete_slots(m): the load is below one half
+    uint64_t hash_and, hash_or;                // ~0 and 0; a test narrows the hash with them so that probes collide and wrap
+    uint32_t *merged;                          // [rounds of a batch] links merged by round r
+    unsigned long long *live;                  // [rounds of a batch] links alive when round r began
+};
+constexpr unsigned long long CC_DEAD = ~0ull;  // (a key is at most 2^42)
+uint64_t complete_slots(uint64_t m);           // 2 m + 1
+// Behind the last append: parent[i] = i, the rows' round state cleared, key[e] = forest_key(numer, denom) (CC_DEAD for an entry with
+// hi == lo), and the lookup built -- every slot emptied, then every link's {hi, lo} put in by a 64-bit compare-and-swap on slot_rc.
+hipError_t launch_complete_begin(const uint4 *edges, uint64_t m, const CompleteBufs &b, uint32_t n, hipStream_t stream);
+// `rounds` rounds as one batch (the launcher zeroes merged / live [0 .. rounds)): round r of the batch does nothing once round r - 1
+// of it merged nothing.  The fixpoint is the first merged[r] == 0; at most n rounds are ever needed.
+hipError_t launch_complete_rounds(const uint4 *edges, uint64_t m, const CompleteBufs &b, uint32_t n, uint32_t rounds, hipStream_t stream);
 
 }  // namespace mg

@@ -1,6 +1,7 @@
 // host_cluster.cpp -- the cluster entry points: the marked pairs of a thresholded triangle (cut_counts) united on the device
-// (cluster.hip, cluster_medoid.hip), or gathered as an edge list for the greedy rounds (cluster_greedy.hip) and the minimum spanning
-// forest (cluster_forest.hip); an earlier clustering extended by new rows either way
+// (cluster.hip, cluster_medoid.hip), or gathered as an edge list for the greedy rounds (cluster_greedy.hip), the minimum spanning
+// forest (cluster_forest.hip) and the complete-linkage rounds (cluster_complete.hip); an earlier clustering extended by new rows in
+// the first two forms
 #include "cut_internal.h"
 #include <deque>
 
@@ -526,6 +527,118 @@ int mg_cluster_forest_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *chosen_o
     for (uint64_t r = 0; r < capacity && r < ctx->forest_live.size(); r++) {
         live_out[r] = ctx->forest_live[r];
         chosen_out[r] = ctx->forest_chosen[r];
+    }
+    return MG_OK;
+}
+
+
+/* ------------------------------------------------- complete linkage (cluster_complete.hip) */
+
+// The whole triangle of t: the edge list with the pairs' counts (gather_edges: it is the forest's list, MASHGPU_FOREST_EDGE_CAP its
+// first capacity), the keys and the lookup built once behind the last append, then the rounds in batches as greedy_fixpoint queues
+// them -- 8 (MASHGPU_COMPLETE_BATCH: the first batch's size, a test knob), then doubling, one wait per batch for merged[] -- and the
+// labels.  At most n rounds are ever needed: each but the last merges a link at least.
+static int cluster_complete_tri(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t *label_out, bool on_device, uint64_t *n_clusters_out,
+                                uint64_t *n_edges_out)
+{
+    *n_clusters_out = *n_edges_out = 0;
+    ctx->complete_rounds = ctx->complete_batches = ctx->complete_regrows = ctx->complete_edge_cap = 0;
+    ctx->complete_live.clear();
+    ctx->complete_merged.clear();
+    ClusterJobs J;
+    int rc = cluster_jobs(ctx, nullptr, t, cut, false, &J, mg::FOREST_DENOM_LIMIT, "cluster complete");
+    if (rc != MG_OK || !J.total) return rc;
+    const uint32_t n = J.total;
+    ForestEdges E(ctx);
+    if ((rc = gather_edges(ctx, J, cut, "MASHGPU_FOREST_EDGE_CAP", E)) != MG_OK) return rc;
+    const uint64_t m = E.used, slots = mg::complete_slots(m);
+    constexpr uint32_t kBatchMax = 256;
+    uint32_t batch = 8;
+    if (const char *o = ctx_opt(ctx, "MASHGPU_COMPLETE_BATCH")) batch = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, strtoull(o, nullptr, 10)), kBatchMax);
+    DevBuf<uint32_t> parent(ctx), mate(ctx), merged(ctx), label(ctx);
+    DevBuf<unsigned long long> best_key(ctx), best_rc(ctx), key(ctx), next(ctx), slot_rc(ctx), slot_e(ctx), live(ctx), d_roots(ctx);
+    if (parent.alloc(n) != hipSuccess || mate.alloc(n) != hipSuccess || merged.alloc(kBatchMax) != hipSuccess || best_key.alloc(n) != hipSuccess ||
+        best_rc.alloc(n) != hipSuccess || live.alloc(kBatchMax) != hipSuccess || d_roots.alloc(1) != hipSuccess ||
+        (!on_device && label.alloc(n) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+    }
+    if (m && (key.alloc(m) != hipSuccess || next.alloc(m) != hipSuccess || slot_rc.alloc(slots) != hipSuccess || slot_e.alloc(slots) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(ctx, MG_ERR_NOMEM, "cluster complete: no device memory for the links' keys and their index (" + std::to_string(16 * m + 16 * slots) +
+                                           " bytes for " + std::to_string(m) + " edges)");
+    }
+    const mg::CompleteBufs cb{parent, mate, best_key, best_rc, key, next, slot_rc, slot_e, slots, ~0ull, 0ull, merged, live};
+    uint32_t *d_label = on_device ? label_out : label.p;
+    HIP_TRY(ctx, mg::launch_complete_begin(E.buf, m, cb, n, ctx->stream));
+    std::vector<uint32_t> h_merged(kBatchMax);
+    std::vector<unsigned long long> h_live(kBatchMax);
+    uint64_t rounds = 0, batches = 0;
+    for (; m; batch = std::min(batch * 2, kBatchMax)) {
+        HIP_TRY(ctx, mg::launch_complete_rounds(E.buf, m, cb, n, batch, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_merged.data(), merged, (size_t)batch * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_live.data(), live, (size_t)batch * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        batches++;
+        uint32_t r = 0;
+        while (r < batch && h_merged[r]) r++;
+        const uint32_t ran = std::min(r + 1, batch);
+        ctx->complete_live.insert(ctx->complete_live.end(), h_live.begin(), h_live.begin() + ran);
+        ctx->complete_merged.insert(ctx->complete_merged.end(), h_merged.begin(), h_merged.begin() + ran);
+        rounds += ran;
+        if (r < batch) break;
+        if (rounds > n) return fail(ctx, MG_ERR_HIP, "cluster complete: the rounds did not reach their fixpoint");      // (at most n are ever needed)
+    }
+    unsigned long long roots = 0;
+    HIP_TRY(ctx, mg::launch_cluster_label(parent, n, d_label, d_roots, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&roots, d_roots, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!on_device) HIP_TRY(ctx, hipMemcpyAsync(label_out, d_label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *n_clusters_out = roots;
+    *n_edges_out = E.n_edges;
+    ctx->complete_rounds = rounds;
+    ctx->complete_batches = batches;
+    ctx->complete_regrows = E.regrows;
+    ctx->complete_edge_cap = E.cap;
+    return MG_OK;
+}
+
+int mg_cluster_tri_complete_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                                 uint32_t *label_out_host, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    return cluster_call(ctx, "mg_cluster_tri_complete_host", nullptr, t, cut, n_clusters_out && n_edges_out && (label_out_host || !rows_of(t)), nullptr,
+                        nullptr, [&] { return cluster_complete_tri(ctx, t, cut, label_out_host, false, n_clusters_out, n_edges_out); });
+}
+
+int mg_cluster_tri_complete_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                                uint32_t *label_out_dev, uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    return cluster_call(ctx, "mg_cluster_tri_complete_dev", nullptr, t, cut, n_clusters_out && n_edges_out && (label_out_dev || !rows_of(t)), nullptr,
+                        nullptr, [&] { return cluster_complete_tri(ctx, t, cut, label_out_dev, true, n_clusters_out, n_edges_out); });
+}
+
+int mg_cluster_complete_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out, uint64_t *edge_capacity_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (rounds_out) *rounds_out = ctx->complete_rounds;
+    if (batches_out) *batches_out = ctx->complete_batches;
+    if (regrows_out) *regrows_out = ctx->complete_regrows;
+    if (edge_capacity_out) *edge_capacity_out = ctx->complete_edge_cap;
+    return MG_OK;
+}
+
+int mg_cluster_complete_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *merged_out, uint64_t capacity, uint64_t *rounds_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (!rounds_out || ((!live_out || !merged_out) && capacity)) return fail(ctx, MG_ERR_INVALID, "mg_cluster_complete_rounds: NULL argument");
+    *rounds_out = ctx->complete_live.size();
+    for (uint64_t r = 0; r < capacity && r < ctx->complete_live.size(); r++) {
+        live_out[r] = ctx->complete_live[r];
+        merged_out[r] = ctx->complete_merged[r];
     }
     return MG_OK;
 }

@@ -114,6 +114,9 @@ struct mg_ctx {
     // mg_cluster_forest_stats: the same for the last mg_cluster_tri_forest_host call
     uint64_t forest_rounds = 0, forest_regrows = 0, forest_edge_cap = 0;
     std::vector<uint64_t> forest_live, forest_chosen;       // mg_cluster_forest_rounds: per round, the live edges it began with and the edges it chose
+    // mg_cluster_complete_stats / mg_cluster_complete_rounds: the same for the last mg_cluster_tri_complete_* call
+    uint64_t complete_rounds = 0, complete_batches = 0, complete_regrows = 0, complete_edge_cap = 0;
+    std::vector<uint64_t> complete_live, complete_merged;   // per round, the links alive when it began and the links it merged
     // the compare dispatch's prices, corrected from this context's own launches; the event pairs that time a phase
     SparseCosts costs;
     struct CostClock { hipEvent_t a = nullptr, b = nullptr; };

@@ -29,6 +29,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -1896,16 +1897,18 @@ int cmd_triangle(int argc, const char **argv)
 // the first three fields are those of the run without -M.
 // -T: the minimum spanning forest of the same pairs instead (mg_cluster_tri_forest_host): one `triangle -E` line per forest edge,
 // best first, not cluster lines.
+// -L: complete-linkage clusters of the same pairs instead (mg_cluster_tri_complete_host): every two members of a cluster are an
+// edge; links merge best first by the exact fraction of their worst pair.  Lines and numbering are those of the plain run.
 // -A <earlier output>: the clusters of the first L inputs are read from an earlier run's stdout and only the pairs that touch a
 // later input are compared (cluster_extend below; include/mashgpu.h: mg_cluster_extend_host).  With plain and with -R only.
 // MASH_AMD_HOST_FINISH=1 is the host route, which the tests judge the device route by: the pairs within -d come from the host calls
 // of `triangle -E -d` and `dist -d` (tri_edge_blocks, rect_edge_blocks), and what follows is done here, once for every form
-// (cluster_on_host: Sets, greedy_walk, nearest_pick, medoid_pick; -T: Kruskal over the same Sets).
+// (cluster_on_host: Sets, greedy_walk, nearest_pick, medoid_pick; -T: Kruskal over the same Sets; -L: complete_walk).
 
-enum ClusterMode { kSingle, kGreedy, kNearest, kMedoid, kForest };      // plain, -R, -B (with or without -R), -M, -T; -A is a flag beside it
+enum ClusterMode { kSingle, kGreedy, kNearest, kMedoid, kForest, kComplete };      // plain, -R, -B (with or without -R), -M, -T, -L; -A is a flag beside it
 
 // The lap of a form's clustering (MASH_AMD_TIMING=1) on the device and on the host route: kClusterLaps[mode][with -A]
-const struct { const char *device, *host; } kClusterLaps[5][2] = {
+const struct { const char *device, *host; } kClusterLaps[6][2] = {
     {{"compare+mark+union+label+copy", "compare+filter+copy+union"},
      {"seed+compare+mark+union (new x old, new x new)+label+copy", "compare+filter+copy (new x old, new x new)+union"}},
     {{"compare+mark+append+rounds+assign+copy", "compare+filter+copy+walk"},
@@ -1913,6 +1916,7 @@ const struct { const char *device, *host; } kClusterLaps[5][2] = {
     {{"compare+mark+append+rounds+nearest+copy", "compare+filter+copy+walk+nearest"}},
     {{"compare+mark+union+score+label+pick+copy", "compare+filter+copy+union+score+pick"}},
     {{"compare+mark+append+rounds+sort+finish+copy", "compare+filter+copy+sort+kruskal"}},
+    {{"compare+mark+append+index+rounds+label+copy", "compare+filter+copy+walk"}},
 };
 
 // Union-find in place over a vector of labels: a set's root is its smallest member, so the first input of a cluster names it
@@ -1961,6 +1965,54 @@ void medoid_pick(const vector<uint32_t> &lab, const vector<uint64_t> &score, vec
     for (uint64_t i = 0; i < n; i++) med[i] = top[lab[i]];
 }
 
+// -L: the sequential walk of the definition (include/mashgpu.h: mg_cluster_tri_complete_host).  links[a][b], for cluster ids a and b
+// either way round, holds the counts of the worst edge between the two clusters, present iff every pair between them is an edge;
+// `order` holds every link once, best first (mg::forest_before over {larger id, smaller id}).  The first link is merged: the
+// survivor's links are those BOTH clusters had, each with the worse of the two weights.
+void complete_walk(vector<uint32_t> &lab, const vector<mg_edge> &edges)
+{
+    struct Weight { uint32_t numer, denom; };
+    struct Link { uint32_t numer, denom; uint64_t rc; };
+    auto before = [](const Link &a, const Link &b) { return mg::forest_before(a.numer, a.denom, a.rc, b.numer, b.denom, b.rc); };
+    auto link_of = [](uint32_t a, uint32_t b, const Weight &w) { return Link{w.numer, w.denom, mg::forest_rc(std::max(a, b), std::min(a, b))}; };
+    vector<std::map<uint32_t, Weight>> links(lab.size());
+    std::set<Link, decltype(before)> order(before);
+    for (const mg_edge &e : edges) {
+        const Weight w{e.numer, e.denom};
+        links[e.row][e.col] = links[e.col][e.row] = w;
+        order.insert(link_of(e.row, e.col, w));
+    }
+    vector<uint32_t> up(lab.size());
+    for (size_t i = 0; i < up.size(); i++) up[i] = (uint32_t)i;
+    while (!order.empty()) {
+        const Link first = *order.begin();
+        const uint32_t gone = (uint32_t)(first.rc >> 32), stay = (uint32_t)first.rc;
+        std::map<uint32_t, Weight> merged;
+        for (const auto &[other, w] : links[gone]) {
+            order.erase(link_of(gone, other, w));
+            links[other].erase(gone);
+            const auto at = links[stay].find(other);
+            if (other == stay || at == links[stay].end()) continue;
+            // the worse of the two: the smaller fraction (equal fractions: either, the key of the order is the same)
+            merged[other] = mg::forest_before(w.numer, w.denom, 0, at->second.numer, at->second.denom, 0) ? at->second : w;
+        }
+        for (const auto &[other, w] : links[stay]) {
+            if (other == gone) continue;
+            order.erase(link_of(stay, other, w));
+            links[other].erase(stay);
+        }
+        for (const auto &[other, w] : merged) {
+            links[other][stay] = w;
+            order.insert(link_of(stay, other, w));
+        }
+        links[gone].clear();
+        links[stay] = std::move(merged);
+        up[gone] = stay;
+    }
+    Sets sets{up};
+    for (size_t i = 0; i < lab.size(); i++) lab[i] = sets.find((uint32_t)i);
+}
+
 // What a run finds: per input its label, the first member of its cluster (-R, -B: its representative), and with -M its cluster's
 // medoid; or with -T the forest's records, best first
 struct Clusters { vector<uint32_t> lab, med; vector<mg_result> forest; };
@@ -1977,12 +2029,14 @@ int cluster_on_host(ClusterMode mode, uint64_t first, Clusters &c, Source passin
     for (uint64_t i = first; i < n; i++) lab[i] = (uint32_t)i;
     Sets sets{lab};
     vector<vector<uint32_t>> smaller(greedy ? n - first : 0);
-    vector<mg_edge> kept;                                      // -B: every edge with its counts
+    vector<mg_edge> kept;                                      // -B, -L: every edge with its counts
     vector<uint64_t> score(mode == kMedoid ? n : 0);           // -M: per input the sum of its edges' weights
     vector<mg_result> all;                                     // -T: every edge as the record of its line
     if (passing_edges([&](const mg_edge &e, const mg_pair &pr) {
             if (mode == kForest) {
                 all.push_back(mg_result{e.row, e.col, pr.numer, pr.denom, pr.distance, pr.p_value});
+            } else if (mode == kComplete) {
+                kept.push_back(e);
             } else if (greedy) {
                 smaller[std::max(e.row, e.col) - first].push_back(std::min(e.row, e.col));
                 if (mode == kNearest) kept.push_back(e);
@@ -2001,6 +2055,8 @@ int cluster_on_host(ClusterMode mode, uint64_t first, Clusters &c, Source passin
             return mg::forest_before(a.numer, a.denom, mg::forest_rc(a.row, a.col), b.numer, b.denom, mg::forest_rc(b.row, b.col)); });
         for (const mg_result &e : all)
             if (sets.unite(e.row, e.col)) c.forest.push_back(e);
+    } else if (mode == kComplete) {
+        complete_walk(lab, kept);
     } else if (greedy) {
         greedy_walk(lab, first, smaller);
         if (mode == kNearest) nearest_pick(lab, kept);
@@ -2037,6 +2093,7 @@ int cluster_table(TriRun &r, ClusterMode mode, Clusters &c)
         c.forest.resize(r.n - 1);
         rc = mg_cluster_tri_forest_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.forest.data(), c.forest.size(), &count, nullptr, &n_clusters, &n_edges);
         break;
+    case kComplete: rc = mg_cluster_tri_complete_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.lab.data(), &n_clusters, &n_edges); break;
     }
     if (rc != MG_OK) return report_error(r.gpu);
     c.forest.resize(count);
@@ -2158,6 +2215,7 @@ int cmd_cluster(int argc, const char **argv)
     c.add("tree", Opt::Boolean, "T");
     c.add("assign", Opt::File, "A");
     c.add("medoid", Opt::Boolean, "M");
+    c.add("complete", Opt::Boolean, "L");
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "0.05", 0., 1.);
     c.use_sketch_options();
@@ -2197,7 +2255,15 @@ int cmd_cluster(int argc, const char **argv)
                 "            pair of the cluster that is no edge counts 0), and the medoid is the member with the largest\n"
                 "            score, equal scores to the earlier member: with full sketches, the member with the largest mean\n"
                 "            Jaccard estimate to the rest of its cluster.  Exact integers throughout.  Not with -R, -B, -T\n"
-                "            or -A (the weights between earlier inputs are not among the pairs -A compares).\n\n";
+                "            or -A (the weights between earlier inputs are not among the pairs -A compares).\n"
+                "  -L        Complete-linkage clusters instead of single linkage: every two members of a cluster share an\n"
+                "            edge.  Two clusters are linked if every pair between them is an edge, and the link weighs what\n"
+                "            its worst pair does: the smallest shared-hashes as an exact fraction.  Starting from single\n"
+                "            sketches, the best link is merged, equal fractions going to the link whose later cluster comes\n"
+                "            first in the input, then to the one whose earlier cluster does, until no link is left.  The\n"
+                "            result depends on the edges and their shared-hashes alone.  Output fields and numbering are\n"
+                "            those of the plain run.  Not with -R, -B, -M or -T.  Not with -A: merges among the earlier\n"
+                "            inputs are not a function of the pairs -A compares.\n\n";
         return 0;
     }
     const bool comment = c.o("comment").active, extend = c.o("assign").active;
@@ -2208,6 +2274,7 @@ int cmd_cluster(int argc, const char **argv)
         {"medoid", "assign", " (the weights between earlier inputs are not among the pairs -A compares)"},
         {"best", "tree", ""}, {"best", "assign", " (a new representative can be nearer to an earlier member)"},
         {"tree", "representatives", ""}, {"tree", "assign", ""},
+        {"complete", "representatives", ""}, {"complete", "best", ""}, {"complete", "medoid", ""}, {"complete", "tree", ""}, {"complete", "assign", ""},
     };
     for (const auto &x : refusals) {
         if (!c.o(x.a).active || !c.o(x.b).active) continue;
@@ -2221,7 +2288,7 @@ int cmd_cluster(int argc, const char **argv)
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // as `mash triangle` (CommandTriangle.cpp:74-77)
-    const ClusterMode mode = c.o("tree").active ? kForest : c.o("medoid").active ? kMedoid : c.o("best").active ? kNearest
+    const ClusterMode mode = c.o("complete").active ? kComplete : c.o("tree").active ? kForest : c.o("medoid").active ? kMedoid : c.o("best").active ? kNearest
                              : c.o("representatives").active ? kGreedy : kSingle;
     Earlier old;
     if (extend && !read_earlier(c.o("assign").arg, old)) return 1;           // (before a device is opened)
@@ -2817,7 +2884,7 @@ int main(int argc, const char **argv)
         "  dist      Estimate the distance of query sequences to references.\n"
         "  within    Estimate the containment of query sequences within references.\n"
         "  triangle  Estimate a lower-triangular distance matrix.\n"
-        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), name each single-linkage cluster's medoid (-M), extend an earlier clustering by new sequences (-A), or print the minimum spanning forest (-T).\n  info      Display information about sketch files.\n"
+        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), name each single-linkage cluster's medoid (-M), extend an earlier clustering by new sequences (-A), print the minimum spanning forest (-T), or form complete-linkage clusters, every two members within the distance (-L).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"

@@ -342,6 +342,11 @@ static inline uint32_t atomicCAS(uint32_t *p, uint32_t expected, uint32_t v)
     __atomic_compare_exchange_n(p, &expected, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
     return expected;                                        // (the value found, as on the device)
 }
+static inline unsigned long long atomicCAS(unsigned long long *p, unsigned long long expected, unsigned long long v)
+{
+    __atomic_compare_exchange_n(p, &expected, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return expected;
+}
 // scoped atomic loads and stores: every scope is the process here
 #ifndef __HIP_MEMORY_SCOPE_AGENT
 #define __HIP_MEMORY_SCOPE_AGENT 4
