@@ -625,17 +625,20 @@ int SparseJobRun::open_index()
 }
 
 // The constant of a matrix job -- {0, s} for every pair that shares no hash -- depends on nothing the index says: while the
-// index is built it is written on a stream of its own, 64 KB chunks taken from a counter by a few workgroups -- a quarter of
-// the CUs have one: a fill at full speed keeps the memory's queues full of writes and the build's loads, kernels that live
+// index is built it is written on a stream of its own, 64 KB chunks taken from a counter by a few workgroups -- five in
+// sixteen CUs have one: a fill at full speed keeps the memory's queues full of writes and the build's loads, kernels that live
 // on round trips, wait behind them (round 5 measured exactly that with 2 - 16 workgroups per CU and dropped it; 64
 // workgroups write ~4 TB/s and the build takes 10 ms instead of 8, with the fill's 6.7 ms gone).  What is left when the build
 // has ended is taken from the same counter at full speed on the context's stream (end_prefill), so a pace that is too slow
 // costs little.  C3 per table: 15.4 -> 11.8 ms (tools/aside_sweep.sh).  (Swept again since the build reads the table in place:
-// no naps gained 0.06 - 0.14 ms per table, which is the spread of the runs -- the pace stays)
+// no naps gained 0.06 - 0.14 ms per table, which is the spread of the runs -- the pace stays, DESIGN.md 4.1.  And again since K3
+// takes its ranks in registers and keeps three workgroups per CU: the build alone became 0.5 ms shorter and the step beside 64
+// workgroups did not -- what the build ends earlier, the fill has left over; 80 workgroups with one nap: 10.59 - 10.88 ms per
+// table against 11.00 - 11.09)
 // MASHGPU_FILL_ASIDE = "<workgroups>[,<naps of 64 cycles per 4 KB>[,<work-items>]]"; 0: off.
 int SparseJobRun::prefill()
 {
-    uint32_t wgs = std::max(16u, (uint32_t)ctx->cu_count / 4u), naps = 1, threads = 256;
+    uint32_t wgs = std::max(16u, (uint32_t)ctx->cu_count * 5u / 16u), naps = 1, threads = 256;
     if (const char *e = ctx_opt(ctx, "MASHGPU_FILL_ASIDE")) {
         if (atoi(e) == 0) return MG_OK;
         if (sscanf(e, "%u,%u,%u", &wgs, &naps, &threads) < 1 || wgs == 0 || (threads != 64 && threads != 128 && threads != 256)) return MG_OK;

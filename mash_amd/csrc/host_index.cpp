@@ -235,13 +235,21 @@ struct SparseIndexBuild {
         explicit TileScratch(mg_ctx *c) : start(c), big(c), pk(c), tc(c) {}
     };
 
+    // K3's body: the ranks taken in registers unless MASHGPU_IX_PARTITION=lsd asks for the tile's LSD sort in LDS (=rank: the
+    // default itself; for A/B runs and tests -- both leave the same words)
+    int partition_body()
+    {
+        const char *o = ctx_opt(ctx, "MASHGPU_IX_PARTITION");
+        return o && strcmp(o, "lsd") == 0 ? mg::IX_PART_LSD : mg::IX_PART_RANK;
+    }
+
     // the ONE call of index_build.hip: its stages by bit mask (index_build.h), the leaders' lists once the candidates are laid out
     hipError_t tiles(const TileScratch &w, int stages)
     {
         const mg::IxLeaders lv = lead.view(d_lead_rows);
         return mg::index_build_mapped(plan, H, rowmap, sp->off, d_lb, d_tcnt, w.start, w.big, w.pk, w.tc, sp->keys_sorted, sp->sorted_rows, sp->gend, gs_of, sp->code_img,
                                sp->pos_img, d_slots, &d_stat.p->shared, &d_stat.p->max_group, &d_stat.p->groups, d_stat.p->ixf, lead_ready ? &lv : nullptr,
-                               ctx->stream, stages, sp->row_any);
+                               ctx->stream, stages, sp->row_any, partition_body());
     }
     // The bucket sorts: values, rows, groups, statistics, leaders are final behind them.  The leaders' lists are made one; their
     // totals come back with the statistics -- the host's after the caller's wait.
@@ -753,6 +761,8 @@ hipError_t SparseIndexBuild::tile_passes()
                 h_stat.ixf[mg::IXF_DEGENERATE] ? " -- clumped values: sorted instead" : "");
     if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
         fprintf(stderr, "compare sparse: block counts %s\n", cnt_made ? "made with the window offsets (one read of the table)" : "by the tiles (K1)");
+    if (ctx_opt(ctx, "MASHGPU_SPARSE_DBG"))
+        fprintf(stderr, "compare sparse: tile partition %s\n", partition_body() == mg::IX_PART_LSD ? "by the LSD sort in LDS (lsd)" : "by ranks in registers (rank)");
     return e;
 }
 

@@ -12,10 +12,16 @@
 //   K1 + K2   entries per (block of 512 rows, bucket) -> where every bucket and every block's share of it starts;
 //   K0 + K1   in ONE pass over the table where 16-bit counters of all buckets fit a workgroup's LDS (index_offsets_counts: a
 //             workgroup per block of rows streams the rows as K0 does and counts every entry in LDS);
-//   K3        a tile = (block of rows, window): the rows' segments are read, sorted by bucket in LDS (stable: by row, then
+//   K3        a tile = (block of rows, window): the rows' segments are read, put in order by bucket (stable: by row, then
 //             position) and written as ONE contiguous piece per bucket -- a single pass replaces the radix passes, because a
 //             tile's entries fall into a few hundred buckets only.  An entry travels as one 64-bit word: its value's bits
-//             below the bucket | its row;
+//             below the bucket | its row.  The order is not sorted for: every row's segment ascends, so the tile read row by
+//             row is a sequence whose stable order by bucket is a RANK -- the entries of the bucket in front of it.  A wave
+//             takes a contiguous share of the sequence, 64 consecutive entries per step; an entry's rank is its bucket's
+//             start + the bucket's entries of the waves below + of the wave's earlier steps (a counter row per wave) + of the
+//             lanes below in the same step (ballots over the bucket's bits).  The word goes to LDS at its rank, to leave in
+//             whole pieces; the slot goes to the position image straight from registers (IX_PART_RANK; IX_PART_LSD is the
+//             body before it: LSD passes of 4 bits over the tile in LDS, kept for A/B runs and tests);
 //   K4        a workgroup per bucket sorts its entries by (value, row) in LDS (counting sort on the next 13 bits, then
 //             rank among the few entries that agree in them), finds the groups of equal values there -- no head flags, no
 //             scan, no tie repair over the whole index -- and writes values, rows, group ends and, in the order the
@@ -85,14 +91,16 @@ hipError_t index_build(const IxPlan &plan, const uint64_t *hashes, const uint32_
                        uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of, uint32_t *code_img, uint32_t *pos_img,
                        void *stat_scratch, unsigned long long *incidences, uint32_t *max_group, uint32_t *groups, uint32_t *flags,
                        const IxLeaders *leaders, hipStream_t stream, int stages = 7, uint32_t *row_any = nullptr);
+// K3's body (MASHGPU_IX_PARTITION=rank|lsd, host_index.cpp): the ranks taken in registers, or the LSD sort of the tile in LDS
+enum { IX_PART_RANK = 0, IX_PART_LSD = 1 };
 // The same with the table read IN PLACE through a row map: index row a is read at hashes + rowmap[a] * stride (nullptr: identity,
 // what index_build passes).  K0, K1 and K3 are the kernels that read the table; the packed word, the images and everything
-// behind K3 speak of INDEX rows and do not know of the map.
+// behind K3 speak of INDEX rows and do not know of the map.  partition: K3's body, both leave the same words.
 hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *off, void *lb, void *cnt, void *start,
                               void *big, void *pk, void *tc, uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of,
                               uint32_t *code_img, uint32_t *pos_img, void *stat_scratch, unsigned long long *incidences, uint32_t *max_group,
                               uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages = 7,
-                              uint32_t *row_any = nullptr);
+                              uint32_t *row_any = nullptr, int partition = IX_PART_RANK);
 // K0 ahead of the build, through the map: the window offsets of the index's rows into lb, the rows' entry counts taken from
 // cnt_table[rowmap[a]] (the TABLE's order -- the index's offsets need not exist yet).  The build then takes stage bit 8.
 hipError_t index_window_offsets(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *cnt_table, void *lb, hipStream_t stream);

@@ -477,13 +477,14 @@ constexpr uint32_t IXL_PACK = 0, IXL_PA = IXL_PACK + IX_PCAP * 8u, IXL_PB = IXL_
                    IXL_ROWPRE = IXL_CNT + 16u * IX_NT * 2u, IXL_LO = IXL_ROWPRE + (IX_RB + 2u) * 4u, IXL_HIST = IXL_LO + IX_RB * 2u,
                    IXL_GBASE = IXL_HIST + (IX_BW_MAX + 2u) * 4u, IXL_PART = IXL_GBASE + IX_BW_MAX * 4u, IXL_BYTES = IXL_PART + 64u;
 
-// K3: the tile's entries, sorted by bucket, go to pk as one piece per bucket (stable: the block's rows in order, positions
+// K3, the body before the ranks (IX_PART_LSD; kept for A/B runs and tests, it leaves the same words): the tile's entries,
+// sorted by bucket, go to pk as one piece per bucket (stable: the block's rows in order, positions
 // ascending); where each entry went is left in the position image (K5 reads {code, position} back from there).
 // rowmap (nullptr: identity): where the table holds the block's rows.  Every work-item asks for its row's with the row's window
 // offsets and keeps it; the rounds below read the rows' from LDS.  Two workgroups' LDS fill a CU to within 2 KB, so the map of
 // the block has no array of its own: it stands in the sort's counters, which are dead until the piece's entries are loaded,
 // and is put back there behind every piece.  The packed word and the images keep the INDEX row.
-__global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint32_t *__restrict__ rowmap,
+__global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_lsd_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint32_t *__restrict__ rowmap,
                                                                   const uint16_t *__restrict__ lb,
                                                                   const uint32_t *__restrict__ colpre, const uint32_t *__restrict__ start,
                                                                   const uint32_t *__restrict__ flags, uint64_t *__restrict__ pk,
@@ -629,6 +630,176 @@ __global__ __launch_bounds__(IX_NT, 4) void ix_tile_partition_kernel(IxGeom g, c
         }
         s_trow[tid] = trow;                               // (the sort's counters stood here)
         __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K3 by ranks (IX_PART_RANK, the default).  The order wanted -- bucket, then row, then position -- needs no sort: every row's
+// segment ascends, so in the tile read row by row (entry i of the tile is entry i - rowpre[r] of row r's segment) an entry's
+// place is the number of entries of its bucket in front of it, behind the bucket's start.
+//   * Wave w owns the share [64 steps w, 64 steps (w + 1)) of the piece's sequence, steps = ceil(np / 512) <= IX_M; in step k its
+//     lane l holds entry 64 steps w + 64 k + l.  A long row is just more consecutive entries: no side loops.  A lane finds its
+//     row in s_tag, where every row has written its id over its entries' places (its own work-item the first IX_SHORT, the
+//     lanes of its wave together what is beyond).  All of a lane's loads leave before the first is used.
+//   * Rank = the piece's bucket start + the bucket's entries in the waves below + in this wave's earlier steps + in the lanes
+//     below in the same step.  The last comes from ballots over the bucket's bits (the lanes without an entry vote 0 and are
+//     not in the mask they start from); the two before it from a row of BW u16 counters that only its wave touches: in
+//     every step the peers of a bucket read its counter, and behind the ballots the lowest of them adds the peers' number.
+//     The order comes from ownership -- a wave's steps in program order, the lanes' order inside the ballot mask, one owner per
+//     counter row -- and not from the order in which the LDS serves the lanes of an instruction.  Between the peers' read
+//     and the owner's write stand the ballots over the bits (at least one), between the write and the next step's read the
+//     ballot of the lanes with an entry.
+//   * Behind a barrier the work-items tid < BW turn the eight rows into bases (one ix_block_scan_sum over the buckets' totals),
+//     and the lane puts its packed word at s_pack[rank], the bucket at s_tag[rank] (the row table is dead by then) and the
+//     slot, which it knows -- gbase[b] + rank - start[b] = s_delta[b] + rank -- into the position image from registers.
+//   * The piece leaves as before: pk[s_delta[b] + j] = s_pack[j], j consecutive.
+// 51 272 bytes of LDS: three workgroups per CU, six waves per SIMD (80 VGPRs at most: the launch bounds).
+constexpr uint32_t IX_SHORT = 16;               // entries of a row that its own work-item names in the row table
+constexpr uint32_t IX_NWV = IX_NT / 64u;        // waves of the workgroup
+constexpr uint32_t IXR_PACK = 0, IXR_WCNT = IXR_PACK + IX_PCAP * 8u, IXR_TAG = IXR_WCNT + IX_NWV * IX_BW_MAX * 2u, IXR_ROWPRE = IXR_TAG + IX_PCAP * 2u,
+                   IXR_TROW = IXR_ROWPRE + (IX_RB + 2u) * 4u, IXR_DELTA = IXR_TROW + IX_RB * 4u, IXR_LO = IXR_DELTA + IX_BW_MAX * 4u,
+                   IXR_PART = IXR_LO + IX_RB * 2u, IXR_BYTES = IXR_PART + 64u;
+static_assert(3u * IXR_BYTES <= 160u * 1024u, "three workgroups of K3 per CU");
+static_assert(IX_RB == IX_NT && IX_RB <= 512u && IX_BW_MAX <= 512u && IX_PCAP < 4096u, "a row per work-item; row and bucket in 9 bits, a rank in 12");
+
+__global__ __launch_bounds__(IX_NT, 6) void ix_tile_partition_kernel(IxGeom g, const uint64_t *__restrict__ H, const uint32_t *__restrict__ rowmap,
+                                                                  const uint16_t *__restrict__ lb,
+                                                                  const uint32_t *__restrict__ colpre, const uint32_t *__restrict__ start,
+                                                                  const uint32_t *__restrict__ flags, uint64_t *__restrict__ pk,
+                                                                  uint32_t *__restrict__ slot_img)
+{
+    MG_DYN_SHARED(unsigned char, lds);
+    uint64_t *s_pack = reinterpret_cast<uint64_t *>(lds + IXR_PACK);
+    uint16_t *s_wcnt = reinterpret_cast<uint16_t *>(lds + IXR_WCNT);     // [wave][bucket]: counts, then bases
+    uint16_t *s_tag = reinterpret_cast<uint16_t *>(lds + IXR_TAG);       // per entry of the piece its row; later, per rank, the bucket
+    uint32_t *s_rowpre = reinterpret_cast<uint32_t *>(lds + IXR_ROWPRE);
+    uint32_t *s_trow = reinterpret_cast<uint32_t *>(lds + IXR_TROW);
+    uint32_t *s_delta = reinterpret_cast<uint32_t *>(lds + IXR_DELTA);   // per bucket: where it goes in pk - where it starts in the piece
+    uint16_t *s_lo = reinterpret_cast<uint16_t *>(lds + IXR_LO);
+    uint32_t *s_part = reinterpret_cast<uint32_t *>(lds + IXR_PART);
+    uint32_t blk = 0, w = 0;
+    if (!ix_tile_id(g, blk, w)) return;                  // uniform
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    IX_CLK_BEGIN();
+    const uint32_t row0 = blk * IX_RB, nrows = g.n - row0 < IX_RB ? g.n - row0 : IX_RB;
+    uint32_t len = 0, gb = 0, trow = 0;
+    if (tid < g.BW) {                                    // (asked for before the scan waits for the segments' bounds)
+        const uint32_t bg = w * g.BW + tid;
+        gb = start[bg] + colpre[(uint64_t)blk * g.Bp + bg];
+    }
+    if (tid < nrows) {
+        trow = rowmap ? rowmap[row0 + tid] : row0 + tid;
+        const uint16_t *p = lb + (uint64_t)(row0 + tid) * (g.NW + 1u) + w;
+        const uint32_t lo = p[0];
+        len = (uint32_t)p[1] - lo;
+        s_lo[tid] = (uint16_t)lo;
+    }
+    uint32_t total = 0;
+    const uint32_t pre = ix_block_scan_sum(len, s_part, total);
+    if (total == 0) return;                              // uniform
+    s_rowpre[tid] = pre;
+    s_trow[tid] = trow;
+    if (tid == IX_NT - 1u) s_rowpre[IX_NT] = total;
+    __syncthreads();
+    IX_CLK(8);
+    const uint64_t lowmask = (1ull << g.shift) - 1ull;    // (shift <= 63)
+    const uint64_t nowhere = (uint64_t)s_trow[0] * g.stride;      // (uniform: what a lane without an entry reads)
+    const uint64_t lanes_below = (1ull << lane) - 1ull;
+    const uint32_t nbits = g.bw_log ? g.bw_log : 1u;      // (one ballot over the bits even where a window is one bucket: see above)
+    uint16_t *cw = s_wcnt + wv * IX_BW_MAX;
+    for (uint32_t i0 = 0; i0 < total; i0 += IX_PCAP) {
+        const uint32_t np = total - i0 < IX_PCAP ? total - i0 : IX_PCAP;
+        const uint32_t nsteps = (np + IX_NT - 1u) / IX_NT, cbase = wv * 64u * nsteps;
+        {   // the row table of the piece [i0, i0 + np), and the wave's counters
+            const uint32_t a = pre > i0 ? pre : i0, e = pre + len < i0 + np ? pre + len : i0 + np;
+            for (uint32_t x = a; x < e && x < a + IX_SHORT; x++) s_tag[x - i0] = (uint16_t)tid;
+            uint64_t longm = __ballot(e > a + IX_SHORT);
+            while (longm) {                              // (uniform over the wave)
+                const uint32_t r = (tid & ~63u) + (uint32_t)__builtin_ctzll(longm);
+                longm &= longm - 1ull;
+                const uint32_t rp = s_rowpre[r], re = s_rowpre[r + 1u];
+                const uint32_t a2 = rp > i0 ? rp : i0, e2 = re < i0 + np ? re : i0 + np;
+                for (uint32_t x = a2 + IX_SHORT + lane; x < e2; x += 64u) s_tag[x - i0] = (uint16_t)r;
+            }
+            for (uint32_t x = lane; x < (g.BW + 1u) / 2u; x += 64u) reinterpret_cast<uint32_t *>(cw)[x] = 0;
+        }
+        __syncthreads();
+        IX_CLK(9);
+        // the lane's entries: row and position from the table, the values asked for together
+        uint32_t meta[IX_M], lrk[IX_M];                   // row | position << 9 (~0: no entry);  local bucket | rank << 9
+        uint64_t v[IX_M];
+#pragma unroll
+        for (uint32_t k = 0; k < IX_M; k++) {
+            const uint32_t j = cbase + 64u * k + lane;
+            meta[k] = k < nsteps && j < np ? s_tag[j] : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < IX_M; k++) {
+            const uint32_t j = cbase + 64u * k + lane;
+            uint64_t at = nowhere;
+            if (meta[k] != 0xFFFFFFFFu) {
+                const uint32_t r = meta[k], p = s_lo[r] + (i0 + j - s_rowpre[r]);
+                at = (uint64_t)s_trow[r] * g.stride + p;
+                meta[k] = r | (p << 9);
+            }
+            v[k] = H[at];
+            lrk[k] = 0;
+        }
+        // counts and ranks inside the wave, step by step
+#pragma unroll
+        for (uint32_t k = 0; k < IX_M; k++) {
+            if (k < nsteps) {                             // uniform
+                const bool valid = meta[k] != 0xFFFFFFFFu;
+                const uint32_t bl = valid ? (uint32_t)(v[k] >> g.shift) & (g.BW - 1u) : 0u;
+                uint64_t peers = __ballot(valid);
+                const uint32_t before = cw[bl];           // the bucket's entries in the wave's earlier steps
+                for (uint32_t bit = 0; bit < nbits; bit++) {
+                    const bool one = (bl >> bit) & 1u;
+                    const uint64_t m = __ballot(valid && one);
+                    peers &= one ? m : ~m;
+                }
+                const uint32_t below = (uint32_t)__popcll(peers & lanes_below);
+                if (valid && below == 0) cw[bl] = (uint16_t)(before + (uint32_t)__popcll(peers));
+                lrk[k] = bl | ((before + below) << 9);
+            }
+        }
+        __syncthreads();
+        IX_CLK(10);
+        {   // the waves' counts become bases: the bucket's start in the piece + what the waves below hold of it
+            uint32_t c[IX_NWV], tot = 0, all = 0;
+#pragma unroll
+            for (uint32_t x = 0; x < IX_NWV; x++) {
+                c[x] = tid < g.BW ? s_wcnt[x * IX_BW_MAX + tid] : 0u;
+                tot += c[x];
+            }
+            const uint32_t ex = ix_block_scan_sum(tot, s_part, all);
+            if (tid < g.BW) {
+                uint32_t run = ex;
+#pragma unroll
+                for (uint32_t x = 0; x < IX_NWV; x++) {
+                    s_wcnt[x * IX_BW_MAX + tid] = (uint16_t)run;
+                    run += c[x];
+                }
+                s_delta[tid] = gb - ex;
+                gb += tot;                                // the next piece of the tile goes behind this one in every bucket
+            }
+        }
+        __syncthreads();
+        IX_CLK(11);
+#pragma unroll
+        for (uint32_t k = 0; k < IX_M; k++) {
+            if (meta[k] != 0xFFFFFFFFu) {
+                const uint32_t bl = lrk[k] & 511u, rank = cw[bl] + (lrk[k] >> 9), r = meta[k] & 511u, p = meta[k] >> 9;
+                s_pack[rank] = ((v[k] & lowmask) << g.rb) | (uint64_t)(row0 + r);
+                s_tag[rank] = (uint16_t)bl;
+                slot_img[(uint64_t)(row0 + r) * g.rs + p] = s_delta[bl] + rank;
+            }
+        }
+        __syncthreads();
+        IX_CLK(12);
+        for (uint32_t j = tid; j < np; j += IX_NT) pk[s_delta[s_tag[j]] + j] = s_pack[j];
+        IX_CLK(13);
+        if (i0 + IX_PCAP < total) __syncthreads();       // uniform (the next piece writes the row table and the counters)
     }
 }
 
@@ -1416,11 +1587,14 @@ void index_dump_clocks()
     unsigned long long h[64];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(ix_clk), sizeof h) != hipSuccess) return;
     static const char *k3[] = {"prologue (lb, scan, gbase)", "loads + pack", "tile sort", "bucket scan", "pk + slots to LDS", "slot image"};
+    static const char *k3r[] = {"prologue (lb, scan, gbase)", "row table + counters", "loads + ranks in the wave", "bases", "pack + slot image", "pk"};
     static const char *k4[] = {"zero + load", "tickets", "counter scan + ticket read", "scatter", "mixed mark + fix-up + write back", "heads + inverse", "out by position + leaders", "statistics + leaders' scan", "tc by arrival", "leaders out"};
-    unsigned long long t3 = 0, t4 = 0;
+    unsigned long long t3 = 0, t3r = 0, t4 = 0;
     for (int i = 0; i < 6; i++) t3 += h[i];
     for (int i = 0; i < 10; i++) t4 += h[32 + i];
-    for (int i = 0; i < 6; i++) fprintf(stderr, "ix clocks K3 %-34s %6.2f %%\n", k3[i], 100.0 * h[i] / (t3 ? t3 : 1));
+    for (int i = 0; i < 6 && t3; i++) fprintf(stderr, "ix clocks K3 (lsd) %-28s %6.2f %%\n", k3[i], 100.0 * h[i] / t3);
+    for (int i = 0; i < 6; i++) t3r += h[8 + i];
+    for (int i = 0; i < 6 && t3r; i++) fprintf(stderr, "ix clocks K3 (rank) %-27s %6.2f %%\n", k3r[i], 100.0 * h[8 + i] / t3r);
     for (int i = 0; i < 10; i++) fprintf(stderr, "ix clocks K4 %-34s %6.2f %%\n", k4[i], 100.0 * h[32 + i] / (t4 ? t4 : 1));
     memset(h, 0, sizeof h);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(ix_clk), h, sizeof h);
@@ -1547,7 +1721,7 @@ hipError_t index_build(const IxPlan &plan, const uint64_t *hashes, const uint32_
 hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const uint32_t *rowmap, const uint32_t *off, void *lb_v, void *cnt_v, void *start_v,
                               void *big_v, void *pk_v, void *tc_v, uint64_t *keys_sorted, uint32_t *sorted_rows, uint32_t *gend, uint32_t *gs_of,
                               uint32_t *code_img, uint32_t *pos_img, void *stat_scratch, unsigned long long *incidences, uint32_t *max_group,
-                              uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages, uint32_t *row_any)
+                              uint32_t *groups, uint32_t *flags, const IxLeaders *leaders, hipStream_t stream, int stages, uint32_t *row_any, int partition)
 {
     // (leaders: looked at by stage 2 only)
     if (!plan.ok) return hipErrorInvalidValue;
@@ -1558,7 +1732,9 @@ hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const 
     uint2 *tc = static_cast<uint2 *>(tc_v);
     hipError_t e = hipSuccess;
     if (stages & 1) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(ix_tile_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)IXL_BYTES);
+        const bool lsd = partition == IX_PART_LSD;
+        e = lsd ? hipFuncSetAttribute(reinterpret_cast<const void *>(ix_tile_partition_lsd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)IXL_BYTES)
+                : hipFuncSetAttribute(reinterpret_cast<const void *>(ix_tile_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)IXR_BYTES);
         if (e != hipSuccess) return e;
         const uint32_t tiles = 8u * ((g.nseq + 7u) / 8u);
         if (!(stages & (8 | 16))) hipLaunchKernelGGL(ix_window_offsets_kernel, dim3((g.n + 3u) / 4u), dim3(256), 0, stream, g, hashes, rowmap, off,
@@ -1568,8 +1744,13 @@ hipError_t index_build_mapped(const IxPlan &plan, const uint64_t *hashes, const 
         hipLaunchKernelGGL(ix_bucket_scan_kernel, dim3(1), dim3(1024), 0, stream, g, start, flags, static_cast<uint32_t *>(big_v));
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ix_tile_partition_kernel, dim3(tiles), dim3(IX_NT), IXL_BYTES, stream, g, hashes, rowmap, (const uint16_t *)lb, (const uint32_t *)cnt,
-                           (const uint32_t *)start, (const uint32_t *)flags, pk, pos_img);
+        if (lsd) {
+            hipLaunchKernelGGL(ix_tile_partition_lsd_kernel, dim3(tiles), dim3(IX_NT), IXL_BYTES, stream, g, hashes, rowmap, (const uint16_t *)lb, (const uint32_t *)cnt,
+                               (const uint32_t *)start, (const uint32_t *)flags, pk, pos_img);
+        } else {
+            hipLaunchKernelGGL(ix_tile_partition_kernel, dim3(tiles), dim3(IX_NT), IXR_BYTES, stream, g, hashes, rowmap, (const uint16_t *)lb, (const uint32_t *)cnt,
+                               (const uint32_t *)start, (const uint32_t *)flags, pk, pos_img);
+        }
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
