@@ -414,7 +414,48 @@ int mg_compare_rect_topk_host(mg_ctx *ctx, const mg_table *ref, const mg_table *
 int mg_compare_tri_topk_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, int kmer_size,
                              double kmer_space, double max_distance, double max_p_value, uint32_t k, mg_result *out_host,
                              uint64_t capacity, uint64_t *count_out);
-/* Containment of queries in references, ON THE DEVICE (within.hip) -- `mash within`.  containSketches (CommandContain.cpp:
+/* The distance SPECTRUM of a job, binned ON THE DEVICE (spectrum.hip) -- `mash triangle -H`, `mash dist -H`.  The reference has no
+ * such option: its user runs `mash triangle -E | cut -f3,5 | sort | uniq -c` over the lines of CommandTriangle.cpp:159-198 /
+ * CommandDistance.cpp:247-304, one line of text per pair, to learn where a collection's distances lie before choosing a -d.
+ *   job      : a triangle over rows [row_begin, row_end), or a rect of queries [q_begin, q_end) x all references;
+ *   passing  : exactly the pairs mg_compare_*_results_host returns under the same max_distance / max_p_value conventions (each < 0 or
+ *              >= 1: that filter is off) -- the pairs `triangle -E` / `dist` print;
+ *   spectrum : the distinct {numer, denom} among the passing pairs, each with the number of pairs that have it as a 64-bit count;
+ *   order    : ascending distance, that is descending fraction, compared exactly: bin a before bin b iff numer_a * denom_b >
+ *              numer_b * denom_a in 64-bit integers; 0/0 (two empty sketches: distance 0, CommandDistance.cpp:390-393) orders as 1/1;
+ *              equal fractions by ascending denominator.
+ * The counts sum to the number of passing pairs; with both filters off, to the number of pairs of the range.  No float takes part in
+ * which bin a pair falls into (the filters are pass A's: integer and exact), integer adds commute, and so the result is a function of
+ * the job alone: not of the route, the blocking or the schedule.
+ * capacity / *count_out / MG_ERR_NOMEM as for mg_compare_*_filter_host (capacity 0 with out_host NULL asks for the number of bins
+ * alone).  Ranges clamp as elsewhere; an empty range gives 0 bins.  A p-value filter on a table without lengths: MG_ERR_INVALID.
+ * Routes (mg_spectrum_stats reports the one the context's last call took; 0: the range had no pairs):
+ *   1  a filter is on: the thresholded counts -- the index engine's candidate lists, or the matrix in row blocks (context option
+ *      MASHGPU_SPECTRUM_BLOCK_PAIRS: pairs per block, a test knob) --, pass A per piece, and one launch that bins the counts beside
+ *      the set bits of its ballots;
+ *   2  filters off, lists available: every list entry is binned by its own {numer, denom} and, a second time, by its rule denominator
+ *      min(s, |A| + |B|) (|X| = min(nhash, s); rect: s = the smaller sketch size).  The pairs NOT on the list are {0, rule
+ *      denominator} (mg_compare_tri_sparse_host states the rule); the host counts the range's pairs per rule denominator from the
+ *      rows' hash counts, subtracts the second binning and adds the rest to the bins {0, D}.  No matrix is allocated, no fill runs;
+ *   3  filters off, no lists (copies of rows, empty rows, nearly every pair related, the engine switched off): the matrix in row
+ *      blocks, every count binned.
+ * mg_spectrum_stats (any pointer may be NULL): the route; on route 2 the list entries and those of them with numer 0 (a hash shared
+ * only behind the first s union elements); the distinct keys whose denominator is not s; the times the device table of those keys was
+ * enlarged and the call run again (context option MASHGPU_SPECTRUM_SLOTS: its first size, a test knob).  Context option
+ * MASHGPU_SPECTRUM_PLAIN: one atomic add per pair straight to memory instead of combining equal keys in the wave and counting in LDS
+ * (an A/B knob: the results are the same bits).
+ * Limits: one device (no sharded form), host output only (no *_dev form), no per-row spectra; with a p-value filter, p-values are
+ * evaluated for every pair that passes the distance filter. */
+typedef struct mg_spectrum_bin { uint32_t numer, denom; uint64_t count; } mg_spectrum_bin;
+int mg_compare_tri_spectrum_host(mg_ctx *ctx, const mg_table *t, uint64_t row_begin, uint64_t row_end, int kmer_size, double kmer_space,
+                                 double max_distance, double max_p_value, mg_spectrum_bin *out_host, uint64_t capacity,
+                                 uint64_t *count_out);
+int mg_compare_rect_spectrum_host(mg_ctx *ctx, const mg_table *ref, const mg_table *qry, uint64_t q_begin, uint64_t q_end, int kmer_size,
+                                  double kmer_space, double max_distance, double max_p_value, mg_spectrum_bin *out_host,
+                                  uint64_t capacity, uint64_t *count_out);
+int mg_spectrum_stats(mg_ctx *ctx, uint64_t *route_out, uint64_t *listed_out, uint64_t *listed_zero_out, uint64_t *other_keys_out,
+                      uint64_t *regrows_out);
+/* Containment of queries in references, ON THE DEVICE (within.hip) -- `mash within`. containSketches (CommandContain.cpp:
  * 231-263) walks reference R and query Q, both ascending, with two pointers and stops when the query pointer j reaches
  * min(|R|, |Q|) or R is exhausted; it returns score = common / j and error = 1 / sqrt(j).  In closed form, in integers:
  *   c      = #{q in Q : q <= max(R)}

@@ -33,6 +33,7 @@ EXPORTS = [
     "mg_finish_tri_dev", "mg_finish_rect_dev", "mg_compare_tri_pairs_host", "mg_compare_rect_pairs_host",
     "mg_compare_tri_results_host", "mg_compare_rect_results_host", "mg_compare_rect_topk_host", "mg_compare_tri_topk_host",
     "mg_within_rect_host", "mg_within_rect_results_host",
+    "mg_compare_tri_spectrum_host", "mg_compare_rect_spectrum_host", "mg_spectrum_stats",
     "mg_cluster_tri_host", "mg_cluster_tri_dev", "mg_cluster_tri_greedy_host", "mg_cluster_tri_greedy_dev", "mg_cluster_greedy_stats",
     "mg_cluster_tri_nearest_host", "mg_cluster_tri_nearest_dev", "mg_cluster_tri_medoid_host", "mg_cluster_tri_medoid_dev",
     "mg_cluster_extend_host", "mg_cluster_extend_greedy_host",
@@ -86,6 +87,7 @@ PAIR_DTYPE = np.dtype([("numer", "<u4"), ("denom", "<u4"), ("distance", "<f8"), 
                        ("pass", "u1"), ("_pad", "u1", 7)])
 COUNTS_DTYPE = np.dtype([("numer", "<u4"), ("denom", "<u4")])
 EDGE_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("numer", "<u4"), ("denom", "<u4")])
+SPECTRUM_DTYPE = np.dtype([("numer", "<u4"), ("denom", "<u4"), ("count", "<u8")])
 RESULT_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("numer", "<u4"), ("denom", "<u4"),
                          ("distance", "<f8"), ("p_value", "<f8")])
 
@@ -373,6 +375,9 @@ def load_library():
     lib.mg_cluster_tri_medoid_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp, vp, vp]
     lib.mg_cluster_tri_medoid_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp, vp, vp]
     lib.mg_cluster_greedy_stats.argtypes = [vp, vp, vp, vp, vp]
+    lib.mg_compare_tri_spectrum_host.argtypes = [vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
+    lib.mg_compare_rect_spectrum_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, vp, u64, vp]
+    lib.mg_spectrum_stats.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.mg_cluster_extend_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_extend_greedy_host.argtypes = [vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_tri_forest_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, u64, vp, vp, vp, vp]
@@ -1007,6 +1012,27 @@ class MashGpu:
         q_end = qry.rows if q_end is None else min(q_end, qry.rows)
         return self._filter(lambda o, c, n: self.lib.mg_compare_rect_results_host(
             self.ctx, ref.handle, qry.handle, q_begin, q_end, k, kmer_space, max_d, max_p, o, c, n), capacity, RESULT_DTYPE)
+
+    def tri_spectrum(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0, row_begin=0, row_end=None, capacity=1 << 12):
+        """the distance spectrum of rows [row_begin,row_end) x earlier rows: SPECTRUM_DTYPE {numer, denom, count} per distinct
+        {numer, denom} among the pairs that pass the filters, binned on the device, in ascending distance -- descending exact
+        fraction, 0/0 as 1/1, equal fractions by ascending denominator (mg_compare_tri_spectrum_host)"""
+        row_end = table.rows if row_end is None else min(row_end, table.rows)
+        return self._filter(lambda o, c, n: self.lib.mg_compare_tri_spectrum_host(
+            self.ctx, table.handle, row_begin, row_end, k, kmer_space, max_d, max_p, o, c, n), capacity, SPECTRUM_DTYPE)
+
+    def rect_spectrum(self, ref, qry, k, kmer_space, max_d=-1.0, max_p=-1.0, q_begin=0, q_end=None, capacity=1 << 12):
+        """the same over queries [q_begin,q_end) x all references (mg_compare_rect_spectrum_host)"""
+        q_end = qry.rows if q_end is None else min(q_end, qry.rows)
+        return self._filter(lambda o, c, n: self.lib.mg_compare_rect_spectrum_host(
+            self.ctx, ref.handle, qry.handle, q_begin, q_end, k, kmer_space, max_d, max_p, o, c, n), capacity, SPECTRUM_DTYPE)
+
+    def spectrum_stats(self):
+        """what this context's last tri_spectrum / rect_spectrum call did: {route (1 filtered, 2 lists and the rule, 3 the matrix,
+        0 no pairs), listed, listed_zero, other_keys, regrows} (mg_spectrum_stats)"""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._check(self.lib.mg_spectrum_stats(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("route", "listed", "listed_zero", "other_keys", "regrows"), (int(x.value) for x in v)))
 
     def compare_rect_topk(self, ref, qry, k, kmer_space, topk, max_d=-1.0, max_p=-1.0, q_begin=0, q_end=None, capacity=None):
         """per query its `topk` nearest references among the pairs that pass the filters, chosen on the device: best first by the

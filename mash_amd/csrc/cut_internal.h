@@ -79,6 +79,12 @@ struct CandLists {
     void release() { rc.free(); cnt.free(); byrow.free(); base.free(); temp.free(); }
 };
 
+// The inverted-index engine's job over R as lists, for a consumer that takes them whole (host_spectrum.cpp: with the filters off the
+// lists are every pair that is not {0, rule denominator}).  *ok false: no lists -- the engine is forced off or leaves the job to the
+// matrix (copies of rows, empty rows, nearly every pair related), or they do not fit; that is no error, and L is released then.
+// *ok with L.K == 0: no pair of R shares a hash.  extra(K) allocates the consumer's buffers for K entries (false: they do not fit).
+int job_cand_lists(mg_ctx *ctx, const OutRange &R, CandLists &L, bool *ok, const std::function<bool(uint64_t K)> &extra);
+
 // Pass A of a finish (finish_mark_kernel) over up to `pairs` entries: its ballots and segments, the denominators it flags
 struct PassABufs {
     DevBuf<unsigned long long> masks, seg_off;

@@ -2017,6 +2017,12 @@ static int cand_lists(mg_ctx *ctx, const OutRange &R, CandLists &L, bool *ok, Ex
     return job_lists(ctx, job, nrows, R.triangle ? 0u : (uint32_t)R.rb, R.s, L.byrow, L.base, L.temp, L.tb, L.rc, L.cnt);
 }
 
+// cand_lists for a consumer in another file (cut_internal.h)
+int job_cand_lists(mg_ctx *ctx, const OutRange &R, CandLists &L, bool *ok, const std::function<bool(uint64_t K)> &extra)
+{
+    return cand_lists(ctx, R, L, ok, [&](uint64_t K, size_t &) { return extra(K); });
+}
+
 // The counts of R for a consumer that thresholds them (cut_internal.h says what the callbacks are given), by one of two routes: the
 // lists (cand_lists), or the matrix in row blocks (matrix_blocks: alloc answers as its callback does)
 int cut_counts(mg_ctx *ctx, const OutRange &R, const Cut &cut, bool try_lists, const Blocks &how, CutBufs &B, const CutAlloc &alloc,

@@ -5,6 +5,7 @@
 // host_reads.cpp   sketching in reads mode: sessions fed chunk by chunk, the reference's heap on the host
 // host_compare.cpp comparing: tile engine, inverted-index engine, finishing, thresholded and list outputs
 // host_cluster.cpp clustering: unions and edge lists over the thresholded counts (cut_internal.h: what host_compare.cpp gives them)
+// host_spectrum.cpp the distance spectrum: the counts of a job binned on the device (cut_internal.h, spectrum_internal.h)
 // host_comm.cpp    several GPUs: communicator, replicated / row-sharded tables, sharded calls
 // host_screen.cpp  screening, on one GPU and on several
 // host_taxscreen.cpp  taxonomy of a screen: per-hash LCA, per-taxon counts
@@ -41,6 +42,7 @@
 #include "screen_finish_internal.h"
 #include "screen_internal.h"
 #include "sketch_internal.h"
+#include "spectrum_internal.h"
 #include "taxscreen_internal.h"
 
 struct ProfRec { hipEvent_t a, b; };
@@ -117,6 +119,9 @@ struct mg_ctx {
     // mg_cluster_complete_stats / mg_cluster_complete_rounds: the same for the last mg_cluster_tri_complete_* call
     uint64_t complete_rounds = 0, complete_batches = 0, complete_regrows = 0, complete_edge_cap = 0;
     std::vector<uint64_t> complete_live, complete_merged;   // per round, the links alive when it began and the links it merged
+    // mg_spectrum_stats: the route the last mg_compare_*_spectrum_host call took (0: no pairs), the list entries it binned and those
+    // of them with numer 0, the distinct keys with a denominator other than s, the times the table of those keys was enlarged
+    uint64_t spectrum_route = 0, spectrum_listed = 0, spectrum_listed_zero = 0, spectrum_other_keys = 0, spectrum_regrows = 0;
     // the compare dispatch's prices, corrected from this context's own launches; the event pairs that time a phase
     SparseCosts costs;
     struct CostClock { hipEvent_t a = nullptr, b = nullptr; };

@@ -1027,6 +1027,13 @@ struct FastOut {
         buf.append(t, r.ptr);
         return *this;
     }
+    FastOut &operator<<(uint64_t v)
+    {
+        char t[24];
+        auto r = std::to_chars(t, t + sizeof t, v);
+        buf.append(t, r.ptr);
+        return *this;
+    }
     void eol() { buf += '\n'; room(); }
 };
 
@@ -1286,6 +1293,56 @@ using DTable = std::unique_ptr<mg_dtable, DTableFree>;
 // what every compare command ends with
 int finish_run(const SketchSet &set, const KmerWarning &w, bool reads) { if (w.count > 0 && !reads) warn_kmer_size(set, w); return 0; }
 
+// Options that cannot be given together, for `dist` and `triangle`: the first row that matches is the one reported.  Non-zero: refused.
+struct OptionClash { const char *a, *b; };
+int refuse_clashes(const Cmd &c, std::initializer_list<OptionClash> clashes)
+{
+    for (const OptionClash &x : clashes) {
+        if (!c.o(x.a).active || !c.o(x.b).active) continue;
+        cerr << "ERROR: The option -" << c.o(x.a).id << " cannot be used with -" << c.o(x.b).id << "." << endl;
+        return 1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- -H: the distance spectrum
+// `triangle -H` / `dist -H`: instead of the pairs that pass -d and -v, the distinct shared-hashes fractions among them and how many
+// pairs have each (include/mashgpu.h: mg_compare_tri_spectrum_host) -- one line per bin, nearest first:
+//   <distance> TAB <numer>/<denom> TAB <pairs> TAB <pairs at or below this distance>
+// The bins are counted on the device, block of rows by block of rows; bins of equal key are added here.
+// MASH_AMD_HOST_FINISH=1 is the host route, which the tests judge the device route by: with a filter on the records of
+// mg_compare_*_results_host are binned here; with the filters off the pairs that share a hash (mg_compare_*_sparse_host) are, and
+// every other pair is {0, min(s, |A| + |B|)} by the rule stated there.
+struct Spectrum {
+    std::map<uint64_t, uint64_t> bins;        // numer << 32 | denom -> pairs
+    void add(uint32_t numer, uint32_t denom, uint64_t n = 1) { if (n) bins[(uint64_t)numer << 32 | denom] += n; }
+    // the pairs of one row with clamped hash count c against rows whose clamped counts are histogrammed in `below`: all {0, rule
+    // denominator} until the listed ones are taken out again (unlist)
+    void add_rule(uint64_t s, uint64_t c, const std::map<uint64_t, uint64_t> &below)
+    {
+        for (const auto &h : below) add(0, (uint32_t)std::min(s, c + h.first), h.second);
+    }
+    void unlist(uint64_t s, uint64_t ca, uint64_t cb) { bins[std::min(s, ca + cb)]--; }
+    void print(FastOut &out, int kmer) const
+    {
+        vector<std::pair<uint64_t, uint64_t>> v;
+        for (const auto &b : bins) if (b.second) v.push_back(b);
+        // ascending distance: descending fraction, exactly; 0/0 (distance 0) as 1/1; equal fractions by ascending denominator
+        std::sort(v.begin(), v.end(), [](const std::pair<uint64_t, uint64_t> &a, const std::pair<uint64_t, uint64_t> &b) {
+            const uint64_t ad = (uint32_t)a.first, bd = (uint32_t)b.first;
+            const uint64_t l = (ad ? a.first >> 32 : 1) * (bd ? bd : 1), r = (bd ? b.first >> 32 : 1) * (ad ? ad : 1);
+            return l != r ? l > r : ad < bd;
+        });
+        uint64_t below = 0;
+        for (const auto &b : v) {
+            const uint32_t numer = (uint32_t)(b.first >> 32), denom = (uint32_t)b.first;
+            below += b.second;
+            out << mg_distance(numer, denom, kmer) << '\t' << numer << '/' << denom << '\t' << b.second << '\t' << below;
+            out.eol();
+        }
+    }
+};
+
 // ------------------------------------------------------------------------------- dist
 // Budgets of a block of query rows (MASH_AMD_BLOCK_PAIRS lowers them; kDistFilteredPairs stands with rect_edge_blocks):
 const uint64_t kDistFullPairs = 1ull << 24;         // the whole matrix comes back: 512 MiB of mg_pair per block
@@ -1387,6 +1444,44 @@ int dist_filtered(DistRun &r)
     return 0;
 }
 
+// -H: the spectrum of the pairs that pass -d and -v (one device: the first of those selected)
+int dist_spectrum(DistRun &r)
+{
+    Spectrum sp;
+    const bool filtered = r.d_max < 1.0 || r.p_max < 1.0;
+    const uint64_t s = std::min(r.ref.p.sketch_size, r.qry.p.sketch_size);
+    auto clamped = [&](const Ref &x) { return std::min<uint64_t>(x.hashes.size(), s); };
+    vector<mg_spectrum_bin> bins;
+    vector<mg_result> res;
+    vector<mg_edge> edges;
+    std::map<uint64_t, uint64_t> href;
+    for (const Ref &x : r.ref.refs) href[clamped(x)]++;
+    for (Blocks b(0, r.nq, kDistFilteredPairs, r.nref); b.next();) {
+        if (!host_finish_wanted()) {
+            if (!fetch_list(r.gpu, bins, [&](mg_spectrum_bin *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_rect_spectrum_host(r.gpu.ctx, r.tr, r.tq, b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, n); }))
+                return 1;
+            for (const mg_spectrum_bin &x : bins) sp.add(x.numer, x.denom, x.count);
+        } else if (filtered) {
+            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_rect_results_host(r.gpu.ctx, r.tr, r.tq, b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, n); }))
+                return 1;
+            for (const mg_result &e : res) sp.add(e.numer, e.denom);
+        } else {
+            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_rect_sparse_host(r.gpu.ctx, r.tr, r.tq, b.r0, b.r1, o, cap, n); }))
+                return 1;
+            for (uint64_t q = b.r0; q < b.r1; q++) sp.add_rule(s, clamped(r.qry.refs[q]), href);
+            for (const mg_edge &e : edges) {
+                sp.unlist(s, clamped(r.qry.refs[e.row]), clamped(r.ref.refs[e.col]));
+                sp.add(e.numer, e.denom);
+            }
+        }
+    }
+    sp.print(r.out, r.kmer);
+    return 0;
+}
+
 // Every pair: lines, or with -t one row of cells per query (writeOutput, CommandDistance.cpp:247-304)
 int dist_full(DistRun &r)
 {
@@ -1470,20 +1565,22 @@ int cmd_dist(int argc, const char **argv)
     c.add("distance", Opt::Number, "d", "1.0", 0., 1.);
     c.add("comment", Opt::Boolean, "C");
     c.add("nearest", Opt::Integer, "N", "", 1, (float)MG_TOPK_MAX);          // (not in the reference: its user pipes through sort | head)
+    c.add("spectrum", Opt::Boolean, "H");                                    // (not in the reference: ... | cut -f3,5 | sort | uniq -c)
     c.use_sketch_options();
     if (c.parse(argc, argv)) return 1;
     if (c.args.size() < 2 || c.o("help").active) {
         cout << "\nUsage:\n\n  mash dist [options] <reference> <query> [<query>] ...\n\n"
                 "Output fields: [reference-ID, query-ID, distance, p-value, shared-hashes].\n"
-                "Options: -l -t -v <max p> -d <max dist> -C -N <int> and the sketch options of `mash sketch`.\n"
+                "Options: -l -t -v <max p> -d <max dist> -C -N <int> -H and the sketch options of `mash sketch`.\n"
                 "  -N <int>  Per query at most <int> lines (1-" << MG_TOPK_MAX << "): its nearest references among those that pass -d and -v,\n"
-                "            best first by shared-hashes as an exact fraction, equal fractions in reference order.\n\n";
+                "            best first by shared-hashes as an exact fraction, equal fractions in reference order.\n"
+                "  -H        The distance spectrum instead of the pairs: one line per distinct shared-hashes fraction among the pairs\n"
+                "            that pass -d and -v, nearest first: [distance, shared-hashes, pairs, pairs at or below this distance].\n"
+                "            Not with -t or -N.\n\n";
         return 0;
     }
-    if (c.o("nearest").active && c.o("table").active) {
-        cerr << "ERROR: The option -" << c.o("nearest").id << " cannot be used with -" << c.o("table").id << "." << endl;
-        return 1;
-    }
+    if (refuse_clashes(c, {{"nearest", "table"}, {"spectrum", "table"}, {"spectrum", "nearest"}})) return 1;
+    const bool spectrum = c.o("spectrum").active;
     const uint32_t nearest = c.o("nearest").active ? (uint32_t)c.o("nearest").num : 0;
     const bool table = c.o("table").active, comment = c.o("comment").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
@@ -1517,9 +1614,9 @@ int cmd_dist(int argc, const char **argv)
     if (nref == 0 || nq == 0) return 0;
     // several GPUs: the larger side is cut into row blocks; references larger than the queries
     // are then not even replicated (the host-tail test paths address device 0's table as a whole)
-    const bool ref_by_rows = mg_comm_size(gpu.comm) > 1 && nref > nq && !host_finish_wanted() && !getenv("MASH_AMD_NO_FILTER");
+    const bool ref_by_rows = mg_comm_size(gpu.comm) > 1 && nref > nq && !host_finish_wanted() && !getenv("MASH_AMD_NO_FILTER") && !spectrum;
     DistRun run(gpu, ref, qry, table, comment, nearest, d_max, p_max, ref_by_rows);
-    if (nearest ? dist_nearest(run) : !table && edge_filter_wanted(d_max, p_max) ? dist_filtered(run) : dist_full(run)) return 1;
+    if (spectrum ? dist_spectrum(run) : nearest ? dist_nearest(run) : !table && edge_filter_wanted(d_max, p_max) ? dist_filtered(run) : dist_full(run)) return 1;
     return finish_run(ref, w, p.reads);
 }
 
@@ -1834,6 +1931,47 @@ int tri_dense(TriRun &r, uint64_t r0)
     return 0;
 }
 
+// -H: the spectrum of the pairs that pass -d and -v (one device: the first of those selected)
+int tri_spectrum(TriRun &r)
+{
+    Spectrum sp;
+    const bool filtered = r.d_max < 1.0 || r.p_max < 1.0;
+    const uint64_t s = r.set.p.sketch_size;
+    auto clamped = [&](uint64_t i) { return std::min<uint64_t>(r.set.refs[i].hashes.size(), s); };
+    vector<mg_spectrum_bin> bins;
+    vector<mg_result> res;
+    vector<mg_edge> edges;
+    std::map<uint64_t, uint64_t> below;                           // the clamped hash counts of the rows ahead of the one at hand
+    if (r.n) below[clamped(0)]++;
+    for (Blocks b(1, r.n, kTriFilteredPairs); b.next();) {
+        if (!host_finish_wanted()) {
+            if (!fetch_list(r.gpu, bins, [&](mg_spectrum_bin *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_tri_spectrum_host(r.gpu.ctx, r.t, b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, n); }))
+                return 1;
+            for (const mg_spectrum_bin &x : bins) sp.add(x.numer, x.denom, x.count);
+        } else if (filtered) {
+            if (!fetch_list(r.gpu, res, [&](mg_result *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_tri_results_host(r.gpu.ctx, r.t, b.r0, b.r1, r.kmer, r.kspace, r.d_max, r.p_max, o, cap, n); }))
+                return 1;
+            for (const mg_result &e : res) sp.add(e.numer, e.denom);
+        } else {
+            if (!fetch_list(r.gpu, edges, [&](mg_edge *o, uint64_t cap, uint64_t *n) {
+                    return mg_compare_tri_sparse_host(r.gpu.ctx, r.t, b.r0, b.r1, o, cap, n); }))
+                return 1;
+            for (uint64_t i = b.r0; i < b.r1; i++) {
+                sp.add_rule(s, clamped(i), below);
+                below[clamped(i)]++;
+            }
+            for (const mg_edge &e : edges) {
+                sp.unlist(s, clamped(e.row), clamped(e.col));
+                sp.add(e.numer, e.denom);
+            }
+        }
+    }
+    sp.print(r.out, r.kmer);
+    return 0;
+}
+
 int cmd_triangle(int argc, const char **argv)
 {
     Cmd c;
@@ -1845,22 +1983,28 @@ int cmd_triangle(int argc, const char **argv)
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "1.0", 0., 1.);
     c.add("nearest", Opt::Integer, "N", "", 1, (float)MG_TOPK_MAX);          // (not in the reference)
+    c.add("spectrum", Opt::Boolean, "H");                                    // (not in the reference)
     c.use_sketch_options();
     if (c.parse(argc, argv)) return 1;
     if (c.args.empty() || c.o("help").active) {
         cout << "\nUsage:\n\n  mash triangle [options] <seq1> [<seq2>] ...\n\n"
                 "Lower-triangular distance matrix in relaxed Phylip format (or -E edge list).\n"
-                "Options: -l -C -E -v <max p> -d <max dist> -N <int> and the sketch options of `mash sketch`.\n"
+                "Options: -l -C -E -v <max p> -d <max dist> -N <int> -H and the sketch options of `mash sketch`.\n"
                 "  -N <int>  Per sketch, in input order, at most <int> edge-list lines (1-" << MG_TOPK_MAX << "): its nearest neighbours among the other\n"
                 "            sketches that pass -d and -v, best first by shared-hashes as an exact fraction, equal fractions in input\n"
-                "            order.  Implies -E; a pair can appear under both its sketches.\n\n";
+                "            order.  Implies -E; a pair can appear under both its sketches.\n"
+                "  -H        The distance spectrum instead of the matrix: one line per distinct shared-hashes fraction among the pairs\n"
+                "            that pass -d and -v, nearest first: [distance, shared-hashes, pairs, pairs at or below this distance] --\n"
+                "            the last field is the number of lines -E -d <distance> would print.  Not with -E or -N.\n\n";
         return 0;
     }
+    if (refuse_clashes(c, {{"spectrum", "edge"}, {"spectrum", "nearest"}})) return 1;
+    const bool spectrum = c.o("spectrum").active;
     const uint32_t nearest = c.o("nearest").active ? (uint32_t)c.o("nearest").num : 0;
     const bool comment = c.o("comment").active;
     bool edge = c.o("edge").active;
     const double p_max = c.o("pvalue").num, d_max = c.o("distance").num;
-    if (c.o("pvalue").active || c.o("distance").active || nearest) edge = true;
+    if (c.o("pvalue").active || c.o("distance").active || nearest || spectrum) edge = true;
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // CommandTriangle.cpp:74-77
@@ -1878,7 +2022,7 @@ int cmd_triangle(int argc, const char **argv)
     const uint64_t keep = std::min<uint64_t>(nearest, n - 1);
     if (nearest && !keep) return 0;                              // one sketch: no neighbour to rank
     uint64_t r0 = 1;                                             // the row at which the sparse route hands over to the dense one
-    if (nearest ? tri_nearest(run, keep) : edge && edge_filter_wanted(d_max, p_max) ? tri_filtered(run) : tri_sparse(run, r0) || tri_dense(run, r0)) return 1;
+    if (spectrum ? tri_spectrum(run) : nearest ? tri_nearest(run, keep) : edge && edge_filter_wanted(d_max, p_max) ? tri_filtered(run) : tri_sparse(run, r0) || tri_dense(run, r0)) return 1;
     run.dt.reset();                                              // (inside the "teardown" lap, as the later lines)
     if (!edge) cerr << "Max p-value: " << run.peak.peak << endl;
     return finish_run(set, w, p.reads);
@@ -2881,9 +3025,9 @@ int main(int argc, const char **argv)
 {
     const string usage =
         "\nMash (MI355X hot path), commands:\n\n  sketch    Create sketches (reduced representations for fast operations).\n"
-        "  dist      Estimate the distance of query sequences to references.\n"
+        "  dist      Estimate the distance of query sequences to references, or the spectrum of those distances (-H).\n"
         "  within    Estimate the containment of query sequences within references.\n"
-        "  triangle  Estimate a lower-triangular distance matrix.\n"
+        "  triangle  Estimate a lower-triangular distance matrix, or the spectrum of its distances (-H).\n"
         "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), name each single-linkage cluster's medoid (-M), extend an earlier clustering by new sequences (-A), print the minimum spanning forest (-T), or form complete-linkage clusters, every two members within the distance (-L).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
