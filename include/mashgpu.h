@@ -673,6 +673,48 @@ int mg_cluster_tri_complete_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, d
 int mg_cluster_complete_stats(mg_ctx *ctx, uint64_t *rounds_out, uint64_t *batches_out, uint64_t *regrows_out,
                               uint64_t *edge_capacity_out);
 int mg_cluster_complete_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *merged_out, uint64_t capacity, uint64_t *rounds_out);
+/* Density clusters (DBSCAN) of the same thresholded all-vs-all, found ON THE DEVICE (cluster_density.hip) -- `mash cluster -D`.  The
+ * reference has no such command (its user fetches the lines of `mash triangle -E -d` and runs scikit-learn on them); the definition
+ * stands on those lines.  Everything is exact, no float takes part, and nothing depends on execution order, route or blocking:
+ *   edge      : exactly a pair {row, col} that mg_compare_tri_results_host(ctx, t, 0, rows, kmer_size, kmer_space, max_distance,
+ *               max_p_value, ...) returns -- the edge of mg_cluster_tri_host -- with its counts numer / denom;
+ *   degree[i] : the number of edges with an end at i;
+ *   core      : degree[i] >= min_neighbours, that is, at least min_neighbours OTHER rows lie within the threshold (the classic
+ *               minPts, which counts the point itself, is min_neighbours + 1);
+ *   clusters  : the connected components of the cores under the edges whose BOTH ends are cores;
+ *   border    : not a core, with an edge to at least one core.  It joins the cluster of its nearest core neighbour via[i]: the one
+ *               whose edge has the larger numer/denom, compared exactly, numer_a * denom_b against numer_b * denom_a in 64-bit integers,
+ *               0/0 counting as 0/1 (the order of mg_cluster_tri_forest_host's edges); equal fractions, also under different
+ *               denominators, go to the core of smaller row.  Edges between two rows that are not cores decide nothing: a border
+ *               never links two clusters;
+ *   noise     : neither; a cluster of its own, of size 1;
+ *   label[i]  : the smallest row of i's final cluster -- a border may precede every core of its cluster, so a cluster's label can
+ *               be a border's row;   via[i] : i for a core and for noise, the chosen core for a border;
+ *   n_clusters: the number of i with label[i] == i, noise included;   n_edges : mg_cluster_tri_host's.
+ * With min_neighbours == 1 every row with an edge is a core, nothing is a border, and label, n_clusters and n_edges are
+ * mg_cluster_tri_host's; with min_neighbours above the largest degree every row is noise.  min_neighbours == 0: MG_ERR_INVALID.
+ * via_out and degree_out may be NULL.  All other errors and limits are those of mg_cluster_tri_nearest_host: the whole table only,
+ * one device, at most 2^31 - 1 rows; a sketch size of 2^21 or more: MG_ERR_UNSUPPORTED (the 64-bit weight key orders denominators
+ * below 2^21 exactly); both filters disabled: MG_ERR_INVALID; a table without lengths: MG_ERR_INVALID; a table of 0 or 1 rows: MG_OK.
+ * The p-value filter is evaluated for every pair that passes max_distance.  The edges are kept on the device as 16 bytes each while
+ * the call runs (the list of mg_cluster_tri_nearest_host: it grows on demand, MASHGPU_GREEDY_EDGE_CAP sets its first capacity); if
+ * they do not fit the call returns MG_ERR_NOMEM, it never drops an edge.  Everything behind the last append is one batch with one
+ * wait.  Only rows x 4 bytes per array cross PCIe; _dev leaves the arrays on the device.  MASHGPU_CLUSTER_BLOCK_PAIRS and
+ * MASHGPU_RESULTS_MATRIX as for mg_cluster_tri_host; the context option MASHGPU_DENSITY_PLAIN sends two atomic adds per edge to memory
+ * in the degree pass instead of combining a row's run in the wave first (an A/B knob: the results are the same bits).  There is no
+ * extending form: a new row changes the degrees, and so the roles, of old rows.
+ * mg_cluster_density_stats: what the context's last such call found -- cores, borders, noise (they add up to rows), times the edge
+ * list was regrown, its final capacity in edges (any pointer may be NULL). */
+int mg_cluster_tri_density_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                                double max_p_value, uint32_t min_neighbours, uint32_t *label_out_host /* [rows] */,
+                                uint32_t *via_out_host /* [rows] or NULL */, uint32_t *degree_out_host /* [rows] or NULL */,
+                                uint64_t *n_clusters_out, uint64_t *n_edges_out);
+int mg_cluster_tri_density_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance,
+                               double max_p_value, uint32_t min_neighbours, uint32_t *label_out_dev /* [rows] */,
+                               uint32_t *via_out_dev /* [rows] or NULL */, uint32_t *degree_out_dev /* [rows] or NULL */,
+                               uint64_t *n_clusters_out, uint64_t *n_edges_out);
+int mg_cluster_density_stats(mg_ctx *ctx, uint64_t *cores_out, uint64_t *borders_out, uint64_t *noise_out, uint64_t *regrows_out,
+                             uint64_t *edge_capacity_out);
 /* Scalar helpers (same arithmetic as the bulk calls). */
 double mg_distance(uint32_t numer, uint32_t denom, int kmer_size);
 double mg_p_value(uint64_t x, uint64_t len_ref, uint64_t len_qry, double kmer_space,

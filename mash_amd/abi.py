@@ -39,6 +39,7 @@ EXPORTS = [
     "mg_cluster_extend_host", "mg_cluster_extend_greedy_host",
     "mg_cluster_tri_forest_host", "mg_cluster_forest_stats", "mg_cluster_forest_rounds",
     "mg_cluster_tri_complete_host", "mg_cluster_tri_complete_dev", "mg_cluster_complete_stats", "mg_cluster_complete_rounds",
+    "mg_cluster_tri_density_host", "mg_cluster_tri_density_dev", "mg_cluster_density_stats",
     "mg_prof_enable", "mg_prof_reset", "mg_prof_avg_ms",
     "mg_screen_create", "mg_screen_create_translated", "mg_screen_add_host", "mg_screen_add_dev", "mg_screen_finish_host", "mg_screen_counts_dev", "mg_screen_free",
     "mg_screen_reset", "mg_screen_finish_sparse_host", "mg_screen_tier_note", "mg_dscreen_finish_sparse_host", "mg_dscreen_reset",
@@ -387,6 +388,9 @@ def load_library():
     lib.mg_cluster_tri_complete_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, vp, vp, vp]
     lib.mg_cluster_complete_stats.argtypes = [vp, vp, vp, vp, vp]
     lib.mg_cluster_complete_rounds.argtypes = [vp, vp, vp, u64, vp]
+    lib.mg_cluster_tri_density_host.argtypes = [vp, vp, i32, dbl, dbl, dbl, u32, vp, vp, vp, vp, vp]
+    lib.mg_cluster_tri_density_dev.argtypes = [vp, vp, i32, dbl, dbl, dbl, u32, vp, vp, vp, vp, vp]
+    lib.mg_cluster_density_stats.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.mg_compare_rect_topk_sharded_host.argtypes = [vp, vp, vp, u64, u64, i32, dbl, dbl, dbl, C.c_uint32, vp, u64, vp]
     lib.mg_dscreen_create.argtypes = [vp, C.POINTER(MgParams), vp, i32, C.POINTER(vp)]
     lib.mg_dscreen_add_host.argtypes = [vp, vp, u64]
@@ -1177,6 +1181,32 @@ class MashGpu:
         n = C.c_uint64(0)
         self._check(self.lib.mg_cluster_forest_rounds(self.ctx, live.ctypes.data, chosen.ctypes.data, 64, C.byref(n)))
         return live[:n.value].tolist(), chosen[:n.value].tolist()
+
+    def cluster_tri_density_host(self, table, k, kmer_space, min_neighbours, max_d=-1.0, max_p=-1.0):
+        """density clusters of the pairs compare_tri_results returns for the whole table, found on the device: a row with at least
+        min_neighbours edges is a core, cores cluster over the edges between them, a row that is no core joins the core whose edge has
+        the larger numer/denom, exactly (equal fractions: the smaller core), the rest is noise: (label u32[rows] = the smallest row of
+        the row's cluster, via u32[rows] = the chosen core of a border, else the row itself, degree u32[rows], clusters, edges)
+        (mg_cluster_tri_density_host)"""
+        label, via, degree = (np.zeros(table.rows, dtype=np.uint32) for _ in range(3))
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_density_host(self.ctx, table.handle, k, kmer_space, max_d, max_p, min_neighbours, label.ctypes.data,
+                                                         via.ctypes.data, degree.ctypes.data, C.byref(nc), C.byref(ne)))
+        return label, via, degree, int(nc.value), int(ne.value)
+
+    def cluster_tri_density_dev(self, table, k, kmer_space, min_neighbours, label_ptr, via_ptr=None, degree_ptr=None, max_d=-1.0, max_p=-1.0):
+        """cluster_tri_density_host with the arrays left on the device at label_ptr, via_ptr and degree_ptr (u32[rows]; the last two may
+        be None): (clusters, edges)"""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.mg_cluster_tri_density_dev(self.ctx, table.handle, k, kmer_space, max_d, max_p, min_neighbours, label_ptr, via_ptr,
+                                                        degree_ptr, C.byref(nc), C.byref(ne)))
+        return int(nc.value), int(ne.value)
+
+    def cluster_density_stats(self):
+        """what this context's last cluster_tri_density_* call found: {cores, borders, noise, regrows, edge_capacity} (mg_cluster_density_stats)"""
+        v = [C.c_uint64(0) for _ in range(5)]
+        self._check(self.lib.mg_cluster_density_stats(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("cores", "borders", "noise", "regrows", "edge_capacity"), (int(x.value) for x in v)))
 
     def cluster_tri_complete_host(self, table, k, kmer_space, max_d=-1.0, max_p=-1.0):
         """complete-linkage clusters of the pairs compare_tri_results returns for the whole table, cut at the threshold, found on the

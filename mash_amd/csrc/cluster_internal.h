@@ -1,7 +1,7 @@
 // cluster_internal.h — launch interface between host_cluster.cpp and cluster.hip (single-linkage clusters of a thresholded triangle),
 // cluster_medoid.hip (the same clusters with their medoids), cluster_greedy.hip (greedy representative clusters of the same graph) and
-// cluster_forest.hip (its minimum spanning forest) and cluster_complete.hip (its complete-linkage clusters), and the lock-free
-// union-find that cluster.hip, cluster_medoid.hip and cluster_forest.hip share.
+// cluster_forest.hip (its minimum spanning forest), cluster_complete.hip (its complete-linkage clusters) and cluster_density.hip (its
+// density clusters), and the lock-free union-find that cluster.hip, cluster_medoid.hip, cluster_forest.hip and cluster_density.hip share.
 #pragma once
 #include "finish_internal.h"          // (under MG_HIP_EMU that header brings tools/hipemu: tests/test_cluster_emu.py)
 #include <stdint.h>
@@ -189,5 +189,21 @@ hipError_t launch_complete_begin(const uint4 *edges, uint64_t m, const CompleteB
 // `rounds` rounds as one batch (the launcher zeroes merged / live [0 .. rounds)): round r of the batch does nothing once round r - 1
 // of it merged nothing.  The fixpoint is the first merged[r] == 0; at most n rounds are ever needed.
 hipError_t launch_complete_rounds(const uint4 *edges, uint64_t m, const CompleteBufs &b, uint32_t n, uint32_t rounds, hipStream_t stream);
+
+// ---- cluster_density.hip
+// What the density passes work on, all of it written by launch_density (nothing has to be cleared before the call)
+struct DensityBufs {
+    uint32_t *deg, *parent;                    // [n] edges with an end at the row; the union-find over the cores
+    uint32_t *label, *via, *first;             // [n] the results; per label the smallest row filed under it
+    unsigned long long *best_key;              // [n] per row that is not a core: the best weight key among its edges to cores
+    unsigned long long *counts;                // [5] cores, borders, noise, clusters, scratch
+};
+// Everything behind the last append of {hi, lo, numer, denom} (launch_forest_append; an entry with hi == lo is skipped), queued as one
+// batch: deg[i] = edges at i; a row is a core iff deg >= min_neighbours; the cores united over the edges between two of them; a row
+// that is no core but has an edge to one is a border under via[i] = the core whose edge is best in the order of forest_key.h (equal
+// fractions: the smaller core); via[i] = i for cores and for the rest (noise); label[i] = the smallest row of i's cluster, borders
+// included; counts[0 .. 3] = cores, borders, noise, rows with label[i] == i.  Denominators must be below FOREST_DENOM_LIMIT.
+// plain_degree: two atomic adds per edge instead of one per run of equal rows in a wave; the same deg[].
+hipError_t launch_density(const uint4 *edges, uint64_t m, const DensityBufs &b, uint32_t n, uint32_t min_neighbours, bool plain_degree, hipStream_t stream);
 
 }  // namespace mg

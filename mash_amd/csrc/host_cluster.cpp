@@ -1,7 +1,7 @@
 // host_cluster.cpp -- the cluster entry points: the marked pairs of a thresholded triangle (cut_counts) united on the device
 // (cluster.hip, cluster_medoid.hip), or gathered as an edge list for the greedy rounds (cluster_greedy.hip), the minimum spanning
-// forest (cluster_forest.hip) and the complete-linkage rounds (cluster_complete.hip); an earlier clustering extended by new rows in
-// the first two forms
+// forest (cluster_forest.hip), the complete-linkage rounds (cluster_complete.hip) and the density passes (cluster_density.hip); an
+// earlier clustering extended by new rows in the first two forms
 #include "cut_internal.h"
 #include <deque>
 
@@ -640,5 +640,90 @@ int mg_cluster_complete_rounds(mg_ctx *ctx, uint64_t *live_out, uint64_t *merged
         live_out[r] = ctx->complete_live[r];
         merged_out[r] = ctx->complete_merged[r];
     }
+    return MG_OK;
+}
+
+
+/* ------------------------------------------------- density clusters (cluster_density.hip) */
+
+// where a density call wants its results; via and degree may be NULL
+struct DensityOut { uint32_t *label, *via, *degree; };
+
+// The whole triangle of t: the edge list with the pairs' counts (gather_edges: the list of `-B`, MASHGPU_GREEDY_EDGE_CAP its first
+// capacity), then ONE batch behind the last append -- degrees, the cores united, the borders' best keys and picks, the relabelling --
+// and one wait for it.  MASHGPU_DENSITY_PLAIN: two atomic adds per edge in the degree pass (the A/B of tools/cluster_density_bench.py;
+// the bits are the same).
+static int cluster_density(mg_ctx *ctx, const mg_table *t, const Cut &cut, uint32_t min_neighbours, const DensityOut &out, bool on_device,
+                           uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    *n_clusters_out = *n_edges_out = 0;
+    ctx->density_cores = ctx->density_borders = ctx->density_noise = ctx->density_regrows = ctx->density_edge_cap = 0;
+    if (!min_neighbours) return fail(ctx, MG_ERR_INVALID, "cluster density: min_neighbours is 0 (every row would be a core)");
+    ClusterJobs J;
+    int rc = cluster_jobs(ctx, nullptr, t, cut, false, &J, mg::FOREST_DENOM_LIMIT, "cluster density");
+    if (rc != MG_OK || !J.total) return rc;
+    const uint32_t n = J.total;
+    const bool plain = ctx_opt(ctx, "MASHGPU_DENSITY_PLAIN") != nullptr;
+    ForestEdges E(ctx);
+    if ((rc = gather_edges(ctx, J, cut, "MASHGPU_GREEDY_EDGE_CAP", E)) != MG_OK) return rc;
+    const bool own_via = !(on_device && out.via), own_deg = !(on_device && out.degree);
+    DevBuf<uint32_t> parent(ctx), first(ctx), label(ctx), via(ctx), deg(ctx);
+    DevBuf<unsigned long long> best_key(ctx), d_counts(ctx);
+    if (parent.alloc(n) != hipSuccess || first.alloc(n) != hipSuccess || best_key.alloc(n) != hipSuccess || d_counts.alloc(5) != hipSuccess ||
+        (!on_device && label.alloc(n) != hipSuccess) || (own_via && via.alloc(n) != hipSuccess) || (own_deg && deg.alloc(n) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(ctx, MG_ERR_NOMEM, "cluster: device allocation failed");
+    }
+    const mg::DensityBufs db{own_deg ? deg.p : out.degree, parent, on_device ? out.label : label.p, own_via ? via.p : out.via, first, best_key, d_counts};
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_TRY(ctx, mg::launch_density(E.buf, E.used, db, n, min_neighbours, plain, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h, d_counts, 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (!on_device) {
+        HIP_TRY(ctx, hipMemcpyAsync(out.label, db.label, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (out.via) HIP_TRY(ctx, hipMemcpyAsync(out.via, db.via, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (out.degree) HIP_TRY(ctx, hipMemcpyAsync(out.degree, db.deg, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (h[0] + h[1] + h[2] != n) return fail(ctx, MG_ERR_HIP, "cluster density: cores, borders and noise do not add up to the rows");
+    *n_clusters_out = h[3];
+    *n_edges_out = E.n_edges;
+    ctx->density_cores = h[0];
+    ctx->density_borders = h[1];
+    ctx->density_noise = h[2];
+    ctx->density_regrows = E.regrows;
+    ctx->density_edge_cap = E.cap;
+    return MG_OK;
+}
+
+int mg_cluster_tri_density_host(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                                uint32_t min_neighbours, uint32_t *label_out_host, uint32_t *via_out_host, uint32_t *degree_out_host,
+                                uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    const DensityOut out{label_out_host, via_out_host, degree_out_host};
+    return cluster_call(ctx, "mg_cluster_tri_density_host", nullptr, t, cut, n_clusters_out && n_edges_out && (label_out_host || !rows_of(t)), nullptr,
+                        nullptr, [&] { return cluster_density(ctx, t, cut, min_neighbours, out, false, n_clusters_out, n_edges_out); });
+}
+
+int mg_cluster_tri_density_dev(mg_ctx *ctx, const mg_table *t, int kmer_size, double kmer_space, double max_distance, double max_p_value,
+                               uint32_t min_neighbours, uint32_t *label_out_dev, uint32_t *via_out_dev, uint32_t *degree_out_dev,
+                               uint64_t *n_clusters_out, uint64_t *n_edges_out)
+{
+    const Cut cut{kmer_size, kmer_space, max_distance, max_p_value};
+    const DensityOut out{label_out_dev, via_out_dev, degree_out_dev};
+    return cluster_call(ctx, "mg_cluster_tri_density_dev", nullptr, t, cut, n_clusters_out && n_edges_out && (label_out_dev || !rows_of(t)), nullptr,
+                        nullptr, [&] { return cluster_density(ctx, t, cut, min_neighbours, out, true, n_clusters_out, n_edges_out); });
+}
+
+int mg_cluster_density_stats(mg_ctx *ctx, uint64_t *cores_out, uint64_t *borders_out, uint64_t *noise_out, uint64_t *regrows_out,
+                             uint64_t *edge_capacity_out)
+{
+    if (!ctx) return MG_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (cores_out) *cores_out = ctx->density_cores;
+    if (borders_out) *borders_out = ctx->density_borders;
+    if (noise_out) *noise_out = ctx->density_noise;
+    if (regrows_out) *regrows_out = ctx->density_regrows;
+    if (edge_capacity_out) *edge_capacity_out = ctx->density_edge_cap;
     return MG_OK;
 }

@@ -119,6 +119,8 @@ struct mg_ctx {
     // mg_cluster_complete_stats / mg_cluster_complete_rounds: the same for the last mg_cluster_tri_complete_* call
     uint64_t complete_rounds = 0, complete_batches = 0, complete_regrows = 0, complete_edge_cap = 0;
     std::vector<uint64_t> complete_live, complete_merged;   // per round, the links alive when it began and the links it merged
+    // mg_cluster_density_stats: the roles the last mg_cluster_tri_density_* call found, and its edge list
+    uint64_t density_cores = 0, density_borders = 0, density_noise = 0, density_regrows = 0, density_edge_cap = 0;
     // mg_spectrum_stats: the route the last mg_compare_*_spectrum_host call took (0: no pairs), the list entries it binned and those
     // of them with numer 0, the distinct keys with a denominator other than s, the times the table of those keys was enlarged
     uint64_t spectrum_route = 0, spectrum_listed = 0, spectrum_listed_zero = 0, spectrum_other_keys = 0, spectrum_regrows = 0;

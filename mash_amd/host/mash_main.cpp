@@ -2043,16 +2043,19 @@ int cmd_triangle(int argc, const char **argv)
 // best first, not cluster lines.
 // -L: complete-linkage clusters of the same pairs instead (mg_cluster_tri_complete_host): every two members of a cluster are an
 // edge; links merge best first by the exact fraction of their worst pair.  Lines and numbering are those of the plain run.
+// -D <m>: density clusters of the same pairs instead (mg_cluster_tri_density_host): a sketch with at least m edges is a core, cores
+// cluster over the edges between them, any other sketch with an edge to a core is a border under its nearest core, the rest is noise.
+// Lines get two more fields, the role and the number of edges; with -D 1 the first three fields are those of the plain run.
 // -A <earlier output>: the clusters of the first L inputs are read from an earlier run's stdout and only the pairs that touch a
 // later input are compared (cluster_extend below; include/mashgpu.h: mg_cluster_extend_host).  With plain and with -R only.
 // MASH_AMD_HOST_FINISH=1 is the host route, which the tests judge the device route by: the pairs within -d come from the host calls
 // of `triangle -E -d` and `dist -d` (tri_edge_blocks, rect_edge_blocks), and what follows is done here, once for every form
-// (cluster_on_host: Sets, greedy_walk, nearest_pick, medoid_pick; -T: Kruskal over the same Sets; -L: complete_walk).
+// (cluster_on_host: Sets, greedy_walk, nearest_pick, medoid_pick; -T: Kruskal over the same Sets; -L: complete_walk; -D: density_walk).
 
-enum ClusterMode { kSingle, kGreedy, kNearest, kMedoid, kForest, kComplete };      // plain, -R, -B (with or without -R), -M, -T, -L; -A is a flag beside it
+enum ClusterMode { kSingle, kGreedy, kNearest, kMedoid, kForest, kComplete, kDensity };      // plain, -R, -B (with or without -R), -M, -T, -L, -D; -A is a flag beside it
 
 // The lap of a form's clustering (MASH_AMD_TIMING=1) on the device and on the host route: kClusterLaps[mode][with -A]
-const struct { const char *device, *host; } kClusterLaps[6][2] = {
+const struct { const char *device, *host; } kClusterLaps[7][2] = {
     {{"compare+mark+union+label+copy", "compare+filter+copy+union"},
      {"seed+compare+mark+union (new x old, new x new)+label+copy", "compare+filter+copy (new x old, new x new)+union"}},
     {{"compare+mark+append+rounds+assign+copy", "compare+filter+copy+walk"},
@@ -2061,6 +2064,7 @@ const struct { const char *device, *host; } kClusterLaps[6][2] = {
     {{"compare+mark+union+score+label+pick+copy", "compare+filter+copy+union+score+pick"}},
     {{"compare+mark+append+rounds+sort+finish+copy", "compare+filter+copy+sort+kruskal"}},
     {{"compare+mark+append+index+rounds+label+copy", "compare+filter+copy+walk"}},
+    {{"compare+mark+append+degree+union+border+label+copy", "compare+filter+copy+degree+union+border"}},
 };
 
 // Union-find in place over a vector of labels: a set's root is its smallest member, so the first input of a cluster names it
@@ -2158,8 +2162,37 @@ void complete_walk(vector<uint32_t> &lab, const vector<mg_edge> &edges)
 }
 
 // What a run finds: per input its label, the first member of its cluster (-R, -B: its representative), and with -M its cluster's
-// medoid; or with -T the forest's records, best first
-struct Clusters { vector<uint32_t> lab, med; vector<mg_result> forest; };
+// medoid; or with -T the forest's records, best first; with -D (min_nb: its argument) per input the core it came in by and its edges
+struct Clusters { vector<uint32_t> lab, med; vector<mg_result> forest; uint32_t min_nb = 0; vector<uint32_t> via, deg; };
+
+// -D: the definition (include/mashgpu.h: mg_cluster_tri_density_host) over the kept edges: degrees, the cores united over the edges
+// between two of them, a border under the best of its edges to a core (mg::forest_before with the core in the row pair's place),
+// then every cluster named by its first member, borders included
+void density_walk(Clusters &c, const vector<mg_edge> &edges)
+{
+    vector<uint32_t> &lab = c.lab, &via = c.via, &deg = c.deg;
+    const uint64_t n = lab.size();
+    std::fill(deg.begin(), deg.end(), 0u);
+    for (const mg_edge &e : edges) { deg[e.row]++; deg[e.col]++; }
+    auto core = [&](uint32_t i) { return deg[i] >= c.min_nb; };
+    Sets sets{lab};
+    vector<const mg_edge *> best(n, nullptr);
+    for (uint64_t i = 0; i < n; i++) via[i] = (uint32_t)i;
+    for (const mg_edge &e : edges) {
+        if (core(e.row) && core(e.col)) sets.unite(e.row, e.col);
+        if (core(e.row) == core(e.col)) continue;
+        const uint32_t member = core(e.row) ? e.col : e.row, k = core(e.row) ? e.row : e.col;
+        const mg_edge *b = best[member];
+        if (!b || mg::forest_before(e.numer, e.denom, k, b->numer, b->denom, via[member])) {
+            best[member] = &e;
+            via[member] = k;
+        }
+    }
+    vector<uint32_t> root(n), first(n, 0xFFFFFFFFu);
+    for (uint64_t i = 0; i < n; i++) root[i] = sets.find(via[i]);
+    for (uint64_t i = 0; i < n; i++) first[root[i]] = std::min(first[root[i]], (uint32_t)i);
+    for (uint64_t i = 0; i < n; i++) lab[i] = first[root[i]];
+}
 
 // The host route of every form, with and without -A, from the passing edges.  Inputs below `first` are decided already and lab
 // holds their labels (-A: first == L; else 0).  passing_edges(take) calls take(edge, pair) for every edge that passes -d and -v,
@@ -2173,13 +2206,13 @@ int cluster_on_host(ClusterMode mode, uint64_t first, Clusters &c, Source passin
     for (uint64_t i = first; i < n; i++) lab[i] = (uint32_t)i;
     Sets sets{lab};
     vector<vector<uint32_t>> smaller(greedy ? n - first : 0);
-    vector<mg_edge> kept;                                      // -B, -L: every edge with its counts
+    vector<mg_edge> kept;                                      // -B, -L, -D: every edge with its counts
     vector<uint64_t> score(mode == kMedoid ? n : 0);           // -M: per input the sum of its edges' weights
     vector<mg_result> all;                                     // -T: every edge as the record of its line
     if (passing_edges([&](const mg_edge &e, const mg_pair &pr) {
             if (mode == kForest) {
                 all.push_back(mg_result{e.row, e.col, pr.numer, pr.denom, pr.distance, pr.p_value});
-            } else if (mode == kComplete) {
+            } else if (mode == kComplete || mode == kDensity) {
                 kept.push_back(e);
             } else if (greedy) {
                 smaller[std::max(e.row, e.col) - first].push_back(std::min(e.row, e.col));
@@ -2201,6 +2234,8 @@ int cluster_on_host(ClusterMode mode, uint64_t first, Clusters &c, Source passin
             if (sets.unite(e.row, e.col)) c.forest.push_back(e);
     } else if (mode == kComplete) {
         complete_walk(lab, kept);
+    } else if (mode == kDensity) {
+        density_walk(c, kept);
     } else if (greedy) {
         greedy_walk(lab, first, smaller);
         if (mode == kNearest) nearest_pick(lab, kept);
@@ -2238,6 +2273,9 @@ int cluster_table(TriRun &r, ClusterMode mode, Clusters &c)
         rc = mg_cluster_tri_forest_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.forest.data(), c.forest.size(), &count, nullptr, &n_clusters, &n_edges);
         break;
     case kComplete: rc = mg_cluster_tri_complete_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.lab.data(), &n_clusters, &n_edges); break;
+    case kDensity:
+        rc = mg_cluster_tri_density_host(r.gpu.ctx, r.t, r.kmer, r.kspace, r.d_max, r.p_max, c.min_nb, c.lab.data(), c.via.data(), c.deg.data(), &n_clusters, &n_edges);
+        break;
     }
     if (rc != MG_OK) return report_error(r.gpu);
     c.forest.resize(count);
@@ -2360,6 +2398,7 @@ int cmd_cluster(int argc, const char **argv)
     c.add("assign", Opt::File, "A");
     c.add("medoid", Opt::Boolean, "M");
     c.add("complete", Opt::Boolean, "L");
+    c.add("density", Opt::Integer, "D", "", 1, (float)0x7FFFFFFF);
     c.add("pvalue", Opt::Number, "v", "1.0", 0., 1.);
     c.add("distance", Opt::Number, "d", "0.05", 0., 1.);
     c.use_sketch_options();
@@ -2407,7 +2446,17 @@ int cmd_cluster(int argc, const char **argv)
                 "            first in the input, then to the one whose earlier cluster does, until no link is left.  The\n"
                 "            result depends on the edges and their shared-hashes alone.  Output fields and numbering are\n"
                 "            those of the plain run.  Not with -R, -B, -M or -T.  Not with -A: merges among the earlier\n"
-                "            inputs are not a function of the pairs -A compares.\n\n";
+                "            inputs are not a function of the pairs -A compares.\n"
+                "  -D <int>  Density clusters (DBSCAN) instead of single linkage (1-2147483647).  A sketch with at least <int>\n"
+                "            edges, that is <int> OTHER sketches within the threshold, is a core (the classic minPts, which\n"
+                "            counts the sketch itself, is <int> + 1).  Clusters are the connected components of the cores\n"
+                "            under the edges between two cores.  Any other sketch with an edge to a core is a border and joins\n"
+                "            the cluster of its nearest core: the larger shared-hashes as an exact fraction, equal fractions to\n"
+                "            the earlier core.  A border never joins two clusters, so a thin bridge between two groups does\n"
+                "            not chain them.  The rest is noise, each a cluster of its own.  Output gets two more fields,\n"
+                "            [cluster-number, cluster-size, ID, role, neighbours]: role is core, border or noise, neighbours\n"
+                "            the number of the sketch's edges.  Numbering is that of the plain run, from 1 by first member;\n"
+                "            with -D 1 the first three fields are the plain run's.  Not with -R, -B, -T, -A, -M or -L.\n\n";
         return 0;
     }
     const bool comment = c.o("comment").active, extend = c.o("assign").active;
@@ -2419,6 +2468,8 @@ int cmd_cluster(int argc, const char **argv)
         {"best", "tree", ""}, {"best", "assign", " (a new representative can be nearer to an earlier member)"},
         {"tree", "representatives", ""}, {"tree", "assign", ""},
         {"complete", "representatives", ""}, {"complete", "best", ""}, {"complete", "medoid", ""}, {"complete", "tree", ""}, {"complete", "assign", ""},
+        {"density", "representatives", ""}, {"density", "best", ""}, {"density", "tree", ""},
+        {"density", "assign", " (a new input changes the degrees, and so the roles, of earlier ones)"}, {"density", "medoid", ""}, {"density", "complete", ""},
     };
     for (const auto &x : refusals) {
         if (!c.o(x.a).active || !c.o(x.b).active) continue;
@@ -2432,7 +2483,13 @@ int cmd_cluster(int argc, const char **argv)
     Params p;
     if (sketch_parameter_setup(p, c)) return 1;
     if (c.args.size() == 1 && !c.o("list").active) p.concatenated = false;   // as `mash triangle` (CommandTriangle.cpp:74-77)
-    const ClusterMode mode = c.o("complete").active ? kComplete : c.o("tree").active ? kForest : c.o("medoid").active ? kMedoid : c.o("best").active ? kNearest
+    // (-D: the option holds a float, exact to 2^24 only: the count is read from the text the parser has accepted)
+    const uint64_t min_nb = c.o("density").active ? strtoull(c.o("density").arg.c_str(), nullptr, 10) : 0;
+    if (c.o("density").active && (min_nb < 1 || min_nb > 0x7FFFFFFFull)) {
+        cerr << "ERROR: Argument to -" << c.o("density").id << " must be an integer between 1 and 2147483647 (" << c.o("density").arg << " given)" << endl;
+        return 1;
+    }
+    const ClusterMode mode = c.o("density").active ? kDensity : c.o("complete").active ? kComplete : c.o("tree").active ? kForest : c.o("medoid").active ? kMedoid : c.o("best").active ? kNearest
                              : c.o("representatives").active ? kGreedy : kSingle;
     Earlier old;
     if (extend && !read_earlier(c.o("assign").arg, old)) return 1;           // (before a device is opened)
@@ -2456,7 +2513,8 @@ int cmd_cluster(int argc, const char **argv)
         }
     }
     if (n == 0) return 0;
-    Clusters found{vector<uint32_t>(n), vector<uint32_t>(mode == kMedoid ? n : 0), {}};
+    Clusters found{vector<uint32_t>(n), vector<uint32_t>(mode == kMedoid ? n : 0), {}, (uint32_t)min_nb, vector<uint32_t>(mode == kDensity ? n : 0),
+                   vector<uint32_t>(mode == kDensity ? n : 0)};
     auto print_clusters = [&](FastOut &out) {
         // label = the cluster's first member: numbers in order of first appearance are numbers by ascending label
         const vector<uint32_t> &lab = found.lab, &med = found.med;
@@ -2470,6 +2528,7 @@ int cmd_cluster(int argc, const char **argv)
             out << number[lab[i]] << '\t' << size[lab[i]] << '\t' << label(i);
             if (mode == kNearest) out << '\t' << label(lab[i]);
             if (mode == kMedoid) out << '\t' << label(med[i]);
+            if (mode == kDensity) out << '\t' << (found.deg[i] >= min_nb ? "core" : found.via[i] != i ? "border" : "noise") << '\t' << found.deg[i];
             out.eol();
         }
     };
@@ -3028,7 +3087,7 @@ int main(int argc, const char **argv)
         "  dist      Estimate the distance of query sequences to references, or the spectrum of those distances (-H).\n"
         "  within    Estimate the containment of query sequences within references.\n"
         "  triangle  Estimate a lower-triangular distance matrix, or the spectrum of its distances (-H).\n"
-        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), name each single-linkage cluster's medoid (-M), extend an earlier clustering by new sequences (-A), print the minimum spanning forest (-T), or form complete-linkage clusters, every two members within the distance (-L).\n  info      Display information about sketch files.\n"
+        "  cluster   Group sequences into single-linkage or greedy representative (-R) clusters by distance, file members under their nearest representative (-B), name each single-linkage cluster's medoid (-M), extend an earlier clustering by new sequences (-A), print the minimum spanning forest (-T), form complete-linkage clusters, every two members within the distance (-L), or form density clusters of cores, borders and noise (-D).\n  info      Display information about sketch files.\n"
         "  paste     Create a single sketch file from multiple sketch files.\n"
         "  screen    Determine whether query sequences are within a larger mixture of sequences.\n"
         "  taxscreen Create Kraken-style taxonomic report based on mash screen.\n"
